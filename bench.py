@@ -1,9 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec of the MI355X-native Faster-R-CNN/FPN detection hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: it builds the inputs, warms up, times exactly K steps and prints the line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, `config`,
+`multi_rank`, a short `summary`).  `--dump-outputs DIR` then also writes what the timed path computed in its last step
+(rank 0's in-flight images: detections, proposals, detection records, pooled RoI features as per-RoI sums plus a fixed,
+seeded sample of RoIs) as DIR/<name>.npy, float32 / float64, < 64 MB; the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.  Everything else the benchmark measures (`roofline`, `cpu_baseline`,
+`value_clustered`, the side file below) runs only with `--full`.
 
 Workload (BASELINE.json metric "images/sec ResNet-101-FPN @ 800x1333", configs[2]): every image goes
 through region_proposal -> roi_pooling -> prediction (+ anchor generation, fg softmax, level assignment)
@@ -21,7 +29,7 @@ thread of the library) carry `--batch` images each whose kernels share their lau
 step); with N > 1 every round of streams x batch images ends with ONE RCCL all-gather of the fixed-size
 detection records.
 
-Prints ONE JSON line (rank 0), <= 8 KB (LINE_LIMIT; asserted in tests/test_bench_contract.py), with the driver's contract plus
+With `--full` it prints ONE JSON line (rank 0), <= 8 KB (LINE_LIMIT; asserted in tests/test_bench_contract.py), with the driver's contract plus
   `roofline`     dominant kernel = the fused RoI crop+pool kernel (HBM bound), the 8-image launch of one stream
                  group: >= 10 launches in a short phase AFTER the timed region, each alone on the GPU with cold
                  maps, HIP events attached to the dispatch.  Those launches run under their own kernel name
@@ -53,7 +61,7 @@ any of those legs costs that leg: the parent prints its line regardless.  The si
                  as one HIP graph), ResNet-50 C4 and VGG16 (BASELINE configs 2 and 1), and the accuracy gates
                  `map_delta_vs_fp32` (a mode vs the exact-float32 detector on identical weights and annotated synthetic
                  scenes, the reference's evaluation loop; `ci_inside_bar` = both ends of the paired-bootstrap CI95 within +-0.002).
-The whole default run aims at `--time-budget` (190 s): the gates run on as many scenes as fit.
+The whole `--full` run aims at `--time-budget` (190 s): the gates run on as many scenes as fit.
 """
 import argparse
 import ctypes
@@ -427,6 +435,52 @@ def compact_line(result):
     return line
 
 
+DUMP_LIMIT = 64 << 20         # bytes of all the .npy files of --dump-outputs together
+DUMP_FEATURE_BYTES = 48 << 20  # of which the sampled pooled RoI features take at most this much
+DUMP_FEATURE_ROIS = 32        # RoIs per image whose pooled features are written in full (fewer when many images are in flight)
+DUMP_SEED = 2025              # fixes which RoIs those are
+
+
+def dump_outputs(slots, records, out_dir):
+    """What the timed path computed in its last step, for every in-flight image of this rank (slot order), as
+    out_dir/<name>.npy in float32 (float64 for counts and sums):
+      det_boxes [n, M, 4], det_labels [n, M], det_scores [n, M], det_count [n]   what post_ops returns for each image
+      proposals [n, K, 4], proposal_count [n]                                    the RPN's proposals in level order
+      records [n, M * 6 + 1]                                                     the fixed-size detection records
+      roi_feature_sums [n, K]                                  each RoI's pooled features summed in float64 (all of them)
+      roi_features_sample [n, R, P, P, C], roi_features_sample_rows [R]        the pooled features of R fixed, seeded RoIs
+    Rows past an image's count hold what the buffers held before (the path writes the first `count` rows only).
+    Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(slots)
+    K = slots[0].roi_features.shape[0]
+    row_bytes = int(np.prod(slots[0].roi_features.shape[1:])) * 4
+    n_rows = max(1, min(DUMP_FEATURE_ROIS, K, DUMP_FEATURE_BYTES // (n * row_bytes)))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(K, n_rows, replace=False))
+    rows_t = torch.from_numpy(rows).to(slots[0].roi_features.device)
+
+    def stack(fn, dtype=np.float32):
+        return np.stack([fn(h).detach().cpu().numpy() for h in slots]).astype(dtype)
+    out = {
+        'det_boxes': stack(lambda h: h.det_boxes),
+        'det_labels': stack(lambda h: h.det_labels),
+        'det_scores': stack(lambda h: h.det_scores),
+        'det_count': stack(lambda h: h.det_count[0], np.float64),
+        'proposals': stack(lambda h: h.sorted_rois),
+        'proposal_count': stack(lambda h: h.roi_count[0], np.float64),
+        'records': records.detach().cpu().numpy().astype(np.float32),
+        'roi_feature_sums': stack(lambda h: h.roi_features.reshape(K, -1).double().sum(1), np.float64),
+        'roi_features_sample': stack(lambda h: h.roi_features.index_select(0, rows_t).float()),
+        'roi_features_sample_rows': rows.astype(np.float64),
+    }
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit('--dump-outputs: %d bytes for %d images exceed the %d-byte limit' % (total, n, DUMP_LIMIT))
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return {name: a.shape for name, a in out.items()}
+
+
 
 def self_launch(n, argv):
     """`python bench.py --gpus N` without a launcher's environment: start `python -m torch.distributed.run --nnodes=1
@@ -479,18 +533,26 @@ def main():
     ap.add_argument('--backend', default='nccl', help="torch.distributed backend for --gpus > 1 ('nccl' = RCCL; "
                     "'gloo' only to rehearse the multi-rank path on a box with fewer GPUs than ranks)")
     ap.add_argument('--time-budget', type=float, default=190.0,
-                    help='seconds the whole run aims to stay within: the accuracy gates of the detail process run on as many '
+                    help='seconds the whole --full run aims to stay within: the accuracy gates of the detail process run on as many '
                          'scenes as fit (recorded as gate_scenes_reduced_to; --time-budget 900 runs them at full size); the '
                          'headline legs are never shortened')
     ap.add_argument('--detail-out', default=os.path.join(ROOT, 'bench_detail.json'),
-                    help='side file of the N = 1 run: config 5, every end-to-end leg and every gate record (the stdout line keeps '
+                    help='side file of the N = 1 --full run: config 5, every end-to-end leg and every gate record (the stdout line keeps '
                          'their headline figures in `summary`)')
     ap.add_argument('--detail-child', default=None, help=argparse.SUPPRESS)    # (internal: this process IS the detail child)
     ap.add_argument('--trace', action='store_true', help='phase time stamps on stderr (synchronises at every mark)')
     ap.add_argument('--force-collective', action='store_true',
                     help='with ONE rank under torch.distributed.run: still issue the all-gather of every stream group (the RCCL '
                          'call path rehearsed on a 1-GPU box)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline as well: the roofline phase, the other RPN score distribution, the CPU '
+                         'baseline and (N = 1) the detail process (config 5, end-to-end legs, accuracy gates); the --no-* '
+                         'options leave parts of it out')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N`: this process has not touched the GPU (importing torch and counting devices do
@@ -890,13 +952,16 @@ def main():
         run_detail(args.detail_child)
         return
 
-    # ---- the headline: SURVEY 8(d)'s distribution (or --scores), then the OTHER distribution beside it
+    # ---- the headline: SURVEY 8(d)'s distribution (or --scores); with --full the OTHER distribution beside it
+    full = args.full
     wl = Workload(cfg3, args.scores, args.nms_first_chunk, args.blind_chunks)
     elapsed, replans = wl.measure(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:                           # (before anything else launches on the slots' buffers)
+        dump_outputs(wl.pool.slots, wl.records, args.dump_outputs)
     per_rank_s, allgathers, nms_reruns = wl.per_rank_s, wl.allgathers, wl.nms_reruns
     host = wl.host
     rf, k_kept, plan0, rec_len0 = None, int(wl.pool.slots[0].roi_count.item()), (wl.nms_first_chunk, wl.blind_chunks), wl.rec_len
-    if rank == 0:
+    if full and rank == 0:
         rf = roofline_phase(wl, args.roofline_samples, 'k_roi_pool<MAX2, NORM_IMAGE> (fused crop_and_resize 14x14 + 2x2 max)',
                             'fpn_hot_path_800x1333_r101fpn_%s%s' % (args.scores, '' if args.maps == 'f32' else '_f16maps'))
         mark('roofline + calibration done')
@@ -905,7 +970,7 @@ def main():
     torch.cuda.empty_cache()
     other_kind = 'clustered' if args.scores == 'distinct' else 'distinct'
     other = None
-    if not args.no_second_distribution:
+    if full and not args.no_second_distribution:
         wl2 = Workload(cfg3, other_kind, args.nms_first_chunk, args.blind_chunks)
         el2, rp2 = wl2.measure(args.steps, args.warmup)
         other = {'value': args.steps * images_per_step * world / el2, 'unit': 'img/s', 'ms_per_step': el2 / args.steps * 1e3,
@@ -935,8 +1000,9 @@ def main():
                        'blind_chunks': plan0[1], 'replanned': replans, 'nms_reruns': nms_reruns,
                        'streams_per_gpu': S, 'images_per_launch': B, 'images_in_flight_per_gpu': S * B,
                        'proposals_kept': k, 'parallelism': 'image-parallel x%d' % world},
-            'roofline': rf,
         }
+        if full:
+            result['roofline'] = rf
         if other is not None:
             # the same path on the other RPN score distribution, its own timed region of the same length (a trained RPN
             # clusters its best anchors: greedy NMS suppresses most of the first candidates and needs a wider chunk)
@@ -958,14 +1024,15 @@ def main():
             'per_rank_spread': (max(rates) - min(rates)) / max(rates),
             'images_per_rank': args.steps * images_per_step,
         }
-        summary = {'hot_path_img_s': round(result['value'], 1), 'hot_path_clustered_img_s': round(other['value'], 1) if other else None,
-                   'roi_frac_B_roi': round(result['roofline']['frac'], 3),
-                   'roi_frac_counter_bytes': (round(result['roofline']['hbm_frac_measured'], 3)
-                                              if result['roofline']['hbm_frac_measured'] else None),
-                   'roi_frac_physical': 'roi_frac_counter_bytes',
-                   'roi_kernel_us': round(result['roofline']['kernel_ms'] * 1e3, 1),
-                   'roi_vs_calibration': round(result['roofline']['calibration']['roi_kernel_vs_calibration'], 3)}
-        if not args.no_cpu_baseline and world == 1:
+        summary = {'hot_path_img_s': round(result['value'], 1)}
+        if full:
+            summary.update({'hot_path_clustered_img_s': round(other['value'], 1) if other else None,
+                            'roi_frac_B_roi': round(rf['frac'], 3),
+                            'roi_frac_counter_bytes': round(rf['hbm_frac_measured'], 3) if rf['hbm_frac_measured'] else None,
+                            'roi_frac_physical': 'roi_frac_counter_bytes',
+                            'roi_kernel_us': round(rf['kernel_ms'] * 1e3, 1),
+                            'roi_vs_calibration': round(rf['calibration']['roi_kernel_vs_calibration'], 3)})
+        if full and not args.no_cpu_baseline and world == 1:
             try:
                 result['cpu_baseline'] = cpu_baseline(host, IMAGE_SHAPE)
                 cb = result['cpu_baseline']
@@ -974,7 +1041,7 @@ def main():
                 result['cpu_baseline'] = {'error': '%s: %s' % (type(ex).__name__, ex), 'kind': 'port', 'value': None, 'unit': 'img/s',
                                           'cores': None, 'sample': None}
             mark('cpu baseline done')
-        if world == 1 and not (args.no_e2e and args.no_config5):
+        if full and world == 1 and not (args.no_e2e and args.no_config5):
             # ---- everything that is not the headline runs in a FRESH CHILD PROCESS (never an exec of this one, which holds the
             # GPU) under a timeout: a hang or a GPU fault in any of its legs costs that leg, not the line.  Its records go to
             # the side file (and its progress to stderr); this line keeps their headline figures in `summary`.

@@ -1,6 +1,7 @@
-"""bench.py's output contract: ONE JSON line of <= 8 KB with the driver's keys, the roofline and cpu_baseline objects; the
-secondary records (config 5, the end-to-end legs, the accuracy gates) in a side file written by a child process; the
-multi-rank path is rehearsed in tests/test_parallel_gloo.py and here (--gpus 2 / 4 over gloo on one card)."""
+"""bench.py's output contract: a plain run prints ONE JSON line with the driver's keys and nothing it does not need (and
+writes the last step's outputs with --dump-outputs); with --full the line of <= 8 KB also holds the roofline and cpu_baseline
+objects, and the secondary records (config 5, the end-to-end legs, the accuracy gates) go to a side file written by a child
+process; the multi-rank path is rehearsed in tests/test_parallel_gloo.py and here (--gpus 2 / 4 over gloo on one card)."""
 import json
 import os
 import subprocess
@@ -89,10 +90,11 @@ def test_detail_child_hang_does_not_cost_the_line(tmp_path, monkeypatch):
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys(tmp_path):
-    # (the driver's own command line plus --no-e2e: the end-to-end detector records and their accuracy gates take minutes)
+    # (the driver's own command line with --full, plus --no-e2e: the end-to-end detector records and their accuracy gates
+    # take minutes)
     side = str(tmp_path / 'detail.json')
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '5',
-                        '--no-e2e', '--detail-out', side], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        '--full', '--no-e2e', '--detail-out', side], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
     assert len(lines) == 1 and len(lines[0]) <= LINE_LIMIT
@@ -160,7 +162,7 @@ def test_bench_e2e_summary_keys(tmp_path):
     accuracy gates -- in the side file -- and the summary of the line that carries their figures"""
     side = str(tmp_path / 'detail.json')
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1',
-                        '--no-cpu-baseline', '--no-config5', '--no-second-distribution', '--gate-images', '256',
+                        '--full', '--no-cpu-baseline', '--no-config5', '--no-second-distribution', '--gate-images', '256',
                         '--time-budget', '900', '--detail-out', side], cwd=ROOT,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1200)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
@@ -241,3 +243,96 @@ def test_bench_gpus_4_at_the_drivers_step_counts_prints_one_small_line():
     assert mr['allgathers_in_timed_region'] == mr['allgathers_expected'] == 20 * 48 * d['config']['streams_per_gpu']
     assert d['config']['global_batch'] == 4 * d['config']['images_per_step_per_gpu'] and d['config']['nms_reruns'] == 0
     assert 'cpu_baseline' not in d and 'detail' not in d and list(d)[-1] == 'summary' and d['summary']['ranks'][0] == 4
+
+
+def _fake_slots(n, K, M, P, C, seed=0):
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(seed)
+    return [types.SimpleNamespace(
+        det_boxes=torch.rand((M, 4), generator=g), det_labels=torch.randint(0, 21, (M,), generator=g, dtype=torch.int32),
+        det_scores=torch.rand(M, generator=g), det_count=torch.tensor([M - s], dtype=torch.int32),
+        sorted_rois=torch.rand((K, 4), generator=g), roi_count=torch.tensor([K], dtype=torch.int32),
+        roi_features=torch.randn((K, P, P, C), generator=g).to(torch.float16 if s % 2 else torch.float32))
+        for s in range(n)], torch.from_numpy(np.arange(n * (M * 6 + 1), dtype=np.float32).reshape(n, M * 6 + 1))
+
+
+def test_dump_outputs_writes_the_last_steps_arrays_within_the_limit(tmp_path, monkeypatch):
+    """(CPU) --dump-outputs: every array of the path's outputs as <name>.npy in float32 / float64, the pooled features as
+    per-RoI float64 sums plus the full features of a fixed, seeded choice of RoIs (the same rows in every run), < 64 MB"""
+    import numpy as np
+    bench = _bench_module()
+    slots, records = _fake_slots(3, 100, 5, 7, 16)
+    shapes = bench.dump_outputs(slots, records, str(tmp_path / 'a'))
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == sorted(k + '.npy' for k in shapes) and len(files) == 10
+    d = {k: np.load(str(tmp_path / 'a' / (k + '.npy'))) for k in shapes}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert d['det_boxes'].shape == (3, 5, 4) and d['det_count'].tolist() == [5, 4, 3] and d['records'].shape == (3, 31)
+    np.testing.assert_array_equal(d['det_labels'][1], slots[1].det_labels.numpy())
+    np.testing.assert_array_equal(d['proposals'][2], slots[2].sorted_rois.numpy())
+    rows = d['roi_features_sample_rows'].astype(np.int64)
+    assert len(rows) == 32 and np.all(np.diff(rows) > 0)
+    for s in range(3):
+        f = slots[s].roi_features.float().numpy()
+        np.testing.assert_array_equal(d['roi_features_sample'][s], f[rows])
+        np.testing.assert_allclose(d['roi_feature_sums'][s], f.reshape(100, -1).astype(np.float64).sum(1), rtol=1e-12, atol=1e-9)
+    bench.dump_outputs(slots, records, str(tmp_path / 'b'))            # same rows, same bytes
+    for k in shapes:
+        assert open(str(tmp_path / 'a' / (k + '.npy')), 'rb').read() == open(str(tmp_path / 'b' / (k + '.npy')), 'rb').read()
+    # the default arrangement (24 images in flight, 1000 RoIs of 7 x 7 x 256) stays under the limit; fewer sampled RoIs when
+    # more images are in flight; and a dump that would still outgrow the limit is an error, not a silent truncation
+    n, row = 24, 7 * 7 * 256 * 4
+    assert 24 * (min(32, bench.DUMP_FEATURE_BYTES // (n * row)) * row + 1000 * (16 + 8) + 50 * 24 + 301 * 4 + 16) < bench.DUMP_LIMIT
+    monkeypatch.setattr(bench, 'DUMP_FEATURE_BYTES', 3 * 8 * 7 * 7 * 16 * 4)
+    assert bench.dump_outputs(slots, records, str(tmp_path / 'c'))['roi_features_sample'][1] == 8
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 1000)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(slots, records, str(tmp_path / 'd'))
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """The plain command (no --full) times exactly --steps steps, prints the driver's keys and nothing that needs runs of its
+    own, and --dump-outputs writes what the timed path computed: image 0 of the last step is the oracle's answer on the
+    seeded inputs (proposals in level order, detections, pooled features of the sampled RoIs)."""
+    import numpy as np
+    from oracle import c_oracle as co
+    from tf_eager_object_detection_amd.pipeline import synthetic_fpn_inputs
+    out = tmp_path / 'dump'
+    d = _one_line([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                   '--dump-outputs', str(out)], timeout=600)
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'n_gpus', 'steps', 'warmup', 'config'):
+        assert k in d, k
+    for k in ('roofline', 'cpu_baseline', 'detail', 'value_clustered'):
+        assert k not in d, k
+    assert d['metric'] == 'images/sec' and d['unit'] == 'img/s' and d['higher_is_better'] is True and d['dtype'] == 'f32'
+    ips = d['config']['images_per_step_per_gpu']
+    assert d['steps'] == 3 and d['config']['timed_images'] == 3 * ips
+    assert abs(d['ms_per_step'] * 3 - d['config']['timed_region_s'] * 1e3) < 1e-6 * d['ms_per_step']
+    assert abs(d['ms_per_step'] * d['value'] / (1000.0 * ips) - 1.0) < 1e-6 and list(d)[-1] == 'summary'
+    a = {f[:-4]: np.load(str(out / f)) for f in os.listdir(out)}
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    n = d['config']['images_in_flight_per_gpu']
+    assert a['det_count'].shape == (n,) and a['proposal_count'].tolist() == [1000] * n
+    rows = a['roi_features_sample_rows'].astype(np.int64)
+    np.testing.assert_allclose(a['roi_feature_sums'][:, rows],
+                               a['roi_features_sample'].reshape(n, len(rows), -1).astype(np.float64).sum(2), rtol=1e-9, atol=1e-6)
+    # image 0 = the seeded inputs the bench gives slot 0, through the oracle
+    shape = (800, 1333)
+    host, _ = synthetic_fpn_inputs(shape, 21, 1000, 256, seed=1234, device='cpu')
+    rois, _ = co.region_proposal(host['rpn_deltas'], co.fpn_anchors(shape), co.rpn_fg_fpn(host['rpn_logits']), shape, 1000, 0.7)
+    lv, perm, _ = co.assign_levels(rois)
+    srois, slv = rois[perm], lv[perm]
+    np.testing.assert_array_equal(a['proposals'][0], srois)
+    for r in rows:
+        want = co.roi_pool(host['feats'][int(slv[r]) - 2], srois[r:r + 1], image_shape=shape, pool=7)[0]
+        np.testing.assert_array_equal(a['roi_features_sample'][0, list(rows).index(r)], want)
+    wb, wl, ws = co.post_ops(host['cls_scores'], host['cls_deltas'], srois, shape, [0, 0, 0, 0], [.1, .1, .2, .2],
+                             50, 50, 0.3, 0.0, 16, 21)
+    m = int(a['det_count'][0])
+    assert m == len(ws)
+    np.testing.assert_array_equal(a['det_labels'][0, :m], wl)
+    np.testing.assert_array_equal(a['det_scores'][0, :m], ws)
+    assert m == 0 or np.max(np.abs(a['det_boxes'][0, :m] - wb)) <= 1e-4 * max(1.0, float(np.abs(wb).max()))
