@@ -35,7 +35,8 @@ extern "C" {
  * workspace.  102: the odet_*_x2 entry points (two float16 limbs) and odet_split_f16x2; odet_bias_relu_maxpool keeps a NaN
  * in float32.  103: the two-limb launches report an out-of-range activation in a status word of their workspace
  * (odet_x2_status_offset); the tile-forcing diagnostics left this header and the shipped library (include/odet_diag.h, a
- * separate -DODET_DIAG build). */
+ * separate -DODET_DIAG build).  Added within 103: odet_preprocess_images (the eval loaders' input front end); no existing
+ * entry point or struct changed. */
 #define ODET_VERSION 103
 
 #define ODET_OK 0
@@ -331,6 +332,34 @@ int odet_eval_detect(const float* scores, const float* deltas, const float* rois
                      float score_threshold, float min_size, float* out_boxes, int32_t* out_labels,
                      float* out_scores, int32_t* out_count, void* workspace,
                      size_t workspace_bytes, odet_stream_t stream);
+
+/* ---- eval input front end ------------------------------------------------------------- */
+
+#define ODET_PREP_VOC 0
+#define ODET_PREP_COCO 1
+#define ODET_PREP_CAFFE 0
+#define ODET_PREP_TF 1
+#define ODET_PREP_MAX_BATCH 64       /* the detectors' max_batch limit */
+#define ODET_PREP_MAX_RAW_W 4096     /* raw pixels per row (two staged rows: 96 KB of LDS) */
+#define ODET_PREP_MAX_RAW_H 65536
+#define ODET_PREP_MAX_OUT 8192       /* output H and W */
+/* The reference's eval preprocessing, decoded uint8 HWC images -> one NHWC batch out [B, H, W, 3] (float32, or float16
+ * when f16 = 1: the float32 result rounded once to nearest even), in one launch; no host sync, no host->device copy.
+ * Host arrays [B]: images (device pointers), raw_h, raw_w, row_pitch (bytes between rows, >= 3 * raw_w); means: host
+ * double[3] in BGR order (may be NULL for preprocessing = ODET_PREP_TF).  out must be 16-byte aligned.  H x W is the
+ * caller's (both loaders truncate scale * size; the two rules differ, see preprocess.py).
+ *  pipeline ODET_PREP_VOC = dataset/eval_pascal_tf_dataset.py:32-52 (_map_from_cv2): BGR input; caffe:
+ *    float32(float64(u) - means[c]) (:37, numpy promotes float32 -= float64[3]); tf: ((float32(u) / 255) * 2) - 1 (:39);
+ *    cv2.resize INTER_LINEAR on float32 (:48; INTER_AREA when both axes shrink by exactly 2, as OpenCV switches);
+ *    rgb = 1 flips the result to RGB (:50-51).
+ *  pipeline ODET_PREP_COCO = dataset/utils/tf_dataset_utils.py:128-155 (preprocessing_eval_func): RGB input; caffe
+ *    (:55-71): reversed to BGR, float32(u) - float32(means[c]); tf (:74-80): ((float32(u) * float32(1/255)) * 2) - 1, RGB;
+ *    tf.image.resize_bilinear of TF 1.x (align_corners=False, the index math of odet_fpn_topdown_merge).  rgb must be 0.
+ * B == 0 is a no-op.  Errors: ODET_E_INVALID (null pointer, bad size / mode, misaligned out), ODET_E_LIMIT (B > 64,
+ * sizes above the limits above). */
+int odet_preprocess_images(const void* const* images, const int* raw_h, const int* raw_w, const long long* row_pitch,
+                           int B, int H, int W, int pipeline, int preprocessing, int rgb, const double* means, void* out,
+                           int f16, odet_stream_t stream);
 
 /* ---- FPN neck: top-down merge -------------------------------------- */
 

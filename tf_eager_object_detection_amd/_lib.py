@@ -105,6 +105,7 @@ SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'odet_eval_detect': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _f, _f, _f,
                               _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'odet_preprocess_images': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'odet_pack_detections': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     'odet_fpn_step_sizeof': (_sz, []),
     'odet_fpn_topdown_merge': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp]),
