@@ -35,8 +35,8 @@ extern "C" {
  * workspace.  102: the odet_*_x2 entry points (two float16 limbs) and odet_split_f16x2; odet_bias_relu_maxpool keeps a NaN
  * in float32.  103: the two-limb launches report an out-of-range activation in a status word of their workspace
  * (odet_x2_status_offset); the tile-forcing diagnostics left this header and the shipped library (include/odet_diag.h, a
- * separate -DODET_DIAG build).  Added within 103: odet_preprocess_images (the eval loaders' input front end); no existing
- * entry point or struct changed. */
+ * separate -DODET_DIAG build).  Added within 103: odet_preprocess_images (the eval loaders' input front end),
+ * odet_eval_detect_topk and the odet_coco_* evaluation; no existing entry point or struct changed. */
 #define ODET_VERSION 103
 
 #define ODET_OK 0
@@ -315,8 +315,8 @@ int odet_post_ops_record(const float* scores, const float* deltas, const float* 
                          int32_t* out_count, float* out_record, void* workspace,
                          size_t workspace_bytes, odet_stream_t stream);
 
-/* evaluation/pascal_eval_files_utils.py:76-106 (the mAP-producing per-image loop; same loop inlined
- * at scripts/eval_coco.py:117-164) on the outputs of im_detect (model/fpn/base_fpn_model.py:364-390,
+/* evaluation/pascal_eval_files_utils.py:76-106 (the mAP-producing per-image loop; scripts/eval_coco.py:117-164
+ * has the same front end but a different per-image cap, see odet_eval_detect_topk) on the outputs of im_detect (model/fpn/base_fpn_model.py:364-390,
  * model/faster_rcnn/base_faster_rcnn_model.py:279-306): rois (resized-image pixels) are divided by
  * img_scale, then per class 1..num_classes-1: score > score_threshold -> decode -> clip to the RAW
  * image (raw_h, raw_w) with the min_size edge filter -> NMS(max_per_class, nms_iou_threshold); then
@@ -332,6 +332,79 @@ int odet_eval_detect(const float* scores, const float* deltas, const float* rois
                      float score_threshold, float min_size, float* out_boxes, int32_t* out_labels,
                      float* out_scores, int32_t* out_count, void* workspace,
                      size_t workspace_bytes, odet_stream_t stream);
+
+/* scripts/eval_coco.py:117-164 (the COCO per-image loop): the front end of odet_eval_detect (rois / img_scale,
+ * score > score_threshold, decode, clip to the raw image with the min_size filter, per-class NMS with max_per_class),
+ * then the cap of :160, tf.nn.top_k(k = min(max_per_image, n)): exactly that many detections stay, ordered by (score
+ * desc, concatenation position asc) -- the merge of odet_post_ops.  Ties at the k-th score are cut in position order
+ * (odet_eval_detect keeps them all, the PASCAL rule).  Same arguments, capacity and workspace as odet_eval_detect;
+ * out_count 0 when no class survives (the reference would raise at its tf.concat of an empty list). */
+int odet_eval_detect_topk(const float* scores, const float* deltas, const float* rois, int R,
+                          const int32_t* count_dev, int Ccls, int num_classes, float img_scale,
+                          float raw_h, float raw_w, const float* means, const float* stds,
+                          int max_per_class, int max_per_image, float nms_iou_threshold,
+                          float score_threshold, float min_size, float* out_boxes, int32_t* out_labels,
+                          float* out_scores, int32_t* out_count, void* workspace,
+                          size_t workspace_bytes, odet_stream_t stream);
+
+/* ---- COCO bbox evaluation (pycocotools COCOeval, iouType 'bbox', default Params) --------- */
+
+/* scripts/eval_coco.py:65-73 eval_by_cocotools runs pycocotools' COCOeval.evaluate / accumulate over the result records.
+ * Three launches restate it in float64; the host (evaluation/coco_eval.py) packs the ground truth and the results into
+ * segments = (category, image) pairs that hold GT or detections, ordered (category asc, image id asc); inside a segment
+ * GT keep annotation-file order and detections record order.  Boxes are xywh float64.  Parameters are fixed to
+ * Params.setDetParams: 10 IoU thresholds, 4 area ranges, maxDets (1, 10, 100), 101 recall thresholds, useCats = 1. */
+#define ODET_COCO_MAX_SEG_DETS 4096      /* detections of one segment before the maxDets[-1] = 100 truncation */
+#define ODET_COCO_MAX_SEG_GT 1024        /* ground-truth boxes of one segment */
+#define ODET_COCO_MAX_ENTRIES (1 << 24)  /* kept detections (at most 100 per segment) over all segments */
+#define ODET_COCO_KEEP 100               /* maxDets[-1] */
+#define ODET_COCO_T 10                   /* IoU thresholds */
+#define ODET_COCO_A 4                    /* area ranges */
+#define ODET_COCO_M 3                    /* maxDets */
+#define ODET_COCO_R 101                  /* recall thresholds */
+
+/* bytes of the workspace of odet_coco_order for num_entries kept detections */
+size_t odet_coco_eval_workspace_bytes(int num_entries);
+
+/* COCOeval.computeIoU (maskApi.c bbIou) + COCOeval.evaluateImg(maxDet = 100) for all 4 area ranges x 10 IoU
+ * thresholds, one workgroup per segment.  Device CSR offsets int32 [S+1]: seg_gt_off, seg_dt_off and seg_entry_off
+ * (entry_off[s+1] - entry_off[s] = min(detections, 100)).  gt_box [Ng,4], gt_area [Ng] (the annotation's area field),
+ * gt_crowd uint8 [Ng] (ignore = iscrowd, as _prepare sets it), dt_box [Nd,4], dt_score [Nd].  Host: iou_thrs double[10],
+ * area_rng double[8] (lo, hi pairs, inclusive).  max_seg_dets / max_seg_gt: the largest segment counts (they size the
+ * LDS; a segment above them is skipped).  Outputs per kept detection e (segment order, then stable score desc):
+ * out_score [E] double, out_matched / out_ignored uint64 [E] (bit a*10 + t: dtMatches != 0, dtIgnore), out_rank int32 [E]
+ * (position in its segment); out_npig int32 [S,4] (GT with gtIgnore == 0 per area range).  Scores are ranked by an
+ * order-keeping key with the index as tie-break, a total order on any values: -0.0 equals 0.0, and a NaN score ranks
+ * after every number (where numpy's argsort of -score puts it), NaNs in input order.  (evaluation/coco_eval.py rejects
+ * NaN before packing; a NaN box gives NaN IoUs, which never fault.)  Errors: ODET_E_LIMIT above the limits, before any
+ * launch. */
+int odet_coco_match(int num_segments, const int32_t* seg_gt_off, const int32_t* seg_dt_off,
+                    const int32_t* seg_entry_off, const double* gt_box, const double* gt_area,
+                    const uint8_t* gt_crowd, const double* dt_box, const double* dt_score,
+                    const double* iou_thrs, const double* area_rng, int max_seg_dets, int max_seg_gt,
+                    int num_entries, double* out_score, uint64_t* out_matched, uint64_t* out_ignored,
+                    int32_t* out_rank, int32_t* out_npig, odet_stream_t stream);
+
+/* COCOeval.accumulate's np.argsort(-dtScores, kind='mergesort') over each category's concatenation: the
+ * kept detections sorted by (category asc, score desc, entry index asc) -- stable LSD radix passes over an order-keeping
+ * 64-bit score key (-0.0 equals 0.0, NaN after every number; the key of odet_coco_match) and the category.
+ * cat_entry_off: device int32 [K+1] (entries of category k are [off[k], off[k+1])).  out_order int32 [E]: entry indices
+ * in sorted order.  Workspace: odet_coco_eval_workspace_bytes. */
+int odet_coco_order(int num_entries, int num_cats, const int32_t* cat_entry_off, const double* entry_score,
+                    int32_t* out_order, void* workspace, size_t workspace_bytes, odet_stream_t stream);
+
+/* COCOeval.accumulate in float64, one workgroup per (IoU threshold, area range x maxDets, category):
+ * cumulative TP / FP counts over the sorted entries with rank < maxDets[m] (ignored entries stay in the index space),
+ * rc = tp / npig, pr = tp / ((fp + tp) + spacing(1)), its suffix maximum, searchsorted(rc, recThrs, 'left').
+ * cat_seg_off: device int32 [K+1] (segments of category k), npig from odet_coco_match, rec_thrs: host double[101],
+ * max_dets: host int[3].  Outputs (device float64): precision and scores [10,101,K,4,3], recall [10,K,4,3]; -1 where the
+ * category has no segment or npig == 0. */
+int odet_coco_accumulate(int num_cats, const int32_t* cat_seg_off, const int32_t* cat_entry_off,
+                         const int32_t* npig, const int32_t* order, const double* entry_score,
+                         const uint64_t* entry_matched, const uint64_t* entry_ignored,
+                         const int32_t* entry_rank, const double* rec_thrs, const int* max_dets,
+                         double* out_precision, double* out_recall, double* out_scores,
+                         odet_stream_t stream);
 
 /* ---- eval input front end ------------------------------------------------------------- */
 

@@ -105,6 +105,13 @@ SIGNATURES = {
                                   _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'odet_eval_detect': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _f, _f, _f,
                               _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'odet_eval_detect_topk': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _f, _f, _f, _vp, _vp, _i, _i, _f, _f, _f,
+                                   _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'odet_coco_eval_workspace_bytes': (_sz, [_i]),
+    'odet_coco_match': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                             _vp]),
+    'odet_coco_order': (_i, [_i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'odet_coco_accumulate': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'odet_preprocess_images': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'odet_pack_detections': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     'odet_fpn_step_sizeof': (_sz, []),

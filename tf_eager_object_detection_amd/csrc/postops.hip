@@ -531,6 +531,20 @@ extern "C" int odet_eval_detect(const float* scores, const float* deltas, const 
                        out_scores, out_count, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// scripts/eval_coco.py:117-164: the same front end as odet_eval_detect, then the top-k merge of odet_post_ops (mode 0)
+extern "C" int odet_eval_detect_topk(const float* scores, const float* deltas, const float* rois, int R,
+                                     const int32_t* count_dev, int Ccls, int num_classes, float img_scale, float raw_h,
+                                     float raw_w, const float* means, const float* stds, int max_per_class,
+                                     int max_per_image, float nms_iou_threshold, float score_threshold, float min_size,
+                                     float* out_boxes, int32_t* out_labels, float* out_scores, int32_t* out_count,
+                                     void* workspace, size_t workspace_bytes, odet_stream_t stream) {
+  ODET_REQUIRE(img_scale > 0.0f && raw_h > 0.0f && raw_w > 0.0f, "odet_eval_detect_topk: bad scale / image size");
+  return post_ops_impl(scores, deltas, rois, R, count_dev, Ccls, num_classes,
+                       PostOpsExtra{raw_w - 1.0f, raw_h - 1.0f, img_scale, 0}, means, stds, max_per_class,
+                       max_per_image, nms_iou_threshold, score_threshold, min_size, out_boxes, out_labels,
+                       out_scores, out_count, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 extern "C" int odet_post_ops_record(const float* scores, const float* deltas, const float* rois, int R,
                                     const int32_t* count_dev, int Ccls, int num_classes, int image_h, int image_w,
                                     const float* means, const float* stds, int max_per_class, int max_per_image,

@@ -18,7 +18,7 @@ __all__ = ['detect_raw_images']
 def detect_raw_images(model, images, pipeline, preprocessing_type='caffe', caffe_pixel_means=P.CAFFE_PIXEL_MEANS,
                       image_format='bgr', min_edge=600, max_edge=1000, score_threshold=0.0, iou_threshold=0.5,
                       max_objects_per_class=50, max_objects_per_image=50, target_means=None, target_stds=None,
-                      min_size=10):
+                      min_size=10, detect=detect_image):
     """images: decoded uint8 HWC images (numpy arrays or tensors; BGR for pipeline 'voc', RGB for 'coco').
     -> one list per image, indexed by class id (entry 0 unused), of float32 [n, 5] arrays in raw-image pixels.
 
@@ -28,7 +28,8 @@ def detect_raw_images(model, images, pipeline, preprocessing_type='caffe', caffe
       preprocessing launch and one im_detect, in the detector's dtype (float16 models get the float16 batch).  Every
       image must resize to model.image_shape (ValueError otherwise, before any work is queued).
     The preprocessing arguments are those of preprocess.preprocess_images; the rest those of pascal_eval.detect_image
-    (pascal_eval_files_utils.py:19-29 defaults)."""
+    (pascal_eval_files_utils.py:19-29 defaults).  detect: the per-image loop, called with detect_image's arguments;
+    coco_eval.detect_image_coco gives the COCO script's cap (each list entry is then its (boxes, labels, scores))."""
     images = list(images)
     prep = dict(pipeline=pipeline, preprocessing_type=preprocessing_type, caffe_pixel_means=caffe_pixel_means,
                 image_format=image_format, min_edge=min_edge, max_edge=max_edge)
@@ -40,7 +41,7 @@ def detect_raw_images(model, images, pipeline, preprocessing_type='caffe', caffe
         for img in images:
             batch, scales, raw = P.preprocess_images([img], **prep)
             scores, deltas, rois = model.im_detect(batch, scales[0])
-            out.append(detect_image(scores, deltas, rois, 1.0, raw[0][0], raw[0][1], **det))   # (rois already / img_scale)
+            out.append(detect(scores, deltas, rois, 1.0, raw[0][0], raw[0][1], **det))   # (rois already / img_scale)
         return out
     if isinstance(model, (ResNetFpnDetector, ResNetC4Detector)):      # (Vgg16Detector is a ResNetC4Detector)
         want = tuple(model.image_shape)
@@ -52,7 +53,7 @@ def detect_raw_images(model, images, pipeline, preprocessing_type='caffe', caffe
         for i in range(0, len(images), step):
             batch, scales, raw = P.preprocess_images(images[i:i + step], dtype=model.dtype, **prep)
             for (scores, deltas, rois), (h, w) in zip(model.im_detect(batch, scales), raw):
-                out.append(detect_image(scores, deltas, rois, 1.0, h, w, **det))
+                out.append(detect(scores, deltas, rois, 1.0, h, w, **det))
         return out
     raise TypeError('detect_raw_images: %s is neither a caller object (BaseFPN / BaseFasterRcnn) nor a fast detector '
                     '(ResNetFpnDetector / ResNetC4Detector / Vgg16Detector)' % type(model).__name__)
