@@ -36,7 +36,8 @@ extern "C" {
  * in float32.  103: the two-limb launches report an out-of-range activation in a status word of their workspace
  * (odet_x2_status_offset); the tile-forcing diagnostics left this header and the shipped library (include/odet_diag.h, a
  * separate -DODET_DIAG build).  Added within 103: odet_preprocess_images (the eval loaders' input front end),
- * odet_eval_detect_topk and the odet_coco_* evaluation; no existing entry point or struct changed. */
+ * odet_eval_detect_topk, the odet_coco_* evaluation and the odet_voc_* evaluation; no existing entry point or struct
+ * changed. */
 #define ODET_VERSION 103
 
 #define ODET_OK 0
@@ -405,6 +406,76 @@ int odet_coco_accumulate(int num_cats, const int32_t* cat_seg_off, const int32_t
                          const int32_t* entry_rank, const double* rec_thrs, const int* max_dets,
                          double* out_precision, double* out_recall, double* out_scores,
                          odet_stream_t stream);
+
+/* ---- PASCAL VOC evaluation and the accuracy gate's paired bootstrap ---------------------- */
+
+/* evaluation/detectron_pascal_evaluation_utils.py voc_eval (:86-222) / voc_ap (:54-83), which scripts/eval_pascal.py:74-96
+ * runs once per class, in float64 and in the reference's operation order.  The host (evaluation/voc_eval_gpu.py) packs
+ * ground truth and detections into segments = (class, image) pairs that hold either, ordered (class asc, image asc);
+ * inside a segment ground truth keeps annotation order and detections the order of the caller's arrays.  Boxes are
+ * x1 y1 x2 y2 float64 (inclusive pixels: the + 1 widths of :190-197).  An entry is a detection; entries of segment s are
+ * [seg_dt_off[s], seg_dt_off[s+1]).  The score order of a class is odet_coco_order's (class asc, score desc, entry index
+ * asc), which on these entries equals np.argsort(-confidence, kind='stable') over the class's detections in image order
+ * (:169; the stable kind is what evaluation/pascal_eval.py uses, numpy's default leaves equal scores undefined). */
+#define ODET_VOC_MAX_SEG_DETS 4096       /* detections of one segment */
+#define ODET_VOC_MAX_SEG_GT 1024         /* ground-truth boxes of one segment */
+#define ODET_VOC_MAX_ENTRIES (1 << 24)   /* detections over all segments (ODET_COCO_MAX_ENTRIES: the order is shared) */
+#define ODET_VOC_R 11                    /* recall thresholds of the 11-point metric */
+#define ODET_VOC_IGNORED 0               /* entry flags: matched a `difficult` box, neither tp nor fp (:204) */
+#define ODET_VOC_TP 1                    /* :206 */
+#define ODET_VOC_FP 2                    /* :209, :211 */
+#define ODET_VOC_AP_07 0                 /* voc_ap(use_07_metric=True), :58-66 */
+#define ODET_VOC_AP_AREA 1               /* voc_ap(use_07_metric=False), :67-82 */
+
+/* bytes of the workspace of odet_voc_accumulate (num_resamples = 1, metric = ODET_VOC_AP_AREA) and odet_voc_bootstrap:
+ * the terms of the area metric's sum, (num_entries + num_classes) doubles per resample; 0 for the 11-point metric */
+size_t odet_voc_eval_workspace_bytes(int num_entries, int num_classes, int num_resamples, int metric);
+
+/* :173-211 for all segments at once, one wave per segment.  A segment's detections are taken in (score desc, input
+ * position asc) order -- the order in which the global walk of :177 meets this image's detections -- with the score key
+ * of odet_coco_match (-0.0 equals 0.0, NaN last).  Per detection: overlaps (:186-199) with every ground-truth box of the
+ * segment, ovmax / jmax = np.max / np.argmax (first maximum; a NaN overlap makes ovmax NaN, so the detection is a false
+ * positive), ovmax > ovthresh strictly (:203), a `difficult` match is ODET_VOC_IGNORED and leaves the box free (:204),
+ * the first match of a box ODET_VOC_TP (:205-207), a later one ODET_VOC_FP (:209), no ground truth ODET_VOC_FP (:211).
+ * Device: seg_gt_off / seg_dt_off int32 [S+1], gt_box [num_gt,4], gt_difficult uint8 [num_gt], dt_box [E,4], dt_score
+ * [E].  max_seg_dets / max_seg_gt: the largest segment counts (they size the LDS; a segment above them is skipped).
+ * Outputs, per entry in its segment's sorted order: out_score double [E], out_flag uint8 [E]; per segment out_npos int32
+ * [S] (boxes that are not difficult, :145).  Errors: ODET_E_LIMIT above the limits, before any launch. */
+int odet_voc_match(int num_segments, const int32_t* seg_gt_off, const int32_t* seg_dt_off, const double* gt_box,
+                   const uint8_t* gt_difficult, const double* dt_box, const double* dt_score, double ovthresh,
+                   int max_seg_dets, int max_seg_gt, int num_gt, int num_entries, double* out_score,
+                   uint8_t* out_flag, int32_t* out_npos, odet_stream_t stream);
+
+/* :213-220 and voc_ap (:54-83), one workgroup per class over the entries in odet_coco_order's order: tp / fp = cumulative
+ * counts (block prefix sums, a carry between chunks), rec = tp / npos (tp * 0 when npos == 0, as
+ * evaluation/pascal_eval.py has it; the reference divides by zero there), prec = tp / max(tp + fp, eps); ap07: ap = ap +
+ * p / 11. over rec_thrs (host double[11] = np.arange(0., 1.1, 0.1)), p = max(prec[rec >= t]) or 0; ap_area: the envelope
+ * and np.sum((mrec[i+1] - mrec[i]) * mpre[i+1]) in numpy's own order of additions (add.reduce: pieces of 8192 elements,
+ * each summed pairwise with eight running sums per block of up to 128), so that it equals the host value too.  Device: cls_seg_off / cls_entry_off int32 [K+1], seg_npos from odet_voc_match, order int32 [E],
+ * entry_flag [E], entry_image int32 [E] (image index of every entry).  Outputs: out_rec / out_prec double [E] in sorted
+ * order, out_ap07 / out_ap_area double [K], out_npos int64 [K], and the inputs of odet_voc_bootstrap: out_sorted_flag uint8
+ * [E], out_sorted_image int32 [E] (flag and image of the entries in sorted order).  Workspace (the terms of the area
+ * sum): odet_voc_eval_workspace_bytes(E, K, 1, ODET_VOC_AP_AREA). */
+int odet_voc_accumulate(int num_classes, int num_segments, int num_entries, const int32_t* cls_seg_off,
+                        const int32_t* cls_entry_off, const int32_t* seg_npos, const int32_t* order,
+                        const uint8_t* entry_flag, const int32_t* entry_image, const double* rec_thrs,
+                        double* out_rec, double* out_prec, double* out_ap07, double* out_ap_area, int64_t* out_npos,
+                        uint8_t* out_sorted_flag, int32_t* out_sorted_image, void* workspace,
+                        size_t workspace_bytes, odet_stream_t stream);
+
+/* evaluation/precision_gate.py _map_weighted (the paired bootstrap over images of the float16 accuracy gate) for every
+ * resample in one launch, grid = (resample, class): counts int32 [B, num_images] (device) says how often resample b drew
+ * image i; npos = sum(counts * npos of the image), every entry weighs counts[b, its image], tp / fp = cumulative weighted
+ * counts where every entry that is not ODET_VOC_TP is a false positive (_map_weighted's ~tp), rec, prec and the AP of
+ * `metric` as in odet_voc_accumulate.  All sums are integers, so the results do not depend on their order.  seg_image:
+ * int32 [S] image index of every segment.  Outputs: out_ap double [B, K] (0 where npos == 0: the host leaves such a class
+ * out of the mean), out_npos int64 [B, K].  Workspace: odet_voc_eval_workspace_bytes(E, K, B, metric) (none for the
+ * 11-point metric). */
+int odet_voc_bootstrap(int num_resamples, int num_classes, int num_images, int num_segments, int num_entries,
+                       const int32_t* cls_seg_off, const int32_t* cls_entry_off, const int32_t* seg_image,
+                       const int32_t* seg_npos, const uint8_t* sorted_flag, const int32_t* sorted_image,
+                       const int32_t* counts, const double* rec_thrs, int metric, double* out_ap, int64_t* out_npos,
+                       void* workspace, size_t workspace_bytes, odet_stream_t stream);
 
 /* ---- eval input front end ------------------------------------------------------------- */
 

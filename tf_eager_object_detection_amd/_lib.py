@@ -112,6 +112,11 @@ SIGNATURES = {
                              _vp]),
     'odet_coco_order': (_i, [_i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'odet_coco_accumulate': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'odet_voc_match': (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'odet_voc_eval_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'odet_voc_accumulate': (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                 _vp]),
+    'odet_voc_bootstrap': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     'odet_preprocess_images': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'odet_pack_detections': (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     'odet_fpn_step_sizeof': (_sz, []),

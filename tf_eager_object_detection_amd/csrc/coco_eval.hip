@@ -54,16 +54,7 @@ static size_t coco_match_lds(int maxd, int maxg, int tile_cap, int gwords) {
          (size_t)ODET_COCO_KEEP * 4 + (size_t)ODET_COCO_A * maxg * 4 + (size_t)COCO_TA * gwords * 4 + (size_t)maxg + 16;
 }
 
-// Descending order-keeping key of a float64 score: smaller key = higher score.  -0.0 is folded onto 0.0, and every NaN
-// gets the largest key (after every number, where numpy's argsort of -score puts it).  With the index as tie-break it
-// is a strict total order on any input, so the ranks below are always a permutation.
-__device__ __forceinline__ u64 coco_desc_key(double s) {
-  if (s != s) return ~0ull;
-  if (s == 0.0) s = 0.0;
-  const u64 u = (u64)__double_as_longlong(s);
-  const u64 asc = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-  return ~asc;
-}
+// (coco_desc_key, the score key of the ranks below and of odet_coco_order: odet_internal.h, shared with voc_eval.hip)
 
 __global__ void __launch_bounds__(CM_THREADS) k_coco_match(CocoMatchParams p) {
   extern __shared__ __align__(16) unsigned char smem[];

@@ -216,6 +216,17 @@ __device__ __forceinline__ int block_excl_scan(int v, int* lds /*[17]*/, int* to
   return lds[w] + inc - v;
 }
 
+// Descending order-keeping key of a float64 score (coco_eval.hip, voc_eval.hip): smaller key = higher score.  -0.0 is
+// folded onto 0.0, and every NaN gets the largest key (after every number, where numpy's argsort of -score puts it).
+// With the index as tie-break it is a strict total order on any input, so ranks built from it are always a permutation.
+__device__ __forceinline__ unsigned long long coco_desc_key(double s) {
+  if (s != s) return ~0ull;
+  if (s == 0.0) s = 0.0;
+  const unsigned long long u = (unsigned long long)__double_as_longlong(s);
+  const unsigned long long asc = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+  return ~asc;
+}
+
 // ---- in-workgroup sorts of 64-bit keys ---------------------------------------------------------
 __device__ __forceinline__ void bitonic_sort_u64(unsigned long long* keys, int P2, int nthreads) {
   for (int k = 2; k <= P2; k <<= 1) {

@@ -441,7 +441,8 @@ def _build(family, depth, num_classes, image_shape, num_proposals, dtype, max_ba
 
 
 def fp16_vs_fp32(num_images=256, image_shape=None, depth=None, num_classes=21, num_proposals=None, batch32=4,
-                 batch16=8, seed=0, train_images=64, ridge=1e-3, resamples=400, family='fpn', test_mode='fp16', **hot_kwargs):
+                 batch16=8, seed=0, train_images=64, ridge=1e-3, resamples=400, family='fpn', test_mode='fp16',
+                 evaluator='host', **hot_kwargs):
     """The whole gate for one detector family ('fpn': ResNet-101-FPN @ 800x1333, 'c4': ResNet-50 C4 @ 800x1333, 'vgg16':
     VGG16 @ 600x800 -- BASELINE configs 3 / 2 / 1).  -> dict for bench.py's `e2e.*.map_delta_vs_fp32` and the GPU tests;
     `within_bar` = the point estimate is inside the north star's +-0.002; `ci_half_width_within_bar` = the paired-bootstrap
@@ -449,7 +450,15 @@ def fp16_vs_fp32(num_images=256, image_shape=None, depth=None, num_classes=21, n
     scenes -- a statement about the gate's RESOLUTION, not about the mode); `ci_inside_bar` = BOTH ends of that interval lie
     within +-0.002 (the statement about the mode: only this one supports "mAP within +-0.002").
     test_mode: 'fp16' (the float16 throughput mode) or 'x3' / 'x2' (the float32 split-precision modes, csrc/conv_x3.hip) as the
-    detector under test; the reference detector is always the exact-float32 mode (the `*_fp16` keys then hold the x3 figures)."""
+    detector under test; the reference detector is always the exact-float32 mode (the `*_fp16` keys then hold the x3 figures).
+    evaluator: 'host' (paired_map_delta, numpy) or 'gpu' (voc_eval_gpu.paired_map_delta_gpu, the same figures from the
+    odet_voc_* kernels) for the mAPs and the bootstrap."""
+    if evaluator not in ('host', 'gpu'):
+        raise ValueError("evaluator must be 'host' or 'gpu', got %r" % (evaluator,))
+    if evaluator == 'gpu':
+        from .voc_eval_gpu import paired_map_delta_gpu as paired
+    else:
+        paired = paired_map_delta
     name, shape0, prop0 = _FAMILIES[family]
     image_shape = tuple(shape0 if image_shape is None else image_shape)
     num_proposals = prop0 if num_proposals is None else num_proposals
@@ -477,8 +486,8 @@ def fp16_vs_fp32(num_images=256, image_shape=None, depth=None, num_classes=21, n
         k16 += k
         gtb += gb
         gtl += gl
-    pair = paired_map_delta(d32, d16, gtb, gtl, num_classes, resamples=resamples, seed=seed)
-    pair_area = paired_map_delta(d32, d16, gtb, gtl, num_classes, resamples=0, seed=seed, use_07_metric=False)
+    pair = paired(d32, d16, gtb, gtl, num_classes, resamples=resamples, seed=seed)
+    pair_area = paired(d32, d16, gtb, gtl, num_classes, resamples=0, seed=seed, use_07_metric=False)
     repro = compare_detections(d32, d16, num_classes, 0.0)
     agree = [len(np.intersect1d(a, b, assume_unique=True)) / max(len(a), 1) for a, b in zip(k32, k16)]
     lo, hi = pair['delta_ci95']
