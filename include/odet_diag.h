@@ -17,6 +17,10 @@ int odet_debug_conv_tile(int form, int nw, int wn, int mt, int ns);
 /* the same for the split-precision float32 launches (csrc/conv_x3.hip): (mt, wn) of its tile list and the K split (workgroups
  * per tile, 1 = none); mt = 0 clears */
 int odet_debug_x3_tile(int mt, int wn, int ksplit);
+/* the float32 -> float16 conversion of the library's epilogues on its own (the packed conversion of csrc/odet_internal.h under
+ * the product's compiler flags): n float32 values (n % 8 == 0, device, 16-byte aligned) -> their float16 bits, once through
+ * d_cvt8_f16 (out_pk) and once through d_cvt_pk_f16 + d_pack8_f16 (out_pack8); values 2k / 2k + 1 share one packed instruction */
+int odet_debug_cvt_f16(const float* src, void* out_pk, void* out_pack8, long long n, odet_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -882,6 +882,9 @@ def test_conv3x3_conv1x1_fused_block_tail(B, H, W, cin, n3, res, cmid):
     got = ops.conv3x3_conv1x1_f16(x, w2, b2, w3, b3, residual=r, relu=True)
     want = reference(x, w2, b2, w3, b3, r)
     assert float(want.abs().max().item()) < 2048 and torch.equal(got.float(), want)
+    # the two-launch form on the same data, bit for bit (nothing rounds here, so float16(conv) + in_bias on load is the same
+    # function; where the convolution rounds it is not: tests/test_f16_rounding_gpu.py holds each form to its own contract)
+    assert torch.equal(ops.conv1x1_f16(ops.conv3x3_f16(x, w2), w3, b3, residual=r, relu=True, in_bias=b2), got)
     x = (torch.randn((B, H, W, cin), device='cuda', generator=g) * 0.5).half()
     w2 = (torch.randn((cmid, cin, 3, 3), device='cuda', generator=g) * 0.02).half().contiguous(memory_format=torch.channels_last)
     b2 = (torch.randn(cmid, device='cuda', generator=g) * 0.1).half()

@@ -900,6 +900,36 @@ static bool tile_override(int form, int cout, int need_wn, ConvTile* t) {
   *t = o;
   return true;
 }
+
+// Diagnostic build only: the float32 -> float16 conversion of every epilogue of this library (d_cvt_pk_f16 / d_cvt8_f16 /
+// d_pack8_f16 of odet_internal.h) on its own, compiled with the product's flags -- tests/test_f16_rounding_gpu.py holds it to
+// round-to-nearest-even on every decision boundary of float16.  Eight values per lane: out_pk gets them through d_cvt8_f16,
+// out_pack8 through four d_cvt_pk_f16 dwords packed by d_pack8_f16 (the two spellings the kernels use); 16-byte vector stores.
+__global__ void __launch_bounds__(256) k_debug_cvt_f16(const float* __restrict__ src, _Float16* __restrict__ out_pk,
+                                                        _Float16* __restrict__ out_pack8, long long n8) {
+  typedef _Float16 dbg_h8 __attribute__((ext_vector_type(8)));
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long long)gridDim.x * 256) {
+    float f[8];
+    const float4 a = *reinterpret_cast<const float4*>(src + i * 8), b = *reinterpret_cast<const float4*>(src + i * 8 + 4);
+    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
+    *reinterpret_cast<dbg_h8*>(out_pk + i * 8) = d_cvt8_f16<dbg_h8>(f);
+    unsigned u[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) u[k] = d_cvt_pk_f16(f[2 * k], f[2 * k + 1]);
+    *reinterpret_cast<dbg_h8*>(out_pack8 + i * 8) = d_pack8_f16<dbg_h8>(u);
+  }
+}
+extern "C" int odet_debug_cvt_f16(const float* src, void* out_pk, void* out_pack8, long long n, odet_stream_t stream) {
+  ODET_REQUIRE(src && out_pk && out_pack8, "odet_debug_cvt_f16: null pointer");
+  ODET_REQUIRE(n >= 0 && n % 8 == 0, "odet_debug_cvt_f16: n %lld must be a multiple of 8", n);
+  ODET_REQUIRE(((uintptr_t)src | (uintptr_t)out_pk | (uintptr_t)out_pack8) % 16 == 0, "odet_debug_cvt_f16: 16-byte aligned arrays");
+  if (n == 0) return ODET_OK;
+  const long long n8 = n / 8;
+  const int grid = (int)std::min<long long>((n8 + 255) / 256, 256 * 16);
+  hipLaunchKernelGGL(k_debug_cvt_f16, dim3(grid), dim3(256), 0, (hipStream_t)stream, src, (_Float16*)out_pk, (_Float16*)out_pack8, n8);
+  ODET_LAUNCH_CHECK();
+  return ODET_OK;
+}
 #else
 static inline bool tile_override(int, int, int, ConvTile*) { return false; }   // (the shipped library: no process-global override)
 #endif

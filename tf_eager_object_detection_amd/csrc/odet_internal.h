@@ -245,7 +245,8 @@ __device__ __forceinline__ void bitonic_sort_u64(unsigned long long* keys, int P
 }
 
 // Two float32 -> one dword of two float16 (round to nearest even) in ONE instruction: gfx950's v_cvt_pk_f16_f32.  hipcc emits
-// two v_cvt_f16_f32 and a v_pack_b32_f16 for the same thing; bit-identical over all 2^32 inputs (tools/exp/cvt_pk_probe.hip).
+// two v_cvt_f16_f32 and a v_pack_b32_f16 for the same thing; bit-identical over all 2^32 inputs (tools/exp/cvt_pk_probe.hip), and
+// held to nearest-even on every decision boundary of float16 under this build's flags by tests/test_f16_rounding_gpu.py.
 __device__ __forceinline__ unsigned d_cvt_pk_f16(float a, float b) {
   unsigned r;
   asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));

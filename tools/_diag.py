@@ -59,6 +59,7 @@ def build_variant(out_path, extra_flags=(), sources=None, patch=None, only=None)
 DIAG_SIGNATURES = {
     'odet_debug_conv_tile': (_lib._i, [_lib._i] * 5),
     'odet_debug_x3_tile': (_lib._i, [_lib._i] * 3),
+    'odet_debug_cvt_f16': (_lib._i, [_lib._vp, _lib._vp, _lib._vp, _lib.C.c_longlong, _lib._vp]),
 }
 _diag_handle = None
 
