@@ -36,8 +36,8 @@ extern "C" {
  * in float32.  103: the two-limb launches report an out-of-range activation in a status word of their workspace
  * (odet_x2_status_offset); the tile-forcing diagnostics left this header and the shipped library (include/odet_diag.h, a
  * separate -DODET_DIAG build).  Added within 103: odet_preprocess_images (the eval loaders' input front end),
- * odet_eval_detect_topk, the odet_coco_* evaluation and the odet_voc_* evaluation; no existing entry point or struct
- * changed. */
+ * odet_eval_detect_topk, the odet_coco_* evaluation, the odet_voc_* evaluation and the fused training targets
+ * (odet_anchor_target, odet_proposal_target); no existing entry point or struct changed. */
 #define ODET_VERSION 103
 
 #define ODET_OK 0
@@ -861,6 +861,68 @@ int odet_exec_submit_batch(odet_exec_t* ex, int worker, const odet_fpn_step_t* c
  * text through odet_exec_last_error) and clears it */
 int odet_exec_wait(odet_exec_t* ex);
 const char* odet_exec_last_error(odet_exec_t* ex);
+
+/* ---- training targets (added within 103) ---------------------------------------------------------------------------
+ * model/anchor_target.py:49-107 and model/proposal_target.py:54-124 for a BATCH of images in a fixed number of launches on
+ * `stream`: no IoU matrix in memory, no allocation, no host read (graph-capturable), every output bitwise reproducible and
+ * independent of the batch an image sits in.
+ *
+ * Ground truth is packed: gt_boxes [sum G, 4], gt_offsets device int32 [batch+1] (image b owns rows
+ * gt_offsets[b] .. gt_offsets[b+1]).  Limits: batch <= 64, total_num_samples <= 1024, max_pos_samples <= total_num_samples,
+ * at most 2^20 anchors and 65536 RoIs per image (ODET_E_LIMIT / ODET_E_INVALID).  At most 1024 boxes per image: the offsets
+ * live on the device, so the call cannot refuse on the host -- an image above the limit is reported ON THE DEVICE by a
+ * `counts` row of -1 and gets fill values (labels -1, everything else 0, no sampled row) in every output.  An image with G = 0
+ * (the reference cannot run it) is background only: row maximum 0, arg-maximum -1, targets 0.
+ *
+ * Sampling rule.  philox(ctr[4], key[2]) = Philox4x32-10.  Candidate i of image b owns
+ *   key64(stream, image_id, i) = (w0 << 32) | w1  of  philox((i, image_id, stream, 0), (seed low word, seed high word)),
+ * image_id = first_image_id + b.  "Keep k of the candidates" = the k candidates with the smallest (key64, i) pairs: a uniformly
+ * random k-subset like the reference's shuffle-and-slice, and a function of (seed, image_id, i) alone.  Streams: 0 anchor
+ * foreground, 1 anchor background, 2 RoI foreground, 3 RoI background; i = index into ALL anchors resp. the RoI's row.
+ * With replacement (proposal_target.py:73-76): draw j picks bg_ascending[(uint64(w0) * n_bg) >> 32], w0 of
+ * philox((j, image_id, 4, 0), seed). */
+
+size_t odet_anchor_target_workspace_bytes(int num_anchors, int batch, int total_num_samples);
+/* anchors [num_anchors,4] shared by the batch (one image shape).  In the reference's order: inside = bboxes_range_filter;
+ * IoU (the arithmetic of odet_pairwise_iou) over inside anchors only; row maximum and FIRST arg-maximum; column maximum per
+ * box; labels -1, then 0 where max < neg, then 1 where IoU[a,g] == column maximum of any g (a box that meets no inside anchor
+ * has maximum 0 and so marks every anchor with zero overlap: the reference's behaviour, kept), then 1 where max >= pos;
+ * foreground kept to max_pos_samples, background to total_num_samples - kept foreground, by the sampling rule.
+ * Outputs.  Dense, each nullable (null = not written): labels float32 [batch,N] in {-1,0,1}; targets [batch,N,4] =
+ * odet_encode's arithmetic of (anchor, box[arg-maximum]) on EVERY inside anchor, 0 elsewhere; inside [batch,N,4] = 1 on
+ * label 1; outside [batch,N,4] = float32(1) / float32(kept foreground + kept background) on labels >= 0.  Compact, required:
+ * sample_idx int32 [batch,S] (S = total_num_samples: kept foreground anchors in ascending index order, then the background
+ * ones, then -1), sample_targets [batch,S,4], counts int32 [batch,5] = inside anchors, foreground and background before
+ * sampling, foreground and background kept.  For parity checks, nullable: labels_before_sampling int32 [batch,N] and
+ * argmax int32 [batch,N], both -1 outside the image. */
+int odet_anchor_target(const float* anchors, int num_anchors, const float* gt_boxes, const int32_t* gt_offsets,
+                       int batch, int image_h, int image_w, float pos_iou_threshold, float neg_iou_threshold,
+                       int total_num_samples, int max_pos_samples, const float* means, const float* stds,
+                       uint64_t seed, uint32_t first_image_id, float* labels, float* targets, float* inside,
+                       float* outside, int32_t* sample_idx, float* sample_targets, int32_t* counts,
+                       int32_t* labels_before_sampling, int32_t* argmax, void* workspace, size_t workspace_bytes,
+                       odet_stream_t stream);
+
+size_t odet_proposal_target_workspace_bytes(int max_rois, int batch);
+/* rois [batch,max_rois,4]; roi_counts (nullable) device int32 [batch]: valid rows per image.  gt_labels int32 [sum G].
+ * Assignment (:55-63): row maximum, FIRST arg-maximum = gt_assignment, labels = gt_labels[gt_assignment]; foreground
+ * max >= pos, background neg <= max < pos.  Keep max_pos_samples of the foreground, then want = S - kept foreground of the
+ * background, with replacement when there are fewer.  Row order: foreground rows first, in ascending (key64, i) order when
+ * they were sampled and in ascending row index when not; the same for the background; with-replacement picks in draw order.
+ * Outputs, all of fixed shape (S = total_num_samples, C = num_classes): final_rois [batch,S,4]; final_labels int32 [batch,S]
+ * (0 on background rows); targets, inside, outside float32 [batch,S,4C] (outside = 1 on written rows); keep int32 [batch,S]
+ * = input row of each output row; gt_assignment int32 [batch,max_rois] (-1 on rows >= roi_counts or without ground truth);
+ * counts int32 [batch,4] = foreground candidates, background candidates, foreground rows, rows written.
+ * reference_row_labels != 0 keeps the reference's column choice (:96, :113): foreground row r writes into the class column
+ * of INPUT RoI number r; 0 uses the sampled RoI's own class.  An image that wants background rows and has no candidate (the
+ * reference fails there) gets its foreground rows, rows written < S, and zeros with keep = -1 behind them. */
+int odet_proposal_target(const float* rois, const int32_t* roi_counts, int max_rois, const float* gt_boxes,
+                         const int32_t* gt_labels, const int32_t* gt_offsets, int batch, int num_classes,
+                         float pos_iou_threshold, float neg_iou_threshold, int total_num_samples,
+                         int max_pos_samples, const float* means, const float* stds, int reference_row_labels,
+                         uint64_t seed, uint32_t first_image_id, float* final_rois, int32_t* final_labels,
+                         float* targets, float* inside, float* outside, int32_t* keep, int32_t* gt_assignment,
+                         int32_t* counts, void* workspace, size_t workspace_bytes, odet_stream_t stream);
 
 #ifdef __cplusplus
 }

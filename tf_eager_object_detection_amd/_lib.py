@@ -174,6 +174,12 @@ SIGNATURES = {
     'odet_exec_submit_batch': (_i, [_vp, _i, _vp, _i, _i]),
     'odet_exec_wait': (_i, [_vp]),
     'odet_exec_last_error': (C.c_char_p, [_vp]),
+    'odet_anchor_target_workspace_bytes': (_sz, [_i, _i, _i]),
+    'odet_anchor_target': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _f, _f, _i, _i, _vp, _vp, C.c_uint64, C.c_uint32,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'odet_proposal_target_workspace_bytes': (_sz, [_i, _i]),
+    'odet_proposal_target': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _f, _i, _i, _vp, _vp, _i, C.c_uint64, C.c_uint32,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -123,17 +123,7 @@ __global__ void __launch_bounds__(256) k_encode(const float4* __restrict__ src, 
                                                 Vec4 means, Vec4 stds, float4* __restrict__ out) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  float4 b = src[i], g = dst[i];
-  float width = b.z - b.x + 1.0f, height = b.w - b.y + 1.0f;     // bbox_transform.py:11-14
-  float cx = b.x + 0.5f * width, cy = b.y + 0.5f * height;
-  float gw = g.z - g.x + 1.0f, gh = g.w - g.y + 1.0f;            // :16-19
-  float gcx = g.x + 0.5f * gw, gcy = g.y + 0.5f * gh;
-  float dx = (gcx - cx) / width;                                 // :21-24
-  float dy = (gcy - cy) / height;
-  float dw = d_log32(gw / width);
-  float dh = d_log32(gh / height);
-  out[i] = make_float4((dx - means.v[0]) / stds.v[0], (dy - means.v[1]) / stds.v[1],
-                       (dw - means.v[2]) / stds.v[2], (dh - means.v[3]) / stds.v[3]);   // :27
+  out[i] = d_encode_box(src[i], dst[i], means.v, stds.v);
 }
 
 extern "C" int odet_encode(const float* src, const float* dst, int n, const float* means, const float* stds,
@@ -328,14 +318,7 @@ __global__ void __launch_bounds__(256) k_pairwise_iou(const float4* __restrict__
   int j = blockIdx.y * 64 + (threadIdx.x & 63);
   int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= n || j >= m) return;
-  float4 p = b1[i], q = b2[j];
-  float a1 = (p.w - p.y + 1.0f) * (p.z - p.x + 1.0f);            // bbox_tf.py:14-15
-  float a2 = (q.w - q.y + 1.0f) * (q.z - q.x + 1.0f);
-  float ih = fmaxf(0.0f, fminf(p.w, q.w) - fmaxf(p.y, q.y) + 1.0f);   // :28-30
-  float iw = fmaxf(0.0f, fminf(p.z, q.z) - fmaxf(p.x, q.x) + 1.0f);   // :31-33
-  float inter = ih * iw;
-  float uni = a1 + a2 - inter;                                   // :51-52
-  out[(int64_t)i * m + j] = (inter == 0.0f) ? 0.0f : inter / uni;   // :54-56
+  out[(int64_t)i * m + j] = d_pair_iou(b1[i], b2[j]);
 }
 
 extern "C" int odet_pairwise_iou(const float* boxes1, int n, const float* boxes2, int m, float* out,

@@ -108,6 +108,32 @@ __device__ __forceinline__ float4 d_clip_box(float4 b, float minv, float wmax, f
                      fmaxf(fminf(b.z, wmax), minv), fmaxf(fminf(b.w, hmax), minv));
 }
 
+// utils/bbox_tf.py:7-56 IoU of one pair (+1 convention, 0 where the intersection is 0): THE operation sequence of
+// odet_pairwise_iou, shared with the fused training targets (targets.hip) so that every pass over a pair gives the same bits.
+__device__ __forceinline__ float d_pair_iou(float4 p, float4 q) {
+  float a1 = (p.w - p.y + 1.0f) * (p.z - p.x + 1.0f);            // bbox_tf.py:14-15
+  float a2 = (q.w - q.y + 1.0f) * (q.z - q.x + 1.0f);
+  float ih = fmaxf(0.0f, fminf(p.w, q.w) - fmaxf(p.y, q.y) + 1.0f);   // :28-30
+  float iw = fmaxf(0.0f, fminf(p.z, q.z) - fmaxf(p.x, q.x) + 1.0f);   // :31-33
+  float inter = ih * iw;
+  float uni = a1 + a2 - inter;                                   // :51-52
+  return (inter == 0.0f) ? 0.0f : inter / uni;                   // :54-56
+}
+
+// utils/bbox_transform.py:4-29 encode of one (box, ground truth) pair: THE operation sequence of odet_encode.
+__device__ __forceinline__ float4 d_encode_box(float4 b, float4 g, const float* means, const float* stds) {
+  float width = b.z - b.x + 1.0f, height = b.w - b.y + 1.0f;     // bbox_transform.py:11-14
+  float cx = b.x + 0.5f * width, cy = b.y + 0.5f * height;
+  float gw = g.z - g.x + 1.0f, gh = g.w - g.y + 1.0f;            // :16-19
+  float gcx = g.x + 0.5f * gw, gcy = g.y + 0.5f * gh;
+  float dx = (gcx - cx) / width;                                 // :21-24
+  float dy = (gcy - cy) / height;
+  float dw = d_log32(gw / width);
+  float dh = d_log32(gh / height);
+  return make_float4((dx - means[0]) / stds[0], (dy - means[1]) / stds[1],
+                     (dw - means[2]) / stds[2], (dh - means[3]) / stds[3]);   // :27
+}
+
 // order-preserving map float32 -> uint32 (ascending)
 __device__ __forceinline__ uint32_t d_float_asc_key(float f) {
   uint32_t u = __float_as_uint(f);

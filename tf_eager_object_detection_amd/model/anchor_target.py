@@ -7,10 +7,11 @@ torch generator stands in for it, so parity is exact up to the sampling step (`l
 distribution-level after it (counts, subset relations)."""
 import torch
 
+from .. import ops
 from ..utils.bbox_tf import bboxes_range_filter, pairwise_iou
 from ..utils.bbox_transform import encode_bbox_with_mean_and_std
 
-__all__ = ['AnchorTarget']
+__all__ = ['AnchorTarget', 'FusedAnchorTarget']
 
 
 def _unmap(data, count, inds, fill=0.0):
@@ -72,5 +73,39 @@ class AnchorTarget:
         outside[labels >= 0] = 1.0 / num_examples                                          # :100-101
         return (_unmap(labels, total, idx, -1), _unmap(targets, total, idx, 0),
                 _unmap(inside, total, idx, 0), _unmap(outside, total, idx, 0))             # :104-107
+
+    call = __call__
+
+
+class FusedAnchorTarget:
+    """The same targets from ONE call of the fused HIP stage (ops.anchor_targets, csrc/targets.hip): no IoU matrix, no host
+    read, a batch of images per call.  The sub-sampling is the counter-based rule of include/odet.h (Philox keys, the k
+    smallest (key, index) pairs), a function of (seed, image id, anchor index) alone -- so every output, the sampled half
+    included, has a bit-exact CPU restatement.  `AnchorTarget` keeps the generator-driven sampling."""
+
+    def __init__(self, pos_iou_threshold=0.7, neg_iou_threshold=0.3, total_num_samples=256, max_pos_samples=128,
+                 target_means=None, target_stds=None, seed=0):
+        self._pos_iou_threshold = pos_iou_threshold
+        self._neg_iou_threshold = neg_iou_threshold
+        self._total_num_samples = total_num_samples
+        self._max_pos_samples = max_pos_samples
+        self._target_means = [0, 0, 0, 0] if target_means is None else target_means
+        self._target_stds = [1, 1, 1, 1] if target_stds is None else target_stds
+        self._seed = seed
+        self._next_image_id = 0              # advanced by every single-image call: successive calls draw different samples
+
+    def batch(self, gt_boxes, gt_offsets, image_shape, all_anchors, first_image_id=0, dense=True, parity=False):
+        """gt_boxes [sum G,4] + gt_offsets int32 [B+1] (device) -> ops.AnchorTargets, every tensor batch-first."""
+        return ops.anchor_targets(all_anchors, gt_boxes, gt_offsets, image_shape, self._pos_iou_threshold,
+                                  self._neg_iou_threshold, self._total_num_samples, self._max_pos_samples,
+                                  self._target_means, self._target_stds, seed=self._seed, first_image_id=first_image_id,
+                                  dense=dense, parity=parity)
+
+    def __call__(self, inputs, training=None, mask=None):
+        gt_bboxes, image_shape, all_anchors = inputs
+        off = torch.tensor([0, gt_bboxes.shape[0]], dtype=torch.int32, device=all_anchors.device)
+        out = self.batch(gt_bboxes, off, image_shape, all_anchors, first_image_id=self._next_image_id)
+        self._next_image_id += 1
+        return out.labels[0], out.targets[0], out.inside[0], out.outside[0]
 
     call = __call__

@@ -13,12 +13,11 @@ import torch
 
 from .. import ops
 from ..utils.anchor_generator import generate_anchor_base, generate_by_anchor_base_tf
-from .anchor_target import AnchorTarget
 from .fpn_detector import caller_range_checked
 from .base_fpn_model import _Part, _image_nhwc
 from .losses import cls_loss, smooth_l1_loss
 from .prediction import post_ops_prediction
-from .proposal_target import ProposalTarget
+from .proposal_target import training_target_layers
 from .region_proposal import RegionProposal
 from .roi_pooling import RoiPoolingCropAndResize
 
@@ -54,7 +53,8 @@ class BaseFasterRcnn(torch.nn.Module):
                  rpn_training_max_pos_samples, roi_proposal_means, roi_proposal_stds, roi_pool_size,
                  roi_pooling_max_pooling_flag, roi_sigma, roi_training_pos_iou_threshold, roi_training_neg_iou_threshold,
                  roi_training_total_num_samples, roi_training_max_pos_samples, prediction_max_objects_per_image,
-                 prediction_max_objects_per_class, prediction_nms_iou_threshold, prediction_score_threshold):
+                 prediction_max_objects_per_class, prediction_nms_iou_threshold, prediction_score_threshold,
+                 training_targets='torch'):
         super().__init__()
         self.num_classes = num_classes
         self.weight_decay = weight_decay
@@ -78,16 +78,17 @@ class BaseFasterRcnn(torch.nn.Module):
             num_post_nms_train=rpn_proposal_num_post_nms_train, num_pre_nms_test=rpn_proposal_num_pre_nms_test,
             num_post_nms_test=rpn_proposal_num_post_nms_test, nms_iou_threshold=rpn_proposal_nms_iou_threshold,
             target_means=rpn_proposal_means, target_stds=rpn_proposal_stds)
-        self._anchor_target = AnchorTarget(
-            pos_iou_threshold=rpn_training_pos_iou_threshold, neg_iou_threshold=rpn_training_neg_iou_threshold,
-            total_num_samples=rpn_training_total_num_samples, max_pos_samples=rpn_training_max_pos_samples,
-            target_means=rpn_proposal_means, target_stds=rpn_proposal_stds)
         self._roi_pooling = RoiPoolingCropAndResize(pool_size=roi_pool_size, max_pooling_flag=roi_pooling_max_pooling_flag)
-        self._proposal_target = ProposalTarget(
-            num_classes=num_classes, pos_iou_threshold=roi_training_pos_iou_threshold,
-            neg_iou_threshold=roi_training_neg_iou_threshold, total_num_samples=roi_training_total_num_samples,
-            max_pos_samples=roi_training_max_pos_samples, target_means=roi_proposal_means,
-            target_stds=roi_proposal_stds)
+        # training_targets: 'torch' = AnchorTarget / ProposalTarget (generator-driven sampling), 'hip' = the fused stage
+        self._anchor_target, self._proposal_target = training_target_layers(
+            training_targets,
+            dict(pos_iou_threshold=rpn_training_pos_iou_threshold, neg_iou_threshold=rpn_training_neg_iou_threshold,
+                 total_num_samples=rpn_training_total_num_samples, max_pos_samples=rpn_training_max_pos_samples,
+                 target_means=rpn_proposal_means, target_stds=rpn_proposal_stds),
+            dict(num_classes=num_classes, pos_iou_threshold=roi_training_pos_iou_threshold,
+                 neg_iou_threshold=roi_training_neg_iou_threshold, total_num_samples=roi_training_total_num_samples,
+                 max_pos_samples=roi_training_max_pos_samples, target_means=roi_proposal_means,
+                 target_stds=roi_proposal_stds))
         self._extractor = self._get_extractor()
         self._roi_head = self._get_roi_head()
 
@@ -244,7 +245,7 @@ _COMMON = dict(num_classes=21, weight_decay=0.0001, ratios=(0.5, 1.0, 2.0), scal
                roi_proposal_stds=(0.1, 0.1, 0.2, 0.2), roi_pool_size=7, roi_pooling_max_pooling_flag=True, roi_sigma=1,
                roi_training_pos_iou_threshold=0.5, roi_training_neg_iou_threshold=0.1, roi_training_total_num_samples=128,
                roi_training_max_pos_samples=32, prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
-               prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3)
+               prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3, training_targets='torch')
 
 
 class ResNetFasterRcnn(_FrcnnFromDense):

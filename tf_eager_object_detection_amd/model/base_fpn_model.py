@@ -15,11 +15,10 @@ import torch
 
 from .. import ops
 from ..utils.anchor_generator import make_anchors
-from .anchor_target import AnchorTarget
 from .fpn_detector import caller_range_checked
 from .losses import cls_loss, smooth_l1_loss
 from .prediction import post_ops_prediction
-from .proposal_target import ProposalTarget
+from .proposal_target import training_target_layers
 from .region_proposal import RegionProposal
 from .roi_pooling import RoiPoolingCropAndResize2
 
@@ -73,7 +72,7 @@ class BaseFPN(torch.nn.Module):
                  roi_sigma=1, roi_training_pos_iou_threshold=0.5, roi_training_neg_iou_threshold=0.1,
                  roi_training_total_num_samples=128, roi_training_max_pos_samples=32,
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
-                 prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.):
+                 prediction_nms_iou_threshold=0.3, prediction_score_threshold=0., training_targets='torch'):
         super().__init__()
         self.roi_feature_size = roi_feature_size
         self.num_classes = num_classes
@@ -105,15 +104,16 @@ class BaseFPN(torch.nn.Module):
             target_means=rpn_proposal_means, target_stds=rpn_proposal_stds)
         self._roi_pooling = RoiPoolingCropAndResize2(pool_size=roi_pool_size)
         self._roi_head = self._get_roi_head()
-        self._anchor_target = AnchorTarget(
-            pos_iou_threshold=rpn_training_pos_iou_threshold, neg_iou_threshold=rpn_training_neg_iou_threshold,
-            total_num_samples=rpn_training_total_num_samples, max_pos_samples=rpn_training_max_pos_samples,
-            target_means=rpn_proposal_means, target_stds=rpn_proposal_stds)
-        self._proposal_target = ProposalTarget(
-            num_classes=num_classes, pos_iou_threshold=roi_training_pos_iou_threshold,
-            neg_iou_threshold=roi_training_neg_iou_threshold, total_num_samples=roi_training_total_num_samples,
-            max_pos_samples=roi_training_max_pos_samples, target_means=roi_proposal_means,
-            target_stds=roi_proposal_stds)
+        # training_targets: 'torch' = AnchorTarget / ProposalTarget (generator-driven sampling), 'hip' = the fused stage
+        self._anchor_target, self._proposal_target = training_target_layers(
+            training_targets,
+            dict(pos_iou_threshold=rpn_training_pos_iou_threshold, neg_iou_threshold=rpn_training_neg_iou_threshold,
+                 total_num_samples=rpn_training_total_num_samples, max_pos_samples=rpn_training_max_pos_samples,
+                 target_means=rpn_proposal_means, target_stds=rpn_proposal_stds),
+            dict(num_classes=num_classes, pos_iou_threshold=roi_training_pos_iou_threshold,
+                 neg_iou_threshold=roi_training_neg_iou_threshold, total_num_samples=roi_training_total_num_samples,
+                 max_pos_samples=roi_training_max_pos_samples, target_means=roi_proposal_means,
+                 target_stds=roi_proposal_stds))
 
     def _get_roi_head(self):
         raise NotImplementedError
@@ -309,7 +309,7 @@ class ResnetV1Fpn(BaseFPN):
                  roi_training_total_num_samples=256, roi_training_max_pos_samples=64,
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3, dtype=torch.float32, device='cuda',
-                 f32_form='exact'):
+                 f32_form='exact', training_targets='torch'):
         from .fpn_detector import ResNetFpnDetector, check_caller_f32_form
         check_caller_f32_form(f32_form)
         if top_down_dims != 256 or tuple(roi_feature_size) != (roi_pool_size, roi_pool_size, top_down_dims):
@@ -345,7 +345,8 @@ class ResnetV1Fpn(BaseFPN):
             roi_training_max_pos_samples=roi_training_max_pos_samples,
             prediction_max_objects_per_image=prediction_max_objects_per_image,
             prediction_max_objects_per_class=prediction_max_objects_per_class,
-            prediction_nms_iou_threshold=prediction_nms_iou_threshold, prediction_score_threshold=prediction_score_threshold)
+            prediction_nms_iou_threshold=prediction_nms_iou_threshold, prediction_score_threshold=prediction_score_threshold,
+            training_targets=training_targets)
         self.dense = dense
 
     def _get_roi_head(self):

@@ -6,6 +6,7 @@ back padded together with a device-side count.  The reference-surface modules in
 reference itself does at region_proposal.py:78 / prediction.py:147); ``pipeline.py`` keeps
 everything padded and sync-free.
 """
+import collections
 import ctypes as C
 import math
 
@@ -1205,3 +1206,92 @@ def post_ops(scores, deltas, rois, image_shape, means, stds, max_per_class, max_
             raise ValueError('record must hold max_per_image*6+1 floats')
         L.call('odet_post_ops_record', *head, L.dptr(record, torch.float32, 'record'), L.dptr(ws), nb, L.stream())
     return ob, ol, os_, cnt
+
+
+# ---- fused training targets (csrc/targets.hip) ---------------------------------------------------------------------------------
+TARGETS_MAX_GT = 1024
+TARGETS_MAX_BATCH = 64
+
+AnchorTargets = collections.namedtuple('AnchorTargets', [
+    'labels', 'targets', 'inside', 'outside', 'sample_idx', 'sample_targets', 'counts', 'labels_before_sampling', 'argmax'])
+ProposalTargets = collections.namedtuple('ProposalTargets', [
+    'final_rois', 'final_labels', 'targets', 'inside', 'outside', 'keep', 'gt_assignment', 'counts'])
+
+
+def _gt_offsets(gt_offsets, device):
+    """device int32 [B+1] as it is (never read here); a host sequence is checked against the per-image limit and uploaded"""
+    if isinstance(gt_offsets, torch.Tensor) and gt_offsets.is_cuda:
+        if gt_offsets.dtype != torch.int32 or gt_offsets.dim() != 1 or gt_offsets.numel() < 2:
+            raise TypeError('gt_offsets must be an int32 vector of batch + 1 entries')
+        return gt_offsets.contiguous()
+    off = [int(v) for v in gt_offsets]
+    if len(off) < 2 or off[0] < 0 or any(b < a for a, b in zip(off, off[1:])):
+        raise ValueError('gt_offsets must hold batch + 1 non-decreasing offsets')
+    if max(b - a for a, b in zip(off, off[1:])) > TARGETS_MAX_GT:
+        raise L.OdetError('more than %d ground-truth boxes in one image' % TARGETS_MAX_GT)
+    return torch.tensor(off, dtype=torch.int32, device=device)
+
+
+def anchor_targets(anchors, gt_boxes, gt_offsets, image_shape, pos_iou_threshold, neg_iou_threshold, total_num_samples,
+                   max_pos_samples, means, stds, seed=0, first_image_id=0, dense=True, parity=False, workspace=None):
+    """odet_anchor_target for the B = len(gt_offsets) - 1 images that share `anchors` [N,4]: -> AnchorTargets of
+    labels [B,N], targets / inside / outside [B,N,4] (None with dense=False), sample_idx int32 [B,S], sample_targets [B,S,4],
+    counts int32 [B,5], labels_before_sampling / argmax int32 [B,N] (None unless parity=True).  Nothing is read back."""
+    anchors = _boxes(anchors, 'all_anchors')
+    gt = _boxes(gt_boxes, 'gt_boxes')
+    dev = anchors.device
+    if gt.shape[0] == 0:                     # (no ground truth anywhere: the kernels still want a valid address)
+        gt = gt.new_zeros((1, 4))
+    off = _gt_offsets(gt_offsets, dev)
+    B, N, S = off.numel() - 1, anchors.shape[0], int(total_num_samples)
+
+    def new(shape, dtype=torch.float32):
+        return torch.empty(shape, dtype=dtype, device=dev)
+    labels, targets, inside, outside = (new((B, N)), new((B, N, 4)), new((B, N, 4)), new((B, N, 4))) if dense else (None,) * 4
+    before, argmax = (new((B, N), torch.int32), new((B, N), torch.int32)) if parity else (None, None)
+    sample_idx, sample_targets, counts = new((B, S), torch.int32), new((B, S, 4)), new((B, 5), torch.int32)
+    nb = L.lib().odet_anchor_target_workspace_bytes(N, B, S)
+    ws = workspace if workspace is not None and workspace.numel() >= nb else L.workspace(nb, dev)
+    L.call('odet_anchor_target', L.dptr(anchors), N, L.dptr(gt), L.dptr(off), B, int(image_shape[0]), int(image_shape[1]),
+           float(pos_iou_threshold), float(neg_iou_threshold), S, int(max_pos_samples), L.host4(means, 'target_means'),
+           L.host4(stds, 'target_stds'), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_image_id) & 0xFFFFFFFF, L.dptr(labels),
+           L.dptr(targets), L.dptr(inside), L.dptr(outside), L.dptr(sample_idx), L.dptr(sample_targets), L.dptr(counts),
+           L.dptr(before), L.dptr(argmax), L.dptr(ws), ws.numel(), L.stream())
+    return AnchorTargets(labels, targets, inside, outside, sample_idx, sample_targets, counts, before, argmax)
+
+
+def proposal_targets(rois, gt_boxes, gt_labels, gt_offsets, num_classes, pos_iou_threshold, neg_iou_threshold,
+                     total_num_samples, max_pos_samples, means, stds, reference_row_labels=True, seed=0, first_image_id=0,
+                     roi_counts=None, workspace=None):
+    """odet_proposal_target: rois [B,Rmax,4] (roi_counts: optional device int32 [B]) -> ProposalTargets of final_rois [B,S,4],
+    final_labels int32 [B,S], targets / inside / outside [B,S,4*num_classes], keep int32 [B,S], gt_assignment int32 [B,Rmax],
+    counts int32 [B,4].  Nothing is read back."""
+    rois = L.f32c(rois, 'rois')
+    if rois.dim() != 3 or rois.shape[2] != 4:
+        raise ValueError('rois must have shape [B,Rmax,4], got %s' % (tuple(rois.shape),))
+    gt = _boxes(gt_boxes, 'gt_boxes')
+    dev = rois.device
+    off = _gt_offsets(gt_offsets, dev)
+    B, R, S, W = rois.shape[0], rois.shape[1], int(total_num_samples), 4 * int(num_classes)
+    if off.numel() != B + 1:
+        raise ValueError('gt_offsets has %d entries for %d images' % (off.numel(), B))
+    if not isinstance(gt_labels, torch.Tensor) or not gt_labels.is_cuda:
+        raise L.OdetError('gt_labels must live on the GPU: tf_eager_object_detection_amd has no CPU path')
+    gl = gt_labels.to(torch.int32).contiguous()
+    if gl.numel() != gt.shape[0]:
+        raise ValueError('gt_labels has %d entries for %d boxes' % (gl.numel(), gt.shape[0]))
+    if gt.shape[0] == 0:
+        gt, gl = gt.new_zeros((1, 4)), gl.new_zeros(1)
+
+    def new(shape, dtype=torch.float32):
+        return torch.empty(shape, dtype=dtype, device=dev)
+    out = ProposalTargets(new((B, S, 4)), new((B, S), torch.int32), new((B, S, W)), new((B, S, W)), new((B, S, W)),
+                          new((B, S), torch.int32), new((B, R), torch.int32), new((B, 4), torch.int32))
+    nb = L.lib().odet_proposal_target_workspace_bytes(R, B)
+    ws = workspace if workspace is not None and workspace.numel() >= nb else L.workspace(nb, dev)
+    L.call('odet_proposal_target', L.dptr(rois), L.dptr(roi_counts, torch.int32, 'roi_counts'), R, L.dptr(gt), L.dptr(gl),
+           L.dptr(off), B, int(num_classes), float(pos_iou_threshold), float(neg_iou_threshold), S, int(max_pos_samples),
+           L.host4(means, 'target_means'), L.host4(stds, 'target_stds'), 1 if reference_row_labels else 0,
+           int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_image_id) & 0xFFFFFFFF, *[L.dptr(t) for t in out], L.dptr(ws), ws.numel(),
+           L.stream())
+    return out
