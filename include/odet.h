@@ -37,7 +37,8 @@ extern "C" {
  * (odet_x2_status_offset); the tile-forcing diagnostics left this header and the shipped library (include/odet_diag.h, a
  * separate -DODET_DIAG build).  Added within 103: odet_preprocess_images (the eval loaders' input front end),
  * odet_eval_detect_topk, the odet_coco_* evaluation, the odet_voc_* evaluation and the fused training targets
- * (odet_anchor_target, odet_proposal_target); no existing entry point or struct changed. */
+ * (odet_anchor_target, odet_proposal_target) and the fused training losses with their gradients (odet_rpn_loss,
+ * odet_rpn_loss_backward, odet_roi_loss); no existing entry point or struct changed. */
 #define ODET_VERSION 103
 
 #define ODET_OK 0
@@ -923,6 +924,57 @@ int odet_proposal_target(const float* rois, const int32_t* roi_counts, int max_r
                          uint64_t seed, uint32_t first_image_id, float* final_rois, int32_t* final_labels,
                          float* targets, float* inside, float* outside, int32_t* keep, int32_t* gt_assignment,
                          int32_t* counts, void* workspace, size_t workspace_bytes, odet_stream_t stream);
+
+/* ---- training losses (added within 103) ----------------------------------------------------------------------------
+ * The four losses of model/losses.py:4-28 as the caller models use them (fpn/base_fpn_model.py:278-301,
+ * faster_rcnn/base_faster_rcnn_model.py:200-231), for a BATCH of images, from the outputs of odet_anchor_target /
+ * odet_proposal_target and the raw float32 head outputs, with their gradients with respect to the head outputs.  One launch
+ * per forward, no workspace, no allocation, no host read (graph-capturable), no float atomics; every output bitwise
+ * reproducible and independent of the batch an image sits in.  Limits: batch <= 64, total_num_samples <= 1024
+ * (ODET_E_LIMIT).
+ *
+ * Arithmetic.  Element operations are single float32 operations in the reference's order (no FMA contraction), exp / log are
+ * correctly rounded.  sigma_2 = sigma * sigma, and 1 / sigma_2, sigma_2 / 2, 0.5 / sigma_2 are float32 operations.
+ * A softmax row x[0..C): z_j = x_j - max, e_j = exp(z_j), s = e_0 + e_1 + ... , p_j = e_j / float32(s),
+ * CE = log(float32(s)) - z_label.  A smooth-L1 element: d = inside * (pred - target), sign = |d| < 1 / sigma_2,
+ * l = outside * (d * d * (sigma_2 / 2) * sign + (|d| - 0.5 / sigma_2) * (1 - sign)), gradient outside * inside * (sigma_2 * d
+ * where sign, else +-1 with the sign of d).
+ * Sums are accumulated in FLOAT64 in a fixed order and rounded to float32 once: the classes of a row in ascending order; the
+ * 4 coordinates of an RPN row in ascending order; the 4C columns of a RoI row as 64 partial sums (partial l adds columns
+ * l, l + 64, ... in ascending order) that are then added in ascending l; the rows of an image in ascending order. */
+
+/* scores: `layout` (ODET_RPN_LAYOUT_*, anchors_per_location = A; N % A == 0 for the FRCNN layout) of 2N floats per image,
+ * deltas [batch,N,4]; sample_idx [batch,S], sample_targets [batch,S,4], counts [batch,5] as odet_anchor_target wrote them
+ * (S = total_num_samples).  n = counts[3] + counts[4]; rows r < counts[3] have label 1, rows counts[3] <= r < n label 0.
+ * losses float32 [batch,2] = (cls, reg): cls = float32(sum of the rows' CE) / float32(max(n,1)); reg = float32(sum over the
+ * label-1 rows and their 4 coordinates of l), with inside = 1 and outside = float32(1) / float32(n) (dim=[0,1]: a sum).
+ * row_grad_scores [batch,S,2] = (p_j - [j == label]) / float32(n) and row_grad_deltas [batch,S,4] = the smooth-L1 gradient
+ * (0 on label-0 rows): d loss / d (row of the head outputs) at upstream gradient 1.  Rows >= n are 0.  An image whose counts
+ * row is -1 or whose n is 0 has losses 0 and gradients 0.  All pointers are required. */
+int odet_rpn_loss(const float* scores, const float* deltas, int num_anchors, int batch, int layout,
+                  int anchors_per_location, const int32_t* sample_idx, const float* sample_targets, const int32_t* counts,
+                  int total_num_samples, float sigma, float* losses, float* row_grad_scores, float* row_grad_deltas,
+                  odet_stream_t stream);
+/* The dense gradients: grad_scores in the SAME layout as the scores (2N floats per image) and grad_deltas [batch,N,4], each
+ * nullable and 16-byte aligned: 0 everywhere except the rows of sample_idx, which hold upstream[b][0] * row_grad_scores resp.
+ * upstream[b][1] * row_grad_deltas (upstream: device float32 [batch,2], the gradients arriving at (cls, reg)).  Two launches:
+ * the zero fill, then the scatter (sample_idx holds no duplicates within an image). */
+int odet_rpn_loss_backward(const int32_t* sample_idx, const float* row_grad_scores, const float* row_grad_deltas,
+                           const float* upstream, int num_anchors, int batch, int layout, int anchors_per_location,
+                           int total_num_samples, float* grad_scores, float* grad_deltas, odet_stream_t stream);
+/* scores [batch,R,C], deltas [batch,R,4C] (R = num_rows <= 2048, C = num_classes <= 1024: ODET_E_LIMIT); final_labels
+ * [batch,S], targets / inside / outside [batch,S,4C], counts [batch,4] as odet_proposal_target wrote them.  row_map
+ * (nullable) int32 [batch,R]: head row r belongs to target row row_map[r] (the FPN caller's level-order permutation); null =
+ * identity.  rows = counts[3].  A head row takes part when its target row m satisfies 0 <= m < rows (and its label lies in
+ * 0..C-1); every other head row contributes nothing and gets gradient 0.
+ * losses [batch,2] = (float32(sum over head rows of CE) / float32(max(rows,1)), float32(sum over head rows of the row's
+ * smooth-L1 sum) / float32(max(rows,1))).  grad_scores [batch,R,C] = u_cls * ((p_j - [j == label]) / float32(rows)),
+ * grad_deltas [batch,R,4C] = u_reg * (smooth-L1 gradient / float32(rows)), (u_cls, u_reg) = upstream[b] (device float32
+ * [batch,2]) or (1, 1) when upstream is null.  losses, grad_scores and grad_deltas are each nullable. */
+int odet_roi_loss(const float* scores, const float* deltas, int num_rows, int num_classes, int batch,
+                  const int32_t* final_labels, const float* targets, const float* inside, const float* outside,
+                  const int32_t* counts, int total_num_samples, const int32_t* row_map, float sigma,
+                  const float* upstream, float* losses, float* grad_scores, float* grad_deltas, odet_stream_t stream);
 
 #ifdef __cplusplus
 }

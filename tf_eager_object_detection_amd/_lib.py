@@ -180,6 +180,9 @@ SIGNATURES = {
     'odet_proposal_target_workspace_bytes': (_sz, [_i, _i]),
     'odet_proposal_target': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _i, _f, _f, _i, _i, _vp, _vp, _i, C.c_uint64, C.c_uint32,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'odet_rpn_loss': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
+    'odet_rpn_loss_backward': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'odet_roi_loss': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -129,6 +129,21 @@ __device__ __forceinline__ int d_tg_rank(const unsigned long long* keys, const i
   return r;
 }
 
+// Zero fill of a workspace head (column maxima, counters) as a kernel node, not a memset node: the words cleared are the same.
+// Property relied on: a captured graph of these calls can be replayed any number of times with eager calls in between, and
+// every replay starts from cleared counters (tests/test_losses_gpu.py replays twice; DESIGN 3.9 has what was seen otherwise).
+__global__ void __launch_bounds__(TG_BLOCK) k_tg_zero(uint32_t* p, size_t words) {
+  const size_t i = (size_t)blockIdx.x * TG_BLOCK + threadIdx.x;
+  if (i < words) p[i] = 0u;
+}
+
+static int tg_zero_head(void* workspace, size_t head_bytes, hipStream_t st) {
+  const size_t words = (head_bytes + 3) / 4;               // (the head ends on a 4-byte boundary inside the workspace)
+  hipLaunchKernelGGL(k_tg_zero, dim3((unsigned)((words + TG_BLOCK - 1) / TG_BLOCK)), dim3(TG_BLOCK), 0, st, (uint32_t*)workspace, words);
+  ODET_LAUNCH_CHECK();
+  return ODET_OK;
+}
+
 __device__ __forceinline__ bool d_inside(float4 a, float wmax, float hmax) {
   return a.x >= 0.0f && a.y >= 0.0f && a.z <= wmax && a.w <= hmax;      // bbox_tf.py:94-99
 }
@@ -376,7 +391,7 @@ extern "C" int odet_anchor_target(const float* anchors, int num_anchors, const f
   a.labels = labels; a.targets = (float4*)targets; a.inside = (float4*)inside; a.outside = (float4*)outside;
   a.sample_idx = sample_idx; a.sample_targets = (float4*)sample_targets; a.counts = counts;
   a.labels_before = labels_before_sampling;
-  ODET_HIP(hipMemsetAsync(workspace, 0, head, st));
+  { const int zrc = tg_zero_head(workspace, head, st); if (zrc != ODET_OK) return zrc; }
   const dim3 grid((num_anchors + TG_BLOCK - 1) / TG_BLOCK, batch);
   if (num_anchors > 0) {
     hipLaunchKernelGGL(k_at_colmax, grid, dim3(TG_BLOCK), 0, st, a);
@@ -597,7 +612,7 @@ extern "C" int odet_proposal_target(const float* rois, const int32_t* roi_counts
   a.khi = ar.take<uint32_t>(B * R);
   a.final_rois = (float4*)final_rois; a.final_labels = final_labels; a.targets = targets; a.inside = inside;
   a.outside = outside; a.keep = keep; a.gt_assignment = gt_assignment; a.counts = counts;
-  ODET_HIP(hipMemsetAsync(workspace, 0, head, st));
+  { const int zrc = tg_zero_head(workspace, head, st); if (zrc != ODET_OK) return zrc; }
   if (max_rois > 0) {
     hipLaunchKernelGGL(k_pt_assign, dim3((max_rois + TG_BLOCK - 1) / TG_BLOCK, batch), dim3(TG_BLOCK), 0, st, a);
     ODET_LAUNCH_CHECK();

@@ -14,8 +14,8 @@ import torch
 from .. import ops
 from ..utils.anchor_generator import generate_anchor_base, generate_by_anchor_base_tf
 from .fpn_detector import caller_range_checked
-from .base_fpn_model import _Part, _image_nhwc
-from .losses import cls_loss, smooth_l1_loss
+from .base_fpn_model import _Part, _image_nhwc, check_training_losses
+from .losses import cls_loss, fused_roi_losses, fused_rpn_losses, smooth_l1_loss
 from .prediction import post_ops_prediction
 from .proposal_target import training_target_layers
 from .region_proposal import RegionProposal
@@ -54,8 +54,9 @@ class BaseFasterRcnn(torch.nn.Module):
                  roi_pooling_max_pooling_flag, roi_sigma, roi_training_pos_iou_threshold, roi_training_neg_iou_threshold,
                  roi_training_total_num_samples, roi_training_max_pos_samples, prediction_max_objects_per_image,
                  prediction_max_objects_per_class, prediction_nms_iou_threshold, prediction_score_threshold,
-                 training_targets='torch'):
+                 training_targets='torch', training_losses='torch'):
         super().__init__()
+        self._training_losses = check_training_losses(training_losses, training_targets)
         self.num_classes = num_classes
         self.weight_decay = weight_decay
         self._ratios = ratios
@@ -124,6 +125,9 @@ class BaseFasterRcnn(torch.nn.Module):
         with torch.no_grad():
             image_shape, shared_features, anchors, rpn_score, rpn_bbox_txtytwth, rois = \
                 self._anchors_and_proposals(image, training)
+        if training and self._training_losses == 'hip':
+            return self._fused_losses(rpn_score, rpn_bbox_txtytwth, anchors, rois, gt_bboxes, gt_labels, shared_features,
+                                      image_shape, training)
         if training:
             rpn_labels, rpn_bbox_targets, rpn_in_weights, rpn_out_weights = self._anchor_target(
                 (gt_bboxes, image_shape, anchors), training)
@@ -151,6 +155,29 @@ class BaseFasterRcnn(torch.nn.Module):
                                        extractor_stride=self._extractor_stride, num_classes=self.num_classes)
 
     call = forward
+
+    def _fused_losses(self, rpn_score, rpn_bbox_txtytwth, anchors, rois, gt_bboxes, gt_labels, shared_features, image_shape,
+                      training):
+        """training_losses='hip': the same four scalars from the compact targets, the scores read in their own
+        [A bg | A fg] layout (no re-layout, no dense [N,4] target, no nonzero); image ids advance as in the layers' calls"""
+        off = torch.tensor([0, gt_bboxes.shape[0]], dtype=torch.int32, device=anchors.device)
+        at, pt = self._anchor_target, self._proposal_target
+        anchor_targets = at.batch(gt_bboxes, off, image_shape, anchors, first_image_id=at._next_image_id, dense=False)
+        at._next_image_id += 1
+        rpn_cls_loss, rpn_reg_loss = fused_rpn_losses(rpn_score.float()[None], rpn_bbox_txtytwth.float()[None],
+                                                      anchor_targets, self._rpn_sigma, ops.RPN_LAYOUT_FRCNN, self._num_anchors)
+        # strict=False: no host read.  An image that wants background rows and has no candidate does not raise here as it does on
+        # the 'torch' path: it has rows written < S, and the loss kernel gives the unwritten rows no weight and zero gradient.
+        proposal_targets = pt.batch(rois.reshape(1, -1, 4), gt_bboxes, gt_labels, off, first_image_id=pt._next_image_id,
+                                    strict=False)
+        pt._next_image_id += 1
+        with torch.no_grad():
+            roi_features = self._roi_pooling((shared_features, proposal_targets.final_rois[0], self._extractor_stride),
+                                             training=training)
+            roi_score, roi_bboxes_txtytwth = self._roi_head(roi_features, training=training)
+        roi_cls_loss, roi_reg_loss = fused_roi_losses(roi_score.float()[None], roi_bboxes_txtytwth.float()[None],
+                                                      proposal_targets, self._roi_sigma)
+        return rpn_cls_loss[0], rpn_reg_loss[0], roi_cls_loss[0], roi_reg_loss[0]
 
     def _get_rpn_loss(self, rpn_score, rpn_bbox_txtytwth, anchor_target_labels, anchor_target_bboxes_txtytwth,
                       anchor_target_in_weights, anchor_target_out_weights):
@@ -245,7 +272,8 @@ _COMMON = dict(num_classes=21, weight_decay=0.0001, ratios=(0.5, 1.0, 2.0), scal
                roi_proposal_stds=(0.1, 0.1, 0.2, 0.2), roi_pool_size=7, roi_pooling_max_pooling_flag=True, roi_sigma=1,
                roi_training_pos_iou_threshold=0.5, roi_training_neg_iou_threshold=0.1, roi_training_total_num_samples=128,
                roi_training_max_pos_samples=32, prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
-               prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3, training_targets='torch')
+               prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3, training_targets='torch',
+               training_losses='torch')
 
 
 class ResNetFasterRcnn(_FrcnnFromDense):

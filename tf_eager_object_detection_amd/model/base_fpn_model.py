@@ -16,13 +16,23 @@ import torch
 from .. import ops
 from ..utils.anchor_generator import make_anchors
 from .fpn_detector import caller_range_checked
-from .losses import cls_loss, smooth_l1_loss
+from .losses import cls_loss, fused_roi_losses, fused_rpn_losses, smooth_l1_loss
 from .prediction import post_ops_prediction
 from .proposal_target import training_target_layers
 from .region_proposal import RegionProposal
 from .roi_pooling import RoiPoolingCropAndResize2
 
 __all__ = ['BaseFPN', 'RpnHead', 'ResnetV1Fpn']
+
+
+def check_training_losses(training_losses, training_targets):
+    """training_losses: 'torch' = model/losses.py on the dense targets, 'hip' = the fused losses on the compact targets (which
+    only the fused target stage produces)"""
+    if training_losses not in ('torch', 'hip'):
+        raise ValueError("training_losses must be 'torch' or 'hip', got %r" % (training_losses,))
+    if training_losses == 'hip' and training_targets != 'hip':
+        raise ValueError("training_losses='hip' needs training_targets='hip', got training_targets=%r" % (training_targets,))
+    return training_losses
 
 
 def _image_nhwc(image):
@@ -72,8 +82,10 @@ class BaseFPN(torch.nn.Module):
                  roi_sigma=1, roi_training_pos_iou_threshold=0.5, roi_training_neg_iou_threshold=0.1,
                  roi_training_total_num_samples=128, roi_training_max_pos_samples=32,
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
-                 prediction_nms_iou_threshold=0.3, prediction_score_threshold=0., training_targets='torch'):
+                 prediction_nms_iou_threshold=0.3, prediction_score_threshold=0., training_targets='torch',
+                 training_losses='torch'):
         super().__init__()
+        self._training_losses = check_training_losses(training_losses, training_targets)
         self.roi_feature_size = roi_feature_size
         self.num_classes = num_classes
         self.weight_decay = weight_decay
@@ -177,6 +189,9 @@ class BaseFPN(torch.nn.Module):
             all_anchors = self._get_anchors(image_shape)
             cur_scores = self._fg_scores(all_fpn_scores)
             rois = self._rpn_proposal((all_fpn_bbox_pred, all_anchors, cur_scores, image_shape), training=training)
+        if training and self._training_losses == 'hip':
+            return self._fused_losses(all_fpn_scores, all_fpn_bbox_pred, all_anchors, rois, gt_bboxes, gt_labels, p_list,
+                                      image_shape, training)
         if training:
             rpn_labels, rpn_bbox_targets, rpn_in_weights, rpn_out_weights = self._anchor_target(
                 (gt_bboxes, image_shape, all_anchors), training)
@@ -208,6 +223,29 @@ class BaseFPN(torch.nn.Module):
                                        num_classes=self.num_classes)
 
     call = forward
+
+    def _fused_losses(self, all_fpn_scores, all_fpn_bbox_pred, all_anchors, rois, gt_bboxes, gt_labels, p_list, image_shape,
+                      training):
+        """training_losses='hip': the same four scalars from the compact targets (no dense [N,4] target, no nonzero); the
+        image ids advance as the target layers' own single-image calls advance them, so both settings draw the same samples"""
+        off = torch.tensor([0, gt_bboxes.shape[0]], dtype=torch.int32, device=all_anchors.device)
+        at, pt = self._anchor_target, self._proposal_target
+        anchor_targets = at.batch(gt_bboxes, off, image_shape, all_anchors, first_image_id=at._next_image_id, dense=False)
+        at._next_image_id += 1
+        rpn_cls_loss, rpn_reg_loss = fused_rpn_losses(all_fpn_scores.float()[None], all_fpn_bbox_pred.float()[None],
+                                                      anchor_targets, self._rpn_sigma, ops.RPN_LAYOUT_FPN, self._num_anchors)
+        # strict=False: no host read.  An image that wants background rows and has no candidate does not raise here as it does on
+        # the 'torch' path: it has rows written < S, and the loss kernel gives the unwritten rows no weight and zero gradient.
+        proposal_targets = pt.batch(rois.reshape(1, -1, 4), gt_bboxes, gt_labels, off, first_image_id=pt._next_image_id,
+                                    strict=False)
+        pt._next_image_id += 1
+        rois_list, selected_idx = self._assign_levels(proposal_targets.final_rois[0])
+        with torch.no_grad():
+            roi_features = self._get_roi_features(rois_list, p_list, image_shape)
+            roi_score, roi_bboxes_txtytwth = self._roi_head(roi_features, training=training)
+        roi_cls_loss, roi_reg_loss = fused_roi_losses(roi_score.float()[None], roi_bboxes_txtytwth.float()[None],
+                                                      proposal_targets, self._roi_sigma, row_map=selected_idx[None])
+        return rpn_cls_loss[0], rpn_reg_loss[0], roi_cls_loss[0], roi_reg_loss[0]
 
     def _get_rpn_loss(self, rpn_score, rpn_bbox_txtytwth, anchor_target_labels, anchor_target_bboxes_txtytwth,
                       anchor_target_in_weights, anchor_target_out_weights):
@@ -309,7 +347,7 @@ class ResnetV1Fpn(BaseFPN):
                  roi_training_total_num_samples=256, roi_training_max_pos_samples=64,
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3, dtype=torch.float32, device='cuda',
-                 f32_form='exact', training_targets='torch'):
+                 f32_form='exact', training_targets='torch', training_losses='torch'):
         from .fpn_detector import ResNetFpnDetector, check_caller_f32_form
         check_caller_f32_form(f32_form)
         if top_down_dims != 256 or tuple(roi_feature_size) != (roi_pool_size, roi_pool_size, top_down_dims):
@@ -346,7 +384,7 @@ class ResnetV1Fpn(BaseFPN):
             prediction_max_objects_per_image=prediction_max_objects_per_image,
             prediction_max_objects_per_class=prediction_max_objects_per_class,
             prediction_nms_iou_threshold=prediction_nms_iou_threshold, prediction_score_threshold=prediction_score_threshold,
-            training_targets=training_targets)
+            training_targets=training_targets, training_losses=training_losses)
         self.dense = dense
 
     def _get_roi_head(self):

@@ -100,13 +100,15 @@ class FusedProposalTarget:
         self._strict = strict
         self._next_image_id = 0
 
-    def batch(self, rois, gt_boxes, gt_labels, gt_offsets, first_image_id=0, roi_counts=None):
-        """rois [B,Rmax,4], packed ground truth -> ops.ProposalTargets, every tensor batch-first."""
+    def batch(self, rois, gt_boxes, gt_labels, gt_offsets, first_image_id=0, roi_counts=None, strict=None):
+        """rois [B,Rmax,4], packed ground truth -> ops.ProposalTargets, every tensor batch-first.  `strict` overrides the
+        layer's setting for this call (False: no host read)."""
         out = ops.proposal_targets(rois, gt_boxes, gt_labels, gt_offsets, self._num_classes, self._pos_iou_threshold,
                                    self._neg_iou_threshold, self._total_num_samples, self._max_pos_samples,
                                    self._target_means, self._target_stds, reference_row_labels=self._reference_row_labels,
                                    seed=self._seed, first_image_id=first_image_id, roi_counts=roi_counts)
-        if self._strict and bool((out.counts[:, 3] < self._total_num_samples).any()):      # the one host read
+        if (self._strict if strict is None else strict) and \
+                bool((out.counts[:, 3] < self._total_num_samples).any()):                       # the one host read
             raise ValueError('no background RoI to sample from (the reference fails here as well)')
         return out
 

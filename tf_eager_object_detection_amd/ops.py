@@ -1295,3 +1295,81 @@ def proposal_targets(rois, gt_boxes, gt_labels, gt_offsets, num_classes, pos_iou
            int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_image_id) & 0xFFFFFFFF, *[L.dptr(t) for t in out], L.dptr(ws), ws.numel(),
            L.stream())
     return out
+
+
+# ---- fused training losses (csrc/losses.hip) ------------------------------------------------------------------------------------
+LOSSES_MAX_CLASSES = 1024
+LOSSES_MAX_ROWS = 2048
+
+RpnLosses = collections.namedtuple('RpnLosses', ['losses', 'row_grad_scores', 'row_grad_deltas'])
+RpnLossGrads = collections.namedtuple('RpnLossGrads', ['grad_scores', 'grad_deltas'])
+RoiLosses = collections.namedtuple('RoiLosses', ['losses', 'grad_scores', 'grad_deltas'])
+
+
+def _rpn_head_outputs(scores, deltas, B):
+    """float32 contiguous scores (2N floats per image, any shape) and deltas (4N floats per image) of B images -> (s, d, N)"""
+    scores, deltas = L.f32c(scores, 'rpn scores'), L.f32c(deltas, 'rpn deltas')
+    if deltas.numel() % (4 * B) or scores.numel() * 2 != deltas.numel():
+        raise ValueError('rpn scores / deltas of %d / %d elements do not hold 2N / 4N floats for each of %d images'
+                         % (scores.numel(), deltas.numel(), B))
+    return scores, deltas, deltas.numel() // (4 * B)
+
+
+def rpn_losses(scores, deltas, sample_idx, sample_targets, counts, sigma, layout=RPN_LAYOUT_FPN, anchors_per_location=1):
+    """odet_rpn_loss: the head outputs of B images (scores in `layout` with A = `anchors_per_location`, deltas [B,N,4]) and the
+    compact anchor targets (AnchorTargets.sample_idx / sample_targets / counts) -> RpnLosses(losses [B,2] = (cls, reg), row_grad_scores [B,S,2],
+    row_grad_deltas [B,S,4]).  Nothing is read back."""
+    B, S = int(sample_idx.shape[0]), int(sample_idx.shape[1])
+    scores, deltas, N = _rpn_head_outputs(scores, deltas, B)
+    dev = scores.device
+    out = RpnLosses(torch.empty((B, 2), dtype=torch.float32, device=dev), torch.empty((B, S, 2), dtype=torch.float32, device=dev),
+                    torch.empty((B, S, 4), dtype=torch.float32, device=dev))
+    L.call('odet_rpn_loss', L.dptr(scores), L.dptr(deltas), N, B, int(layout), int(anchors_per_location),
+           L.dptr(sample_idx, torch.int32, 'sample_idx'), L.dptr(sample_targets, torch.float32, 'sample_targets'),
+           L.dptr(counts, torch.int32, 'counts'), S, float(sigma), *[L.dptr(t) for t in out], L.stream())
+    return out
+
+
+def rpn_losses_backward(sample_idx, row_grad_scores, row_grad_deltas, upstream, num_anchors, layout=RPN_LAYOUT_FPN,
+                        anchors_per_location=1, scores=True, deltas=True):
+    """odet_rpn_loss_backward for N = `num_anchors` anchors per image (the header's name): upstream float32 [B,2] (device) ->
+    RpnLossGrads(grad_scores [B, 2N] in the scores' layout, grad_deltas [B,N,4]); `scores` / `deltas` = False leaves that gradient out (None)."""
+    B, S, N = int(sample_idx.shape[0]), int(sample_idx.shape[1]), int(num_anchors)
+    dev = sample_idx.device
+    gs = torch.empty((B, 2 * N), dtype=torch.float32, device=dev) if scores else None
+    gd = torch.empty((B, N, 4), dtype=torch.float32, device=dev) if deltas else None
+    L.call('odet_rpn_loss_backward', L.dptr(sample_idx, torch.int32, 'sample_idx'),
+           L.dptr(row_grad_scores, torch.float32, 'row_grad_scores'), L.dptr(row_grad_deltas, torch.float32, 'row_grad_deltas'),
+           L.dptr(upstream, torch.float32, 'upstream'), N, B, int(layout), int(anchors_per_location), S, L.dptr(gs), L.dptr(gd),
+           L.stream())
+    return RpnLossGrads(gs, gd)
+
+
+def roi_losses(scores, deltas, final_labels, targets, inside, outside, counts, sigma, row_map=None, upstream=None,
+               losses=True, grads=True, grad_scores=True, grad_deltas=True):
+    """odet_roi_loss: scores [B,R,C], deltas [B,R,4C] and the outputs of ops.proposal_targets -> RoiLosses(losses [B,2] =
+    (cls, reg), grad_scores [B,R,C], grad_deltas [B,R,4C]) (None where not asked for: `losses`, `grads` for both gradients,
+    `grad_scores` / `grad_deltas` for one).  row_map: int32 [B,R], head row ->
+    target row; upstream: device float32 [B,2].  Nothing is read back."""
+    scores, deltas = L.f32c(scores, 'roi scores'), L.f32c(deltas, 'roi deltas')
+    if scores.dim() != 3 or deltas.dim() != 3 or deltas.shape[:2] != scores.shape[:2] or deltas.shape[2] != 4 * scores.shape[2]:
+        raise ValueError('roi scores / deltas must have shapes [B,R,C] / [B,R,4C], got %s / %s'
+                         % (tuple(scores.shape), tuple(deltas.shape)))
+    B, R, C = (int(v) for v in scores.shape)
+    S = int(final_labels.shape[1])
+    for name, t, shape in (('final_labels', final_labels, (B, S)), ('targets', targets, (B, S, 4 * C)),
+                           ('inside', inside, (B, S, 4 * C)), ('outside', outside, (B, S, 4 * C)), ('counts', counts, (B, 4))):
+        if tuple(t.shape) != shape:
+            raise ValueError('%s of shape %s does not match %s (%d images, %d classes)' % (name, tuple(t.shape), shape, B, C))
+    if row_map is not None and tuple(row_map.shape) != (B, R):
+        raise ValueError('row_map must have shape [%d,%d]' % (B, R))
+    dev = scores.device
+    out = RoiLosses(torch.empty((B, 2), dtype=torch.float32, device=dev) if losses else None,
+                    torch.empty((B, R, C), dtype=torch.float32, device=dev) if grads and grad_scores else None,
+                    torch.empty((B, R, 4 * C), dtype=torch.float32, device=dev) if grads and grad_deltas else None)
+    L.call('odet_roi_loss', L.dptr(scores), L.dptr(deltas), R, C, B, L.dptr(final_labels, torch.int32, 'final_labels'),
+           L.dptr(targets, torch.float32, 'targets'), L.dptr(inside, torch.float32, 'inside'),
+           L.dptr(outside, torch.float32, 'outside'), L.dptr(counts, torch.int32, 'counts'), S,
+           L.dptr(row_map, torch.int32, 'row_map'), float(sigma), L.dptr(upstream, torch.float32, 'upstream'),
+           *[L.dptr(t) for t in out], L.stream())
+    return out
