@@ -129,6 +129,80 @@ def test_argument_errors_are_reported_through_the_abi():
     assert L.odet_post_ops_workspace_bytes(21, 50) > 20 * 50 * 20
 
 
+# ---- the rejection rules of the 15 float32-form convolution entry points (conv3x3, conv3x3_levels, pointwise, lateral_merge,
+# pointwise_dual, each as f32 / x3 / x2).  Argument validation runs before any HIP call, so every row below returns
+# ODET_E_INVALID on a machine without a GPU; the non-null pointers are pointer-VALUED integers nothing dereferences (only
+# `levels` is a real array: the library reads its entries).  A rule that differs between the forms names the forms it holds on.
+_F32_ENTRY_ARGS = {
+    'conv3x3': ('x', 'w', 'bias', 'y', 'batch', 'H', 'W', 'cin', 'cout', 'relu'),
+    'conv3x3_levels': ('levels', 'num_levels', 'w', 'bias', 'batch', 'cin', 'cout', 'relu'),
+    'pointwise': ('x', 'w', 'bias', 'residual', 'y', 'batch', 'H', 'W', 'stride', 'cin', 'cout', 'relu'),
+    'lateral_merge': ('x', 'w', 'bias', 'top', 'th', 'tw', 'y', 'batch', 'H', 'W', 'cin', 'cout'),
+    'pointwise_dual': ('x', 'cin', 'x2', 'cin2', 'H', 'W', 'stride', 'w', 'bias', 'y', 'batch', 'cout', 'relu'),
+}
+_F32_FORM_TAIL = {'f32': ('stream',), 'x3': ('ws', 'ws_bytes', 'stream'), 'x2': ('w_exp', 'ws', 'ws_bytes', 'stream')}
+_F32_GOOD = dict(x=0x10000, w=0x20000, bias=0x30000, y=0x40000, residual=0x50000, top=0x60000, x2=0x70000, ws=0x80000,
+                 ws_bytes=1 << 20, stream=None, batch=1, H=8, W=8, th=4, tw=4, stride=1, cin=64, cin2=64, cout=64, relu=0,
+                 w_exp=0, num_levels=2)
+_ALL_FORMS, _SPLIT_FORMS = ('f32', 'x3', 'x2'), ('x3', 'x2')
+
+
+def _f32_rejections():
+    def null(*names):
+        return [('null ' + n, {n: None}, _ALL_FORMS) for n in names]
+
+    def odd(forms, *names):
+        return [('misaligned ' + n, {n: _F32_GOOD[n] + 4}, forms) for n in names]
+
+    sizes = [('batch 0', {'batch': 0}, _ALL_FORMS), ('batch -1', {'batch': -1}, _ALL_FORMS),
+             ('cin 48', {'cin': 48}, _ALL_FORMS),
+             ('cout 96', {'cout': 96}, _ALL_FORMS), ('cout 0', {'cout': 0}, _ALL_FORMS),
+             ('w_exp 101', {'w_exp': 101}, ('x2',)), ('w_exp -101', {'w_exp': -101}, ('x2',))]
+    maps = [('H 0', {'H': 0}, _ALL_FORMS), ('W 0', {'W': 0}, _ALL_FORMS)]
+    # the exact form needs two K-steps (64 channels along K), the split-precision forms one
+    cin0 = [('cin 0', {'cin': 0}, _ALL_FORMS)]
+    k32 = cin0 + [('cin 32', {'cin': 32}, ('f32',))]
+    # Not in the table: "shortcut and top together" and "merge with relu" (no entry point can pass either combination); a second
+    # source with a bad channel count, a level with a null map or H, W <= 0, the 3x3 forms' misaligned maps and the 4 GiB
+    # bounds (all checked only after the kernels' one-time device set-up, which needs a device).
+    return {
+        # only the split-precision 3x3 forms check the alignment of weights and bias
+        'conv3x3': null('x', 'w', 'y') + sizes + cin0 + odd(_SPLIT_FORMS, 'w', 'bias'),
+        'conv3x3_levels': null('levels', 'w') + sizes + cin0 + odd(_SPLIT_FORMS, 'w', 'bias')
+        + [('num_levels 0', {'num_levels': 0}, _ALL_FORMS), ('num_levels 9', {'num_levels': 9}, _ALL_FORMS)],
+        'pointwise': null('x', 'w', 'y') + sizes + maps + k32 + [('stride 3', {'stride': 3}, _ALL_FORMS)]
+        + odd(_ALL_FORMS, 'x', 'w', 'bias', 'residual', 'y'),
+        'lateral_merge': null('x', 'w', 'y', 'top') + sizes + maps + k32
+        + [('th 0', {'th': 0}, _ALL_FORMS), ('tw 0', {'tw': 0}, _ALL_FORMS)] + odd(_ALL_FORMS, 'x', 'w', 'bias', 'top', 'y'),
+        'pointwise_dual': null('x', 'w', 'y', 'x2') + sizes + maps + [('stride 3', {'stride': 3}, _ALL_FORMS)]
+        # (the exact form counts K over both sources, so it takes cin 0 beside a second source of 64; the split forms do not)
+        + [('cin 32 + cin2 0', {'cin': 32, 'cin2': 0}, ('f32',)), ('cin 0', {'cin': 0}, _SPLIT_FORMS)] + odd(_ALL_FORMS, 'x', 'x2', 'w', 'bias', 'y'),
+    }
+
+
+@pytest.mark.parametrize('form', _ALL_FORMS)
+@pytest.mark.parametrize('entry', sorted(_F32_ENTRY_ARGS))
+def test_float32_form_entry_points_reject_bad_arguments_before_any_device_call(entry, form):
+    from tf_eager_object_detection_amd import _lib
+    L = _lib.lib()
+    fn = getattr(L, 'odet_conv3x3_%s_levels' % form if entry == 'conv3x3_levels' else 'odet_%s_%s' % (entry, form))
+    levels = (_lib.OdetConvLevel * _lib.MAX_LEVELS)()
+    for i in range(_lib.MAX_LEVELS):
+        levels[i].x, levels[i].y, levels[i].H, levels[i].W = 0x100000 * (i + 1), 0x100000 * (i + 1) + 0x80000, 8 >> min(i, 3), 8
+    names = _F32_ENTRY_ARGS[entry] + _F32_FORM_TAIL[form]
+    rows = [r for r in _f32_rejections()[entry] if form in r[2]]
+    assert len(rows) >= 9
+    for label, bad, _ in rows:
+        assert set(bad) <= set(names), label
+        args = dict(_F32_GOOD, levels=levels)
+        args.update(bad)
+        rc = fn(*[args[n] for n in names])
+        msg = L.odet_last_error()
+        print('%s %s: %s -> %d %r' % (entry, form, label, rc, msg))
+        assert rc == -1, '%s (%s): %s returned %d: %r' % (fn.__name__, form, label, rc, msg)      # ODET_E_INVALID
+        assert msg.startswith(b'odet_') and b' failed: ' not in msg, msg                            # (no HIP call was made)
+
+
 def test_no_cpu_fallback():
     from tf_eager_object_detection_amd import _lib
     from tf_eager_object_detection_amd.utils.bbox_transform import decode_bbox_with_mean_and_std

@@ -28,7 +28,7 @@
 typedef __amdgpu_buffer_rsrc_t f32_rsrc_t;
 typedef __attribute__((address_space(3))) void* f32_lds_ptr;
 
-#define F32_BK 32                 // input channels per K-step (128 bytes per row)
+#define F32_BK CONV_F32_BK        // input channels per K-step (128 bytes per row)
 #define F32_LDS_MAX (160 * 1024)
 
 template <int MT, int WN, int TAPS>
@@ -226,28 +226,20 @@ __global__ void __launch_bounds__(512) k_pointwise_f32(ConvF32Params p) {
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
-template <typename F>
-static void f32_for_each_kernel(F f) {
-  f((const void*)k_conv3x3_f32<4, 4>); f((const void*)k_conv3x3_f32<5, 4>); f((const void*)k_conv3x3_f32<6, 4>);
-  f((const void*)k_conv3x3_f32<7, 4>); f((const void*)k_conv3x3_f32<8, 4>); f((const void*)k_conv3x3_f32<2, 2>);
-  f((const void*)k_conv3x3_f32<3, 2>); f((const void*)k_conv3x3_f32<4, 2>); f((const void*)k_conv3x3_f32<1, 1>);
-  f((const void*)k_conv3x3_f32<2, 1>);
-  f((const void*)k_pointwise_f32<4, 4>); f((const void*)k_pointwise_f32<5, 4>); f((const void*)k_pointwise_f32<6, 4>);
-  f((const void*)k_pointwise_f32<7, 4>); f((const void*)k_pointwise_f32<8, 4>); f((const void*)k_pointwise_f32<2, 2>);
-  f((const void*)k_pointwise_f32<3, 2>); f((const void*)k_pointwise_f32<4, 2>); f((const void*)k_pointwise_f32<1, 1>);
-  f((const void*)k_pointwise_f32<2, 1>);
-}
+// tiles (MT, WN): (8 / WN) * 16 * MT pixels x 64 * WN channels
+#define F32_FOR_TILES(F) F(4, 4) F(5, 4) F(6, 4) F(7, 4) F(8, 4) F(2, 2) F(3, 2) F(4, 2) F(1, 1) F(2, 1)
+
+// the exact form's values of the checks the forms differ on (inherited, not designed: conv_f32_common.h)
+static const ConvF32Rules F32_RULES = {4ull, 1ll << 31, false};
 
 static hipError_t f32_prepare_kernels() {
+#define F32_C(MT_, WN_) (const void*)k_conv3x3_f32<MT_, WN_>,
+#define F32_P(MT_, WN_) (const void*)k_pointwise_f32<MT_, WN_>,
+  static const void* const kernels[] = {F32_FOR_TILES(F32_C) F32_FOR_TILES(F32_P)};
+#undef F32_C
+#undef F32_P
   static OdetPerDeviceOnce once;
-  return once.run([] {
-    hipError_t rc = hipSuccess;
-    f32_for_each_kernel([&rc](const void* k) {
-      const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, F32_LDS_MAX);
-      if (e != hipSuccess) rc = e;
-    });
-    return rc;
-  });
+  return conv_f32_raise_lds_limit(&once, kernels, sizeof(kernels) / sizeof(kernels[0]), F32_LDS_MAX);
 }
 
 static unsigned f32_lds_bytes(int tm, int tn) {          // (the kernel's NSTAGE rule)
@@ -284,139 +276,69 @@ static void f32_pick_tile(const long long* M, int num_levels, int cout, int* wn_
 template <bool PW>
 static void f32_launch_tile(int wn, int mt, dim3 grid, unsigned lds_bytes, hipStream_t st, const ConvF32Params& p) {
 #define F32_L(MT_, WN_)                                                                                     \
-  do {                                                                                                      \
+  if (mt == MT_ && wn == WN_) {                                                                             \
     if (PW) hipLaunchKernelGGL((k_pointwise_f32<MT_, WN_>), grid, dim3(512), lds_bytes, st, p);             \
     else hipLaunchKernelGGL((k_conv3x3_f32<MT_, WN_>), grid, dim3(512), lds_bytes, st, p);                  \
-  } while (0)
-  switch (wn * 16 + mt) {
-    case 4 * 16 + 4: F32_L(4, 4); break;
-    case 4 * 16 + 5: F32_L(5, 4); break;
-    case 4 * 16 + 6: F32_L(6, 4); break;
-    case 4 * 16 + 7: F32_L(7, 4); break;
-    case 4 * 16 + 8: F32_L(8, 4); break;
-    case 2 * 16 + 2: F32_L(2, 2); break;
-    case 2 * 16 + 3: F32_L(3, 2); break;
-    case 2 * 16 + 4: F32_L(4, 2); break;
-    case 1 * 16 + 1: F32_L(1, 1); break;
-    default: F32_L(2, 1); break;
+    return;                                                                                                 \
   }
+  F32_FOR_TILES(F32_L)
 #undef F32_L
 }
 
-static void f32_defaults(ConvF32Params* p) {
-  p->stride = 1; p->Ho = p->Wo = 0; p->Min = 0; p->res = nullptr; p->top = nullptr; p->th = p->tw = 0; p->tys = p->txs = 0.0f;
-  p->x2 = nullptr; p->cin2 = 0; p->k1steps = 0; p->Min2 = 0;
-  p->ksplit = 0; p->part = nullptr; p->ticket = nullptr; p->acc_scale = 1.0f; p->status = nullptr;
-}
-
-static int conv3x3_f32_launch(const odet_conv_level_t* levels, int num_levels, const void* w, const void* bias, int batch,
-                              int cin, int cout, int relu, hipStream_t st) {
-  ODET_REQUIRE(levels && w, "odet_conv3x3_f32: null pointer");
-  ODET_REQUIRE(num_levels >= 1 && num_levels <= ODET_MAX_LEVELS, "odet_conv3x3_f32: num_levels %d out of range", num_levels);
-  ODET_REQUIRE(batch > 0, "odet_conv3x3_f32: bad batch");
-  ODET_REQUIRE(cin > 0 && cin % F32_BK == 0, "odet_conv3x3_f32: cin %d must be a multiple of %d", cin, F32_BK);
-  ODET_REQUIRE(cout > 0 && cout % 64 == 0, "odet_conv3x3_f32: cout %d must be a multiple of 64", cout);
-  ODET_REQUIRE((unsigned long long)cout * 9ull * cin * 4ull < 0x7FFFFFFFull, "odet_conv3x3_f32: weights too large");
+// a filled plan -> the kernels' LDS limit, the tile, the plan's tile-dependent rest, the launch
+template <bool PW>
+static int f32_launch(const char* who, ConvF32Params* p, hipStream_t st) {
   ODET_HIP(f32_prepare_kernels());
-  ConvF32Params p;
-  f32_defaults(&p);
-  for (int l = 0; l < ODET_MAX_LEVELS; ++l) {
-    const odet_conv_level_t& L = levels[l < num_levels ? l : 0];
-    ODET_REQUIRE(L.x && L.y && L.H > 0 && L.W > 0, "odet_conv3x3_f32: bad level %d", l);
-    const long long M = (long long)batch * L.H * L.W;
-    ODET_REQUIRE((unsigned long long)M * cin * 4ull + 2ull * (L.W + 1) * cin * 4ull < 0xFFFFFFF0ull,
-                 "odet_conv3x3_f32: level %d input larger than 4 GiB", l);
-    p.x[l] = (const float*)L.x; p.y[l] = (float*)L.y; p.M[l] = M; p.H[l] = L.H; p.W[l] = L.W;
-  }
   int wn, mt;
-  f32_pick_tile(p.M, num_levels, cout, &wn, &mt);
+  f32_pick_tile(p->M, p->num_levels, p->cout, &wn, &mt);
   const int TMsel = (8 / wn) * 16 * mt;
-  long long total = 0;
-  for (int l = 0; l < ODET_MAX_LEVELS; ++l) {
-    p.tile_start[l] = total;
-    if (l < num_levels) total += (p.M[l] + TMsel - 1) / TMsel;
-  }
-  for (int l = num_levels; l <= ODET_MAX_LEVELS; ++l) p.tile_start[l] = total;
-  p.w = (const float*)w; p.bias = (const float*)bias;
-  p.num_levels = num_levels; p.cin = cin; p.cout = cout; p.relu = relu ? 1 : 0;
-  p.tiles_n = cout / (64 * wn);
-  const long long blocks = (total + 7) / 8 * 8 * p.tiles_n;
-  ODET_REQUIRE(blocks < (1ll << 31), "odet_conv3x3_f32: too many workgroups");
-  f32_launch_tile<false>(wn, mt, dim3((unsigned)blocks), f32_lds_bytes(TMsel, 64 * wn), st, p);
+  long long blocks;
+  const int rt = conv_f32_plan_tiles(who, F32_RULES, TMsel, wn, p, &blocks);
+  if (rt != ODET_OK) return rt;
+  f32_launch_tile<PW>(wn, mt, dim3((unsigned)blocks), f32_lds_bytes(TMsel, 64 * wn), st, *p);
   ODET_LAUNCH_CHECK();
   return ODET_OK;
+}
+
+static int conv3x3_f32_launch(const char* who, const odet_conv_level_t* levels, int num_levels, const void* w, const void* bias,
+                              int batch, int cin, int cout, int relu, hipStream_t st) {
+  ConvF32Params p;
+  const int rp = conv_f32_plan_levels(who, F32_RULES, levels, num_levels, w, bias, batch, cin, cout, relu, &p);
+  return rp != ODET_OK ? rp : f32_launch<false>(who, &p, st);
 }
 
 extern "C" int odet_conv3x3_f32(const void* x, const void* w, const void* bias, void* y, int batch, int H, int W, int cin,
                                 int cout, int relu, odet_stream_t stream) {
   ODET_REQUIRE(x && y, "odet_conv3x3_f32: null pointer");
   const odet_conv_level_t one{x, y, H, W};
-  return conv3x3_f32_launch(&one, 1, w, bias, batch, cin, cout, relu, (hipStream_t)stream);
+  return conv3x3_f32_launch("odet_conv3x3_f32", &one, 1, w, bias, batch, cin, cout, relu, (hipStream_t)stream);
 }
 
 extern "C" int odet_conv3x3_f32_levels(const odet_conv_level_t* levels, int num_levels, const void* w, const void* bias,
                                        int batch, int cin, int cout, int relu, odet_stream_t stream) {
-  return conv3x3_f32_launch(levels, num_levels, w, bias, batch, cin, cout, relu, (hipStream_t)stream);
+  return conv3x3_f32_launch("odet_conv3x3_f32_levels", levels, num_levels, w, bias, batch, cin, cout, relu, (hipStream_t)stream);
 }
 
-struct PwF32Epilogue { const void* res; const void* top; int th, tw; const void* x2; int cin2; };
-
 static int pointwise_f32_launch(const char* who, const void* x, const void* w, const void* bias, void* y, int batch, int H,
-                                int W, int stride, int cin, int cout, int relu, const PwF32Epilogue& epi, hipStream_t st) {
-  ODET_REQUIRE(x && w && y, "%s: null pointer", who);
-  ODET_REQUIRE(batch > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2), "%s: bad shape", who);
+                                int W, int stride, int cin, int cout, int relu, const ConvF32PwEpilogue& epi, hipStream_t st) {
+  // inherited, not designed: the exact form asks for two K-steps along K over both sources, the split forms for a positive cin
   ODET_REQUIRE(cin % F32_BK == 0 && cin + (epi.x2 ? epi.cin2 : 0) >= 2 * F32_BK,
                "%s: cin %d must be a multiple of %d, at least %d along K", who, cin, F32_BK, 2 * F32_BK);
-  ODET_REQUIRE(cout > 0 && cout % 64 == 0, "%s: cout %d must be a multiple of 64", who, cout);
-  ODET_REQUIRE(((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)bias | (uintptr_t)epi.res | (uintptr_t)epi.top |
-                (uintptr_t)epi.x2) % 16 == 0, "%s: pointers must be 16-byte aligned", who);
-  ODET_REQUIRE(!(epi.res && epi.top), "%s: shortcut and top-down merge exclude each other", who);
-  ODET_REQUIRE(!epi.top || (stride == 1 && epi.th > 0 && epi.tw > 0 && !relu), "%s: bad merge arguments", who);
-  ODET_HIP(f32_prepare_kernels());
-  const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
-  const long long M = (long long)batch * Ho * Wo;
-  const long long Min = epi.x2 ? M : (long long)batch * H * W;
-  ODET_REQUIRE((unsigned long long)Min * cin * 4ull < 0xFFFFFFF0ull, "%s: input larger than 4 GiB", who);
-  ODET_REQUIRE(!epi.x2 || (epi.cin2 > 0 && epi.cin2 % F32_BK == 0 &&
-                           (unsigned long long)batch * H * W * epi.cin2 * 4ull < 0xFFFFFFF0ull), "%s: bad second source", who);
-  ODET_REQUIRE((unsigned long long)cout * (cin + (epi.x2 ? epi.cin2 : 0)) * 4ull < 0x7FFFFFFFull, "%s: weights too large", who);
   ConvF32Params p;
-  f32_defaults(&p);
-  for (int l = 0; l < ODET_MAX_LEVELS; ++l) {
-    p.x[l] = (const float*)x; p.y[l] = (float*)y; p.M[l] = M; p.H[l] = H; p.W[l] = W;
-  }
-  p.res = (const float*)epi.res;
-  p.top = (const float*)epi.top; p.th = epi.th; p.tw = epi.tw;
-  p.tys = epi.top ? (float)epi.th / (float)Ho : 0.0f;
-  p.txs = epi.top ? (float)epi.tw / (float)Wo : 0.0f;
-  p.stride = stride; p.Ho = Ho; p.Wo = Wo; p.Min = Min;
-  p.x2 = (const float*)epi.x2; p.cin2 = epi.x2 ? epi.cin2 : 0; p.k1steps = cin / F32_BK; p.Min2 = (long long)batch * H * W;
-  int wn, mt;
-  f32_pick_tile(&M, 1, cout, &wn, &mt);
-  const int TMsel = (8 / wn) * 16 * mt;
-  p.tiles_n = cout / (64 * wn);
-  const long long total = (M + TMsel - 1) / TMsel;
-  p.tile_start[0] = 0;
-  for (int l = 1; l <= ODET_MAX_LEVELS; ++l) p.tile_start[l] = total;
-  p.w = (const float*)w; p.bias = (const float*)bias;
-  p.num_levels = 1; p.cin = cin; p.cout = cout; p.relu = relu ? 1 : 0;
-  const long long blocks = (total + 7) / 8 * 8 * p.tiles_n;
-  ODET_REQUIRE(blocks < (1ll << 31), "%s: too many workgroups", who);
-  f32_launch_tile<true>(wn, mt, dim3((unsigned)blocks), f32_lds_bytes(TMsel, 64 * wn), st, p);
-  ODET_LAUNCH_CHECK();
-  return ODET_OK;
+  const int rp = conv_f32_plan_pointwise(who, F32_RULES, x, w, bias, y, batch, H, W, stride, cin, cout, relu, epi, &p);
+  return rp != ODET_OK ? rp : f32_launch<true>(who, &p, st);
 }
 
 extern "C" int odet_pointwise_f32(const void* x, const void* w, const void* bias, const void* residual, void* y, int batch,
                                   int H, int W, int stride, int cin, int cout, int relu, odet_stream_t stream) {
-  const PwF32Epilogue e{residual, nullptr, 0, 0, nullptr, 0};
+  const ConvF32PwEpilogue e{residual, nullptr, 0, 0, nullptr, 0};
   return pointwise_f32_launch("odet_pointwise_f32", x, w, bias, y, batch, H, W, stride, cin, cout, relu, e, (hipStream_t)stream);
 }
 
 extern "C" int odet_lateral_merge_f32(const void* x, const void* w, const void* bias, const void* top, int th, int tw, void* y,
                                       int batch, int H, int W, int cin, int cout, odet_stream_t stream) {
   ODET_REQUIRE(top, "odet_lateral_merge_f32: null pointer");
-  const PwF32Epilogue e{nullptr, top, th, tw, nullptr, 0};
+  const ConvF32PwEpilogue e{nullptr, top, th, tw, nullptr, 0};
   return pointwise_f32_launch("odet_lateral_merge_f32", x, w, bias, y, batch, H, W, 1, cin, cout, 0, e, (hipStream_t)stream);
 }
 
@@ -424,7 +346,7 @@ extern "C" int odet_pointwise_dual_f32(const void* x1, int cin1, const void* x2,
                                        const void* w, const void* bias, void* y, int batch, int cout, int relu,
                                        odet_stream_t stream) {
   ODET_REQUIRE(x2, "odet_pointwise_dual_f32: null pointer");
-  const PwF32Epilogue e{nullptr, nullptr, 0, 0, x2, cin2};
+  const ConvF32PwEpilogue e{nullptr, nullptr, 0, 0, x2, cin2};
   return pointwise_f32_launch("odet_pointwise_dual_f32", x1, w, bias, y, batch, H2, W2, stride2, cin1, cout, relu, e,
                               (hipStream_t)stream);
 }

@@ -51,7 +51,7 @@ typedef unsigned int x3u2 __attribute__((ext_vector_type(2)));
 typedef __amdgpu_buffer_rsrc_t x3_rsrc_t;
 typedef __attribute__((address_space(3))) void* x3_lds_ptr;
 
-#define X3_BK 32                  // float32 input channels per K-step (128 bytes of a pixel's row; 64 bytes per limb)
+#define X3_BK CONV_F32_BK         // float32 input channels per K-step (128 bytes of a pixel's row; 64 bytes per limb)
 #define X3_LDS_MAX (160 * 1024)
 // K-steps the pixel slots are loaded ahead of their use, as a function of the LDS stages (register buffers; measured NS + 1 and
 // NS + 2 on both forms: no gain -- what the slot path costs is its instructions, not its latency)
@@ -513,27 +513,18 @@ __global__ void __launch_bounds__(512) k_pointwise_x2(ConvF32Params p) {
 #define X3_FOR_TILES(F) F(4, 2) F(2, 2) F(4, 4) F(2, 1) F(1, 1)
 #define X2_FOR_TILES(F) F(2, 2) F(4, 4) F(2, 1) F(1, 1)
 
-template <typename F>
-static void x3_for_each_kernel(F f) {
-#define X3_K(MT_, WN_) f((const void*)k_conv3x3_x3<MT_, WN_>); f((const void*)k_pointwise_x3<MT_, WN_>);
-#define X2_K(MT_, WN_) f((const void*)k_conv3x3_x2<MT_, WN_>); f((const void*)k_pointwise_x2<MT_, WN_>);
-  X3_FOR_TILES(X3_K)
-  X2_FOR_TILES(X2_K)
-#undef X3_K
-#undef X2_K
-}
+// the split forms' values of the checks the forms differ on (inherited, not designed: conv_f32_common.h)
+static const ConvF32Rules X3_RULES = {6ull, 1ll << 28, true};
 
 static hipError_t x3_prepare_kernels() {
+#define X3_K(MT_, WN_) (const void*)k_conv3x3_x3<MT_, WN_>, (const void*)k_pointwise_x3<MT_, WN_>,
+#define X2_K(MT_, WN_) (const void*)k_conv3x3_x2<MT_, WN_>, (const void*)k_pointwise_x2<MT_, WN_>,
+  static const void* const kernels[] = {X3_FOR_TILES(X3_K) X2_FOR_TILES(X2_K)};
+#undef X3_K
+#undef X2_K
   static OdetPerDeviceOnce once;
-  return once.run([] {
-    hipError_t rc = hipSuccess;
-    x3_for_each_kernel([&rc](const void* k) {
-      // (the largest tile's two stages are 144 KB; the kernels also hold a few bytes of static LDS: the split-K flag)
-      const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024);
-      if (e != hipSuccess) rc = e;
-    });
-    return rc;
-  });
+  // (the largest tile's two stages are 144 KB; the kernels also hold a few bytes of static LDS: the split-K flag)
+  return conv_f32_raise_lds_limit(&once, kernels, sizeof(kernels) / sizeof(kernels[0]), 152 * 1024);
 }
 
 static unsigned x3_lds_bytes(int tm, int tn, int nl) { return (unsigned)((nl == 2 ? 3 : 2) * nl * (tm + tn) * 64); }
@@ -645,12 +636,6 @@ static int x3_launch_tile(int nl, int wn, int mt, dim3 grid, unsigned lds_bytes,
   return odet_set_error(ODET_E_INVALID, "conv_x3: no kernel for the tile (mt %d, wn %d)", mt, wn);
 }
 
-static void x3_defaults(ConvF32Params* p) {
-  p->stride = 1; p->Ho = p->Wo = 0; p->Min = 0; p->res = nullptr; p->top = nullptr; p->th = p->tw = 0; p->tys = p->txs = 0.0f;
-  p->x2 = nullptr; p->cin2 = 0; p->k1steps = 0; p->Min2 = 0;
-  p->ksplit = 0; p->part = nullptr; p->ticket = nullptr; p->acc_scale = 1.0f; p->status = nullptr;
-}
-
 // the limb form of a launch: 3 bfloat16 planes, or 2 float16 planes of w * 2^w_exp
 struct X3Form { int nl, w_exp; };
 static bool x3_form_ok(const X3Form& f) { return f.nl == 3 || (f.nl == 2 && f.w_exp >= -100 && f.w_exp <= 100); }
@@ -658,51 +643,33 @@ static unsigned* x3_status_word(const X3Form& form, void* ws, size_t ws_bytes) {
   return (form.nl == 2 && ws && ws_bytes >= X3_HEAD_BYTES && (uintptr_t)ws % 16 == 0) ? (unsigned*)((char*)ws + (size_t)X3_TICKETS * 4) : nullptr;
 }
 
-static int conv3x3_x3_launch(const X3Form& form, const odet_conv_level_t* levels, int num_levels, const void* w3, const void* bias,
-                             int batch, int cin, int cout, int relu, void* ws, size_t ws_bytes, hipStream_t st) {
-  ODET_REQUIRE(levels && w3, "odet_conv3x3_x3: null pointer");
-  ODET_REQUIRE(x3_form_ok(form), "odet_conv3x3_x2: w_exp %d out of range", form.w_exp);
-  ODET_REQUIRE(num_levels >= 1 && num_levels <= ODET_MAX_LEVELS, "odet_conv3x3_x3: num_levels %d out of range", num_levels);
-  ODET_REQUIRE(batch > 0, "odet_conv3x3_x3: bad batch");
-  ODET_REQUIRE(cin > 0 && cin % X3_BK == 0, "odet_conv3x3_x3: cin %d must be a multiple of %d", cin, X3_BK);
-  ODET_REQUIRE(cout > 0 && cout % 64 == 0, "odet_conv3x3_x3: cout %d must be a multiple of 64", cout);
-  ODET_REQUIRE((unsigned long long)cout * 9ull * cin * 6ull < 0x7FFFFFFFull, "odet_conv3x3_x3: weights too large");
-  ODET_REQUIRE((uintptr_t)w3 % 16 == 0 && (uintptr_t)bias % 16 == 0, "odet_conv3x3_x3: pointers must be 16-byte aligned");
+// a filled plan -> the kernels' LDS limit, the tile and the K split, the plan's tile-dependent rest, the form's extras, the launch
+template <bool PW>
+static int x3_launch(const char* who, const X3Form& form, ConvF32Params* p, void* ws, size_t ws_bytes, hipStream_t st) {
   ODET_HIP(x3_prepare_kernels());
-  ConvF32Params p;
-  x3_defaults(&p);
-  for (int l = 0; l < ODET_MAX_LEVELS; ++l) {
-    const odet_conv_level_t& L = levels[l < num_levels ? l : 0];
-    ODET_REQUIRE(L.x && L.y && L.H > 0 && L.W > 0, "odet_conv3x3_x3: bad level %d", l);
-    ODET_REQUIRE(((uintptr_t)L.x | (uintptr_t)L.y) % 16 == 0, "odet_conv3x3_x3: maps must be 16-byte aligned");
-    const long long M = (long long)batch * L.H * L.W;
-    ODET_REQUIRE((unsigned long long)M * cin * 4ull + 2ull * (L.W + 1) * cin * 4ull < 0xFFFFFFF0ull,
-                 "odet_conv3x3_x3: level %d input larger than 4 GiB", l);
-    p.x[l] = (const float*)L.x; p.y[l] = (float*)L.y; p.M[l] = M; p.H[l] = L.H; p.W[l] = L.W;
-  }
-  const X3Pick pick = x3_pick_tile(p.M, num_levels, cout, 9 * (cin / X3_BK), x3_part_bytes(ws, ws_bytes), form.nl);
-  p.acc_scale = form.nl == 2 ? ldexpf(1.0f, -form.w_exp) : 1.0f;
-  p.status = x3_status_word(form, ws, ws_bytes);
-  const int wn = pick.wn, mt = pick.mt;
-  const int TMsel = x3_tile_pixels(mt, wn);
-  long long total = 0;
-  for (int l = 0; l < ODET_MAX_LEVELS; ++l) {
-    p.tile_start[l] = total;
-    if (l < num_levels) total += (p.M[l] + TMsel - 1) / TMsel;
-  }
-  for (int l = num_levels; l <= ODET_MAX_LEVELS; ++l) p.tile_start[l] = total;
-  p.w = (const float*)w3; p.bias = (const float*)bias;
-  p.num_levels = num_levels; p.cin = cin; p.cout = cout; p.relu = relu ? 1 : 0;
-  p.tiles_n = cout / (64 * wn);
-  const long long blocks = (total + 7) / 8 * 8 * p.tiles_n;
-  ODET_REQUIRE(blocks < (1ll << 28), "odet_conv3x3_x3: too many workgroups");
-  const int rs = x3_apply_split(&p, pick, blocks, TMsel, ws, ws_bytes, "odet_conv3x3_x3");
+  const int ksteps = ((PW ? 1 : 9) * p->cin + p->cin2) / X3_BK;
+  const X3Pick pick = x3_pick_tile(p->M, p->num_levels, p->cout, ksteps, x3_part_bytes(ws, ws_bytes), form.nl);
+  const int TMsel = x3_tile_pixels(pick.mt, pick.wn);
+  long long blocks;
+  const int rt = conv_f32_plan_tiles(who, X3_RULES, TMsel, pick.wn, p, &blocks);
+  if (rt != ODET_OK) return rt;
+  p->acc_scale = form.nl == 2 ? ldexpf(1.0f, -form.w_exp) : 1.0f;
+  p->status = x3_status_word(form, ws, ws_bytes);
+  const int rs = x3_apply_split(p, pick, blocks, TMsel, ws, ws_bytes, who);
   if (rs != ODET_OK) return rs;
-  const int rc = x3_launch_tile<false>(form.nl, wn, mt, dim3((unsigned)(blocks * (p.ksplit > 1 ? p.ksplit : 1))),
-                                       x3_lds_bytes(TMsel, 64 * wn, form.nl), st, p);
+  const int rc = x3_launch_tile<PW>(form.nl, pick.wn, pick.mt, dim3((unsigned)(blocks * (p->ksplit > 1 ? p->ksplit : 1))),
+                                    x3_lds_bytes(TMsel, 64 * pick.wn, form.nl), st, *p);
   if (rc != ODET_OK) return rc;
   ODET_LAUNCH_CHECK();
   return ODET_OK;
+}
+
+static int conv3x3_x3_launch(const char* who, const X3Form& form, const odet_conv_level_t* levels, int num_levels, const void* w3,
+                             const void* bias, int batch, int cin, int cout, int relu, void* ws, size_t ws_bytes, hipStream_t st) {
+  ODET_REQUIRE(x3_form_ok(form), "%s: w_exp %d out of range", who, form.w_exp);
+  ConvF32Params p;
+  const int rp = conv_f32_plan_levels(who, X3_RULES, levels, num_levels, w3, bias, batch, cin, cout, relu, &p);
+  return rp != ODET_OK ? rp : x3_launch<false>(who, form, &p, ws, ws_bytes, st);
 }
 
 extern "C" size_t odet_x3_workspace_bytes(void) { return X3_HEAD_BYTES + ((size_t)64 << 20); }
@@ -712,89 +679,47 @@ extern "C" int odet_conv3x3_x3(const void* x, const void* w3, const void* bias, 
                                int cout, int relu, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
   ODET_REQUIRE(x && y, "odet_conv3x3_x3: null pointer");
   const odet_conv_level_t one{x, y, H, W};
-  return conv3x3_x3_launch(X3Form{3, 0}, &one, 1, w3, bias, batch, cin, cout, relu, workspace, workspace_bytes, (hipStream_t)stream);
+  return conv3x3_x3_launch("odet_conv3x3_x3", X3Form{3, 0}, &one, 1, w3, bias, batch, cin, cout, relu, workspace, workspace_bytes,
+                           (hipStream_t)stream);
 }
 
 extern "C" int odet_conv3x3_x2(const void* x, const void* w2, const void* bias, void* y, int batch, int H, int W, int cin,
                                int cout, int relu, int w_exp, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
   ODET_REQUIRE(x && y, "odet_conv3x3_x2: null pointer");
   const odet_conv_level_t one{x, y, H, W};
-  return conv3x3_x3_launch(X3Form{2, w_exp}, &one, 1, w2, bias, batch, cin, cout, relu, workspace, workspace_bytes, (hipStream_t)stream);
+  return conv3x3_x3_launch("odet_conv3x3_x2", X3Form{2, w_exp}, &one, 1, w2, bias, batch, cin, cout, relu, workspace, workspace_bytes,
+                           (hipStream_t)stream);
 }
 
 extern "C" int odet_conv3x3_x2_levels(const odet_conv_level_t* levels, int num_levels, const void* w2, const void* bias,
                                       int batch, int cin, int cout, int relu, int w_exp, void* workspace, size_t workspace_bytes,
                                       odet_stream_t stream) {
-  return conv3x3_x3_launch(X3Form{2, w_exp}, levels, num_levels, w2, bias, batch, cin, cout, relu, workspace, workspace_bytes,
-                           (hipStream_t)stream);
+  return conv3x3_x3_launch("odet_conv3x3_x2_levels", X3Form{2, w_exp}, levels, num_levels, w2, bias, batch, cin, cout, relu, workspace,
+                           workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int odet_conv3x3_x3_levels(const odet_conv_level_t* levels, int num_levels, const void* w3, const void* bias,
                                       int batch, int cin, int cout, int relu, void* workspace, size_t workspace_bytes,
                                       odet_stream_t stream) {
-  return conv3x3_x3_launch(X3Form{3, 0}, levels, num_levels, w3, bias, batch, cin, cout, relu, workspace, workspace_bytes,
-                           (hipStream_t)stream);
+  return conv3x3_x3_launch("odet_conv3x3_x3_levels", X3Form{3, 0}, levels, num_levels, w3, bias, batch, cin, cout, relu, workspace,
+                           workspace_bytes, (hipStream_t)stream);
 }
 
-struct PwX3Epilogue { const void* res; const void* top; int th, tw; const void* x2; int cin2; };
-
 static int pointwise_x3_launch(const char* who, const X3Form& form, const void* x, const void* w3, const void* bias, void* y,
-                               int batch, int H, int W, int stride, int cin, int cout, int relu, const PwX3Epilogue& epi, void* ws,
-                               size_t ws_bytes, hipStream_t st) {
-  ODET_REQUIRE(x && w3 && y, "%s: null pointer", who);
+                               int batch, int H, int W, int stride, int cin, int cout, int relu, const ConvF32PwEpilogue& epi,
+                               void* ws, size_t ws_bytes, hipStream_t st) {
   ODET_REQUIRE(x3_form_ok(form), "%s: w_exp %d out of range", who, form.w_exp);
-  ODET_REQUIRE(batch > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2), "%s: bad shape", who);
+  // inherited, not designed: the split forms ask for a positive cin, the exact form for two K-steps along K over both sources
   ODET_REQUIRE(cin % X3_BK == 0 && cin > 0, "%s: cin %d must be a positive multiple of %d", who, cin, X3_BK);
-  ODET_REQUIRE(cout > 0 && cout % 64 == 0, "%s: cout %d must be a multiple of 64", who, cout);
-  ODET_REQUIRE(((uintptr_t)x | (uintptr_t)w3 | (uintptr_t)y | (uintptr_t)bias | (uintptr_t)epi.res | (uintptr_t)epi.top |
-                (uintptr_t)epi.x2) % 16 == 0, "%s: pointers must be 16-byte aligned", who);
-  ODET_REQUIRE(!(epi.res && epi.top), "%s: shortcut and top-down merge exclude each other", who);
-  ODET_REQUIRE(!epi.top || (stride == 1 && epi.th > 0 && epi.tw > 0 && !relu), "%s: bad merge arguments", who);
-  ODET_HIP(x3_prepare_kernels());
-  const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
-  const long long M = (long long)batch * Ho * Wo;
-  const long long Min = epi.x2 ? M : (long long)batch * H * W;
-  ODET_REQUIRE((unsigned long long)Min * cin * 4ull < 0xFFFFFFF0ull, "%s: input larger than 4 GiB", who);
-  ODET_REQUIRE(!epi.x2 || (epi.cin2 > 0 && epi.cin2 % X3_BK == 0 &&
-                           (unsigned long long)batch * H * W * epi.cin2 * 4ull < 0xFFFFFFF0ull), "%s: bad second source", who);
-  ODET_REQUIRE((unsigned long long)cout * (cin + (epi.x2 ? epi.cin2 : 0)) * 6ull < 0x7FFFFFFFull, "%s: weights too large", who);
   ConvF32Params p;
-  x3_defaults(&p);
-  for (int l = 0; l < ODET_MAX_LEVELS; ++l) {
-    p.x[l] = (const float*)x; p.y[l] = (float*)y; p.M[l] = M; p.H[l] = H; p.W[l] = W;
-  }
-  p.res = (const float*)epi.res;
-  p.top = (const float*)epi.top; p.th = epi.th; p.tw = epi.tw;
-  p.tys = epi.top ? (float)epi.th / (float)Ho : 0.0f;
-  p.txs = epi.top ? (float)epi.tw / (float)Wo : 0.0f;
-  p.stride = stride; p.Ho = Ho; p.Wo = Wo; p.Min = Min;
-  p.x2 = (const float*)epi.x2; p.cin2 = epi.x2 ? epi.cin2 : 0; p.k1steps = cin / X3_BK; p.Min2 = (long long)batch * H * W;
-  const X3Pick pick = x3_pick_tile(&M, 1, cout, (cin + (epi.x2 ? epi.cin2 : 0)) / X3_BK, x3_part_bytes(ws, ws_bytes), form.nl);
-  p.acc_scale = form.nl == 2 ? ldexpf(1.0f, -form.w_exp) : 1.0f;
-  p.status = x3_status_word(form, ws, ws_bytes);
-  const int wn = pick.wn, mt = pick.mt;
-  const int TMsel = x3_tile_pixels(mt, wn);
-  p.tiles_n = cout / (64 * wn);
-  const long long total = (M + TMsel - 1) / TMsel;
-  p.tile_start[0] = 0;
-  for (int l = 1; l <= ODET_MAX_LEVELS; ++l) p.tile_start[l] = total;
-  p.w = (const float*)w3; p.bias = (const float*)bias;
-  p.num_levels = 1; p.cin = cin; p.cout = cout; p.relu = relu ? 1 : 0;
-  const long long blocks = (total + 7) / 8 * 8 * p.tiles_n;
-  ODET_REQUIRE(blocks < (1ll << 28), "%s: too many workgroups", who);
-  const int rs = x3_apply_split(&p, pick, blocks, TMsel, ws, ws_bytes, who);
-  if (rs != ODET_OK) return rs;
-  const int rc = x3_launch_tile<true>(form.nl, wn, mt, dim3((unsigned)(blocks * (p.ksplit > 1 ? p.ksplit : 1))),
-                                      x3_lds_bytes(TMsel, 64 * wn, form.nl), st, p);
-  if (rc != ODET_OK) return rc;
-  ODET_LAUNCH_CHECK();
-  return ODET_OK;
+  const int rp = conv_f32_plan_pointwise(who, X3_RULES, x, w3, bias, y, batch, H, W, stride, cin, cout, relu, epi, &p);
+  return rp != ODET_OK ? rp : x3_launch<true>(who, form, &p, ws, ws_bytes, st);
 }
 
 extern "C" int odet_pointwise_x3(const void* x, const void* w3, const void* bias, const void* residual, void* y, int batch,
                                  int H, int W, int stride, int cin, int cout, int relu, void* workspace, size_t workspace_bytes,
                                  odet_stream_t stream) {
-  const PwX3Epilogue e{residual, nullptr, 0, 0, nullptr, 0};
+  const ConvF32PwEpilogue e{residual, nullptr, 0, 0, nullptr, 0};
   return pointwise_x3_launch("odet_pointwise_x3", X3Form{3, 0}, x, w3, bias, y, batch, H, W, stride, cin, cout, relu, e, workspace,
                              workspace_bytes, (hipStream_t)stream);
 }
@@ -803,7 +728,7 @@ extern "C" int odet_lateral_merge_x3(const void* x, const void* w3, const void* 
                                      int batch, int H, int W, int cin, int cout, void* workspace, size_t workspace_bytes,
                                      odet_stream_t stream) {
   ODET_REQUIRE(top, "odet_lateral_merge_x3: null pointer");
-  const PwX3Epilogue e{nullptr, top, th, tw, nullptr, 0};
+  const ConvF32PwEpilogue e{nullptr, top, th, tw, nullptr, 0};
   return pointwise_x3_launch("odet_lateral_merge_x3", X3Form{3, 0}, x, w3, bias, y, batch, H, W, 1, cin, cout, 0, e, workspace,
                              workspace_bytes, (hipStream_t)stream);
 }
@@ -812,7 +737,7 @@ extern "C" int odet_pointwise_dual_x3(const void* x1, int cin1, const void* x2, 
                                       const void* w3, const void* bias, void* y, int batch, int cout, int relu,
                                       void* workspace, size_t workspace_bytes, odet_stream_t stream) {
   ODET_REQUIRE(x2, "odet_pointwise_dual_x3: null pointer");
-  const PwX3Epilogue e{nullptr, nullptr, 0, 0, x2, cin2};
+  const ConvF32PwEpilogue e{nullptr, nullptr, 0, 0, x2, cin2};
   return pointwise_x3_launch("odet_pointwise_dual_x3", X3Form{3, 0}, x1, w3, bias, y, batch, H2, W2, stride2, cin1, cout, relu, e,
                              workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -821,7 +746,7 @@ extern "C" int odet_pointwise_dual_x3(const void* x1, int cin1, const void* x2, 
 extern "C" int odet_pointwise_x2(const void* x, const void* w2, const void* bias, const void* residual, void* y, int batch,
                                  int H, int W, int stride, int cin, int cout, int relu, int w_exp, void* workspace,
                                  size_t workspace_bytes, odet_stream_t stream) {
-  const PwX3Epilogue e{residual, nullptr, 0, 0, nullptr, 0};
+  const ConvF32PwEpilogue e{residual, nullptr, 0, 0, nullptr, 0};
   return pointwise_x3_launch("odet_pointwise_x2", X3Form{2, w_exp}, x, w2, bias, y, batch, H, W, stride, cin, cout, relu, e,
                              workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -830,7 +755,7 @@ extern "C" int odet_lateral_merge_x2(const void* x, const void* w2, const void* 
                                      int batch, int H, int W, int cin, int cout, int w_exp, void* workspace, size_t workspace_bytes,
                                      odet_stream_t stream) {
   ODET_REQUIRE(top, "odet_lateral_merge_x2: null pointer");
-  const PwX3Epilogue e{nullptr, top, th, tw, nullptr, 0};
+  const ConvF32PwEpilogue e{nullptr, top, th, tw, nullptr, 0};
   return pointwise_x3_launch("odet_lateral_merge_x2", X3Form{2, w_exp}, x, w2, bias, y, batch, H, W, 1, cin, cout, 0, e, workspace,
                              workspace_bytes, (hipStream_t)stream);
 }
@@ -839,7 +764,7 @@ extern "C" int odet_pointwise_dual_x2(const void* x1, int cin1, const void* x2, 
                                       const void* w2, const void* bias, void* y, int batch, int cout, int relu, int w_exp,
                                       void* workspace, size_t workspace_bytes, odet_stream_t stream) {
   ODET_REQUIRE(x2, "odet_pointwise_dual_x2: null pointer");
-  const PwX3Epilogue e{nullptr, nullptr, 0, 0, x2, cin2};
+  const ConvF32PwEpilogue e{nullptr, nullptr, 0, 0, x2, cin2};
   return pointwise_x3_launch("odet_pointwise_dual_x2", X3Form{2, w_exp}, x1, w2, bias, y, batch, H2, W2, stride2, cin1, cout, relu,
                              e, workspace, workspace_bytes, (hipStream_t)stream);
 }

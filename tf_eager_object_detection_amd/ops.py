@@ -104,27 +104,18 @@ def _plane_key(w):
         return None
 
 
-def _x3_planes(holder, w):
-    """the limb planes of the (contiguous, float32) weight `w`, kept ON the tensor object the caller passed (`holder`: the
-    layer's parameter, or a module's cached concatenation) until that tensor is modified: the planes live exactly as long as
-    the weight they belong to -- no global cache that could outlive or be cleared under a captured HIP graph.  A caller that
-    passes a fresh temporary every time pays the split every time (correct, slow): keep weights in stable tensors."""
+def _limb_planes(holder, w, attr, split):
+    """the limb planes `split(w)` of the (contiguous, float32) weight `w`, kept ON the tensor object the caller passed (`holder`:
+    the layer's parameter, or a module's cached concatenation) under `attr` until that tensor is modified: the planes live exactly
+    as long as the weight they belong to -- no global cache that could outlive or be cleared under a captured HIP graph.  A caller
+    that passes a fresh temporary every time pays the split every time (correct, slow): keep weights in stable tensors.
+    (split_f16x2 reads its exponent from the weights -- one host synchronisation per weight tensor, at its first use: a warm-up
+    pass before a HIP-graph capture, as for the workspace)"""
     key = _plane_key(w)
-    hit = holder.__dict__.get('_odet_x3') if key is not None else None
+    hit = holder.__dict__.get(attr) if key is not None else None
     if hit is None or hit[0] != key:
-        hit = (key, split_bf16x3(w), w)
-        holder.__dict__['_odet_x3'] = hit
-    return hit[1]
-
-
-def _x2_planes(holder, w):
-    """the same for the two-limb form: (planes, w_exp) (the exponent is read from the weights -- one host synchronisation per
-    weight tensor, at its first use: a warm-up pass before a HIP-graph capture, as for the workspace)"""
-    key = _plane_key(w)
-    hit = holder.__dict__.get('_odet_x2') if key is not None else None
-    if hit is None or hit[0] != key:
-        hit = (key, split_f16x2(w), w)
-        holder.__dict__['_odet_x2'] = hit
+        hit = (key, split(w), w)
+        holder.__dict__[attr] = hit
     return hit[1]
 
 
@@ -197,27 +188,45 @@ def invalidate_planes(module_or_tensor):
         t.__dict__.pop('_odet_x2', None)
 
 
-def _f32_sym(sym, w, holder=None):
-    """(entry point, weight pointer, extra arguments before the stream) of a float32 layer in the current form; `holder` = the
-    caller's weight tensor object"""
+# form -> entry-point suffix, the attribute a weight's limb planes are cached under, their splitter, and how the cached value reads
+# as (planes, extra arguments ahead of the workspace's)
+_F32_FORMS = {
+    'exact': ('f32', None, None, None),
+    'x3': ('x3', '_odet_x3', split_bf16x3, lambda planes: (planes, ())),
+    'x2': ('x2', '_odet_x2', split_f16x2, lambda planes_exp: (planes_exp[0], (planes_exp[1],))),
+}
+
+
+def _f32_sym(pattern, w, holder=None):
+    """(form, entry point, weight pointer, extra arguments before the stream) of a float32 layer in the current form: `pattern` %
+    the form's suffix; `holder` = the caller's weight tensor object"""
     form = _F32_CTX.get()[0]
-    if form == 'x3':
-        planes = _x3_planes(w if holder is None else holder, w)
-        return sym[:-3] + 'x3', C.c_void_p(planes.data_ptr()), _x3_workspace(w.device).args()   # odet_*_f32 -> odet_*_x3
-    if form == 'x2':
-        planes, w_exp = _x2_planes(w if holder is None else holder, w)
-        return sym[:-3] + 'x2', C.c_void_p(planes.data_ptr()), (w_exp,) + _x3_workspace(w.device).args()
-    return sym, L.dptr(w), ()
+    sfx, attr, split, read = _F32_FORMS[form]
+    if attr is None:
+        return form, pattern % sfx, L.dptr(w), ()
+    planes, extra = read(_limb_planes(w if holder is None else holder, w, attr, split))
+    return form, pattern % sfx, C.c_void_p(planes.data_ptr()), extra + _x3_workspace(w.device).args()
 
 
-def _f32_call(sym, *args):
-    """L.call for a float32 layer; a split-precision launch that FAILS may leave its workspace's tickets non-zero: reset them"""
+def _f32_call(form, sym, *args):
+    """L.call for a dense layer (`form`: None for float16); a split-precision launch that FAILS may leave its workspace's tickets
+    non-zero: reset them"""
     try:
         L.call(sym, *args)
     except L.OdetError:
-        if sym.endswith(('_x3', '_x2', '_x3_levels', '_x2_levels')):
+        if form in ('x3', 'x2'):
             _x3_workspace(torch.device('cuda', torch.cuda.current_device())).reset()
         raise
+
+
+def _out(out, shape, dtype, device):
+    """the result tensor of a launch: a fresh one, or the caller's `out` when it is a contiguous `dtype` tensor of `shape`"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if out.dtype != dtype or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError('out must be a contiguous %s tensor of shape %s, got %s %s'
+                         % (dtype, tuple(shape), out.dtype, tuple(out.shape)))
+    return out
 
 
 def _boxes(t, name):
@@ -646,14 +655,11 @@ def _conv3x3(dtype, x, weight, bias, relu, out):
     if bias is not None and (bias.dtype != dtype or bias.numel() != cout or not bias.is_contiguous()):
         raise ValueError('bias must be a contiguous %s [cout] tensor' % name)
     shape = (B, H, W, cout)
-    if out is None:
-        out = torch.empty(shape, dtype=dtype, device=x.device)
-    elif out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError('out must be a contiguous %s tensor [B,H,W,cout]' % name)
-    wp, extra = L.dptr(w), ()
+    out = _out(out, shape, dtype, x.device)
+    form, wp, extra = None, L.dptr(w), ()
     if dtype == torch.float32:
-        sym, wp, extra = _f32_sym(sym, w, weight)
-    _f32_call(sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None, L.dptr(out), B, H, W,
+        form, sym, wp, extra = _f32_sym('odet_conv3x3_%s', w, weight)
+    _f32_call(form, sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None, L.dptr(out), B, H, W,
            cin, cout, 1 if relu else 0, *extra, L.stream())
     return out
 
@@ -677,10 +683,10 @@ def _conv3x3_levels(dtype, xs, weight, bias, relu, outs):
         if y.dtype != dtype or tuple(y.shape) != tuple(x.shape[:3]) + (cout,) or not y.is_contiguous():
             raise ValueError('outs must be contiguous %s tensors [B,H,W,cout]' % name)
         lv[i].x, lv[i].y, lv[i].H, lv[i].W = x.data_ptr(), y.data_ptr(), int(x.shape[1]), int(x.shape[2])
-    wp, extra = L.dptr(w), ()
+    form, sym, wp, extra = None, sym + '_levels', L.dptr(w), ()
     if dtype == torch.float32:
-        sym, wp, extra = _f32_sym(sym, w, weight)
-    _f32_call(sym + '_levels', lv, len(xs), wp, L.dptr(bias) if bias is not None else None, B, cin, cout,
+        form, sym, wp, extra = _f32_sym('odet_conv3x3_%s_levels', w, weight)
+    _f32_call(form, sym, lv, len(xs), wp, L.dptr(bias) if bias is not None else None, B, cin, cout,
            1 if relu else 0, *extra, L.stream())
     return outs
 
@@ -706,10 +712,7 @@ def conv3x3_relu_pool2_f16(x, weight, bias, out=None):
     if bias is None or bias.dtype != torch.float16 or bias.numel() != cout or not bias.is_contiguous():
         raise ValueError('bias must be a contiguous float16 [cout] tensor')
     shape = (B, (H + 1) // 2, (W + 1) // 2, cout)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float16, device=x.device)
-    elif out.dtype != torch.float16 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError('out must be a contiguous float16 tensor %s' % (shape,))
+    out = _out(out, shape, torch.float16, x.device)
     L.call('odet_conv3x3_relu_pool2_f16', L.dptr(x), L.dptr(w), L.dptr(bias), L.dptr(out), B, H, W, cin, cout, L.stream())
     return out
 
@@ -780,10 +783,7 @@ def conv3x3_conv1x1_f16(x, weight2, bias2, weight3, bias3, residual=None, relu=T
     shape = (B, H, W, n3)
     if residual is not None and (residual.dtype != torch.float16 or tuple(residual.shape) != shape or not residual.is_contiguous()):
         raise ValueError('residual must be a contiguous float16 tensor [B,H,W,n3]')
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float16, device=x.device)
-    elif out.dtype != torch.float16 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError('out must be a contiguous float16 tensor [B,H,W,n3]')
+    out = _out(out, shape, torch.float16, x.device)
     L.call('odet_bottleneck_tail_f16', L.dptr(x), L.dptr(w2), L.dptr(bias2), L.dptr(w3), L.dptr(bias3),
            L.dptr(residual) if residual is not None else None, L.dptr(out), B, H, W, cin, cmid, n3, 1 if relu else 0,
            L.stream())
@@ -813,10 +813,7 @@ def stem_conv7_pool3(images_nhwc, packed_weight, bias, out=None):
     B, H, W = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
     ch, cw = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     shape = (B, (ch - 1) // 2 + 1, (cw - 1) // 2 + 1, 64)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float16, device=x.device)
-    elif out.dtype != torch.float16 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError('out must be a contiguous float16 tensor %s' % (shape,))
+    out = _out(out, shape, torch.float16, x.device)
     L.call('odet_stem_conv7_pool3_f16', L.dptr(x), 1 if x.dtype == torch.float16 else 0, L.dptr(packed_weight), L.dptr(bias),
            L.dptr(out), B, H, W, L.stream())
     return out
@@ -845,10 +842,7 @@ def conv3x3_rgb(images_nhwc, packed_weight, bias, relu=True, out=None):
         raise ValueError('bias must be a contiguous float16 [64] tensor')
     B, H, W = int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
     shape = (B, H, W, 64)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float16, device=x.device)
-    elif out.dtype != torch.float16 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError('out must be a contiguous float16 tensor %s' % (shape,))
+    out = _out(out, shape, torch.float16, x.device)
     L.call('odet_conv3x3_rgb_f16', L.dptr(x), 1 if x.dtype == torch.float16 else 0, L.dptr(packed_weight), L.dptr(bias),
            L.dptr(out), B, H, W, 1 if relu else 0, L.stream())
     return out
@@ -885,10 +879,7 @@ def conv1x1_f16(x, weight, bias, residual=None, relu=True, out=None, in_bias=Non
     if residual is not None and (residual.dtype != torch.float16 or tuple(residual.shape) != shape
                                  or not residual.is_contiguous()):
         raise ValueError('residual must be a contiguous float16 tensor shaped like the output')
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float16, device=x.device)
-    elif out.dtype != torch.float16 or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError('out must be a contiguous float16 tensor shaped like the output')
+    out = _out(out, shape, torch.float16, x.device)
     if out.data_ptr() == x.data_ptr():
         raise ValueError('out must not alias x')
     if in_bias is not None and (in_bias.dtype != torch.float16 or in_bias.numel() != cin or not in_bias.is_contiguous()):
@@ -934,12 +925,9 @@ def pointwise(x, weight, bias=None, residual=None, relu=False, stride=1, out=Non
     shape = (B, (H + stride - 1) // stride, (W + stride - 1) // stride, cout)
     if residual is not None and (residual.dtype != x.dtype or tuple(residual.shape) != shape or not residual.is_contiguous()):
         raise ValueError('residual must be a contiguous tensor of the output\'s dtype and shape %s' % (shape,))
-    if out is None:
-        out = torch.empty(shape, dtype=x.dtype, device=x.device)
-    elif out.dtype != x.dtype or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError('out must be a contiguous tensor %s of x\'s dtype' % (shape,))
-    sym, wp, extra = ('odet_pointwise_' + sfx, L.dptr(w), ()) if sfx != 'f32' else _f32_sym('odet_pointwise_f32', w, weight)
-    _f32_call(sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None,
+    out = _out(out, shape, x.dtype, x.device)
+    form, sym, wp, extra = _f32_sym('odet_pointwise_%s', w, weight) if sfx == 'f32' else (None, 'odet_pointwise_f16', L.dptr(w), ())
+    _f32_call(form, sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None,
            L.dptr(residual) if residual is not None else None, L.dptr(out), B, H, W, stride, cin, cout, 1 if relu else 0,
            *extra, L.stream())
     return out
@@ -964,12 +952,10 @@ def lateral_merge(x, weight, bias, top, out=None):
             or top.shape[0] != B or top.shape[3] != cout:
         raise ValueError('top must be a contiguous GPU tensor [batch, h, w, cout] of x\'s dtype')
     shape = (B, H, W, cout)
-    if out is None:
-        out = torch.empty(shape, dtype=x.dtype, device=x.device)
-    elif out.dtype != x.dtype or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError('out must be a contiguous tensor %s of x\'s dtype' % (shape,))
-    sym, wp, extra = ('odet_lateral_merge_' + sfx, L.dptr(w), ()) if sfx != 'f32' else _f32_sym('odet_lateral_merge_f32', w, weight)
-    _f32_call(sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None, L.dptr(top),
+    out = _out(out, shape, x.dtype, x.device)
+    form, sym, wp, extra = _f32_sym('odet_lateral_merge_%s', w, weight) if sfx == 'f32' \
+        else (None, 'odet_lateral_merge_f16', L.dptr(w), ())
+    _f32_call(form, sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None, L.dptr(top),
            int(top.shape[1]), int(top.shape[2]), L.dptr(out), B, H, W, cin, cout, *extra, L.stream())
     return out
 
@@ -998,12 +984,10 @@ def pointwise_dual(x1, x2, weight, bias=None, stride=1, relu=True, out=None):
     if c1 % gran or c2 % gran or cout % 64:
         raise ValueError('pointwise_dual: cin1 / cin2 must be multiples of %d, cout of 64' % gran)
     shape = (B, Ho, Wo, cout)
-    if out is None:
-        out = torch.empty(shape, dtype=x1.dtype, device=x1.device)
-    elif out.dtype != x1.dtype or tuple(out.shape) != shape or not out.is_contiguous():
-        raise ValueError('out must be a contiguous tensor %s of x1\'s dtype' % (shape,))
-    sym, wp, extra = ('odet_pointwise_dual_' + sfx, L.dptr(weight), ()) if sfx != 'f32' else _f32_sym('odet_pointwise_dual_f32', weight)
-    _f32_call(sym, L.dptr(x1), c1, L.dptr(x2), c2, H, W, stride, wp,
+    out = _out(out, shape, x1.dtype, x1.device)
+    form, sym, wp, extra = _f32_sym('odet_pointwise_dual_%s', weight) if sfx == 'f32' \
+        else (None, 'odet_pointwise_dual_f16', L.dptr(weight), ())
+    _f32_call(form, sym, L.dptr(x1), c1, L.dptr(x2), c2, H, W, stride, wp,
            L.dptr(bias) if bias is not None else None, L.dptr(out), B, cout, 1 if relu else 0, *extra, L.stream())
     return out
 
@@ -1047,10 +1031,7 @@ def dense_f16_out_f32(x, weight, bias=None, relu=False, out=None):
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != cout or not bias.is_contiguous()):
         raise ValueError('dense_f16_out_f32: bias must be a contiguous float32 [cout] tensor')
     rows = int(x.shape[0])
-    if out is None:
-        out = torch.empty((rows, cout), dtype=torch.float32, device=x.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != (rows, cout) or not out.is_contiguous():
-        raise ValueError('out must be a contiguous float32 tensor [rows, cout]')
+    out = _out(out, (rows, cout), torch.float32, x.device)
     L.call('odet_dense_f16_out_f32', L.dptr(x), L.dptr(w), L.dptr(bias) if bias is not None else None, L.dptr(out), rows,
            cin, cout, 1 if relu else 0, L.stream())
     return out
