@@ -21,6 +21,11 @@ int odet_debug_x3_tile(int mt, int wn, int ksplit);
  * the product's compiler flags): n float32 values (n % 8 == 0, device, 16-byte aligned) -> their float16 bits, once through
  * d_cvt8_f16 (out_pk) and once through d_cvt_pk_f16 + d_pack8_f16 (out_pack8); values 2k / 2k + 1 share one packed instruction */
 int odet_debug_cvt_f16(const float* src, void* out_pk, void* out_pack8, long long n, odet_stream_t stream);
+/* every selection key of this process's next odet_anchor_target / odet_proposal_target calls (csrc/targets.hip: key64 of streams
+ * 0 .. 3, the stored high word included) is ANDed with and_mask, so that keys collide and the selection walks the digits of
+ * key64 * 2^20 + i that real Philox keys never reach; tests/targets_np.py takes the same mask.  The with-replacement draw
+ * (stream 4) is not a selection key and is not masked.  ~0 clears. */
+int odet_debug_tg_key_mask(unsigned long long and_mask);
 
 #ifdef __cplusplus
 }

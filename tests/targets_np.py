@@ -34,20 +34,79 @@ def _seed_words(seed):
     return seed & MASK, seed >> 32
 
 
-def key64(stream, image_id, i, seed):
-    """(w0 << 32) | w1 of philox((i, image_id, stream, 0), seed words) for an array of candidate indices i."""
+def key64(stream, image_id, i, seed, key_mask=None):
+    """(w0 << 32) | w1 of philox((i, image_id, stream, 0), seed words) for an array of candidate indices i.  key_mask (None =
+    all ones) is ANDed onto the key: the diagnostic build's odet_debug_tg_key_mask, which makes keys collide."""
     w = philox((np.asarray(i, np.uint64), image_id, stream, 0), _seed_words(seed))
-    return (w[0] << np.uint64(32)) | w[1]
+    return _masked((w[0] << np.uint64(32)) | w[1], key_mask)
 
 
-def select(candidates, k, stream, image_id, seed):
+def _masked(keys, key_mask):
+    return keys if key_mask is None else keys & np.uint64(int(key_mask) & 0xFFFFFFFFFFFFFFFF)
+
+
+def select(candidates, k, stream, image_id, seed, key_mask=None):
     """The k candidates (int array of indices) with the smallest (key64, index) pairs, in ascending pair order."""
     cand = np.asarray(candidates, np.int64)
     if k <= 0:
         return cand[:0]
-    keys = key64(stream, image_id, cand, seed)
+    keys = _masked(key64(stream, image_id, cand, seed), key_mask)          # the mask goes onto the 64-bit key before the sort
     order = np.lexsort((cand, keys))              # last key is the primary one
     return cand[order[:k]]
+
+
+def selection_trace(keys, indices, k):
+    """COVERAGE ACCOUNTING ONLY (never decides whether a kernel output is right: that is select()'s lexsort).  Mirrors the digit
+    walk of d_tg_radix_select over V = key64 * 2^20 + i in seven 12-bit digits, most significant first, for the k-th smallest
+    (key, index) pair of the candidates.  -> dict(levels=[dict(level, occupied, below, count, need)], end, threshold, kth):
+    per level visited the number of occupied bins among the candidates still in play, the candidates in bins below the chosen
+    one, the chosen bin's count and the rows still needed from it (the walk ends where count == need); `end` the level the
+    walk ended on (None: k <= 0 or k >= n, the kernel returns before the walk); `threshold` the (key, index) pair the walk
+    leaves (remaining low bits all ones, the index 0xFFFFFFFF when it ended above the index digits) and `kth` the largest
+    candidate pair not above it."""
+    keys = np.asarray(keys, np.uint64)
+    idx = np.asarray(indices, np.int64)
+    out = dict(levels=[], end=None, threshold=None, kth=None)
+    if k <= 0 or len(keys) <= k:
+        return out
+    play = np.ones(len(keys), bool)
+    pk, pi, need = 0, 0, int(k)
+    for l in range(7):
+        shift = 72 - 12 * l
+        if shift >= 20:
+            d = ((keys >> np.uint64(shift - 20)) & np.uint64(0xFFF)).astype(np.int64)
+        elif l == 5:
+            d = ((keys & np.uint64(0xF)).astype(np.int64) << 8) | ((idx >> 12) & 0xFF)
+        else:
+            d = idx & 0xFFF
+        hist = np.bincount(d[play], minlength=4096)
+        run = np.cumsum(hist)
+        digit = int(np.searchsorted(run, need))                   # the first bin whose inclusive count reaches `need`
+        below, count = int(run[digit] - hist[digit]), int(hist[digit])
+        need -= below
+        out['levels'].append(dict(level=l, occupied=int(np.count_nonzero(hist)), below=below, count=count, need=need))
+        play &= d == digit
+        if shift >= 20:
+            pk |= digit << (shift - 20)
+        elif l == 5:
+            pk |= digit >> 8
+            pi |= (digit & 0xFF) << 12
+        else:
+            pi |= digit
+        if count == need:
+            if shift >= 20:
+                pk |= (1 << (shift - 20)) - 1
+                pi = 0xFFFFFFFF
+            else:
+                pi |= (1 << shift) - 1
+            out['end'] = l
+            break
+    out['threshold'] = (pk, pi)
+    kept = (keys < np.uint64(pk)) | ((keys == np.uint64(pk)) & (idx <= pi))
+    order = np.lexsort((idx[kept], keys[kept]))
+    out['kept'] = int(kept.sum())
+    out['kth'] = (int(keys[kept][order[-1]]), int(idx[kept][order[-1]]))
+    return out
 
 
 def replacement_pick(j, n_bg, image_id, seed):
@@ -56,7 +115,7 @@ def replacement_pick(j, n_bg, image_id, seed):
     return ((w0 * np.uint64(n_bg)) >> np.uint64(32)).astype(np.int64)
 
 
-def anchor_target(gt, image_shape, anchors, pos, neg, total, max_pos, means, stds, seed=0, image_id=0):
+def anchor_target(gt, image_shape, anchors, pos, neg, total, max_pos, means, stds, seed=0, image_id=0, key_mask=None):
     """One image -> dict of every output of odet_anchor_target (dense surface, compact form, parity outputs)."""
     anchors = np.asarray(anchors, np.float32)
     gt = np.asarray(gt, np.float32).reshape(-1, 4)
@@ -72,8 +131,8 @@ def anchor_target(gt, image_shape, anchors, pos, neg, total, max_pos, means, std
     before = -np.ones(n, np.int32); before[idx] = lab
     argmax = -np.ones(n, np.int32); argmax[idx] = am
     fg, bg = np.nonzero(before == 1)[0], np.nonzero(before == 0)[0]
-    kept_fg = np.sort(select(fg, min(len(fg), max_pos), STREAM_ANCHOR_FG, image_id, seed))
-    kept_bg = np.sort(select(bg, min(len(bg), max(total - len(kept_fg), 0)), STREAM_ANCHOR_BG, image_id, seed))
+    kept_fg = np.sort(select(fg, min(len(fg), max_pos), STREAM_ANCHOR_FG, image_id, seed, key_mask))
+    kept_bg = np.sort(select(bg, min(len(bg), max(total - len(kept_fg), 0)), STREAM_ANCHOR_BG, image_id, seed, key_mask))
     labels = -np.ones(n, np.float32)
     labels[kept_fg] = 1
     labels[kept_bg] = 0
@@ -95,8 +154,9 @@ def anchor_target(gt, image_shape, anchors, pos, neg, total, max_pos, means, std
 
 
 def proposal_target(rois, gt, gt_labels, num_classes, pos, neg, total, max_pos, means, stds, reference_row_labels=True,
-                    seed=0, image_id=0):
-    """One image -> dict of every output of odet_proposal_target."""
+                    seed=0, image_id=0, key_mask=None):
+    """One image -> dict of every output of odet_proposal_target (key_mask: the selection keys only, not the with-replacement
+    draw)."""
     rois = np.asarray(rois, np.float32).reshape(-1, 4)
     gt = np.asarray(gt, np.float32).reshape(-1, 4)
     gt_labels = np.asarray(gt_labels, np.int64)
@@ -108,12 +168,12 @@ def proposal_target(rois, gt, gt_labels, num_classes, pos, neg, total, max_pos, 
         fg = np.arange(r) if np.float32(0) >= np.float32(pos) else np.arange(0)
         bg = np.arange(r) if np.float32(neg) <= np.float32(0) < np.float32(pos) else np.arange(0)
     if len(fg) > max_pos:
-        kfg = select(fg, max_pos, STREAM_ROI_FG, image_id, seed)           # ascending (key64, i)
+        kfg = select(fg, max_pos, STREAM_ROI_FG, image_id, seed, key_mask)         # ascending (key64, i)
     else:
         kfg = np.sort(fg)
     want = total - len(kfg)
     if len(bg) > want:
-        kbg = select(bg, want, STREAM_ROI_BG, image_id, seed)
+        kbg = select(bg, want, STREAM_ROI_BG, image_id, seed, key_mask)
     elif len(bg) == want or len(bg) == 0:
         kbg = np.sort(bg)
     else:

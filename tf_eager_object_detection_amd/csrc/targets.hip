@@ -19,7 +19,27 @@ enum { TG_STREAM_ANCHOR_FG = 0, TG_STREAM_ANCHOR_BG = 1, TG_STREAM_ROI_FG = 2, T
 // per-candidate class byte in the workspace
 enum { TG_FG = 1, TG_BG = 0, TG_IGNORE = -1, TG_OUTSIDE = -2 };
 
+#ifdef ODET_DIAG
+// Diagnostic build only (-DODET_DIAG: tools/libodet_hip_diag.so, include/odet_diag.h; the shipped library has neither the entry
+// point nor the field): every SELECTION key (d_key64 and the stored high word of d_key_hi, all four streams) is ANDed with a
+// mask that travels next to the seed, so that tests can make keys collide and walk the deep levels of d_tg_radix_select.
+// The with-replacement draw (stream 4) is no selection key and stays as it is.  ~0 clears.
+#include <atomic>
+struct TgSeed { uint32_t lo, hi; unsigned long long mask; };
+#define TG_KEY_MASK(s, v) ((v) & (s).mask)
+#define TG_KEY_MASK_HI(s, v) ((v) & (uint32_t)((s).mask >> 32))
+static std::atomic<unsigned long long> g_tg_key_mask{~0ull};
+extern "C" int odet_debug_tg_key_mask(unsigned long long and_mask) {
+  g_tg_key_mask.store(and_mask);
+  return ODET_OK;
+}
+#define TG_SEED_DIAG(a) (a).seed.mask = g_tg_key_mask.load()
+#else
 struct TgSeed { uint32_t lo, hi; };
+#define TG_KEY_MASK(s, v) (v)
+#define TG_KEY_MASK_HI(s, v) (v)
+#define TG_SEED_DIAG(a) ((void)0)
+#endif
 struct TgThr { unsigned long long key; uint32_t idx; int32_t none; };   // selected  <=>  !none && (key64, i) <= (key, idx)
 
 // Philox4x32-10 (Salmon et al., SC'11); only the first two output words are used anywhere here.
@@ -38,12 +58,12 @@ __device__ __forceinline__ void d_philox2(uint32_t c0, uint32_t c1, uint32_t c2,
 __device__ __forceinline__ unsigned long long d_key64(uint32_t stream, uint32_t image, uint32_t i, TgSeed s) {
   uint32_t w0, w1;
   d_philox2(i, image, stream, 0u, s.lo, s.hi, &w0, &w1);
-  return ((unsigned long long)w0 << 32) | w1;
+  return TG_KEY_MASK(s, ((unsigned long long)w0 << 32) | w1);
 }
 __device__ __forceinline__ uint32_t d_key_hi(uint32_t stream, uint32_t image, uint32_t i, TgSeed s) {
   uint32_t w0, w1;
   d_philox2(i, image, stream, 0u, s.lo, s.hi, &w0, &w1);
-  return w0;
+  return TG_KEY_MASK_HI(s, w0);
 }
 
 // is candidate i (stored high key word w0) among the kept ones?  The low word is only computed on the threshold's high word.
@@ -379,6 +399,7 @@ extern "C" int odet_anchor_target(const float* anchors, int num_anchors, const f
   a.S = total_num_samples; a.max_pos = max_pos_samples;
   for (int k = 0; k < 4; ++k) { a.means.v[k] = means[k]; a.stds.v[k] = stds[k]; }
   a.seed.lo = (uint32_t)seed; a.seed.hi = (uint32_t)(seed >> 32); a.first_image = first_image_id;
+  TG_SEED_DIAG(a);
   a.colmax = ar.take<uint32_t>(B * TG_MAX_GT);
   a.cnt = ar.take<int32_t>(B * 8);
   const size_t head = ar.off;
@@ -606,6 +627,7 @@ extern "C" int odet_proposal_target(const float* rois, const int32_t* roi_counts
   for (int k = 0; k < 4; ++k) { a.means.v[k] = means[k]; a.stds.v[k] = stds[k]; }
   a.row_labels = reference_row_labels ? 1 : 0;
   a.seed.lo = (uint32_t)seed; a.seed.hi = (uint32_t)(seed >> 32); a.first_image = first_image_id;
+  TG_SEED_DIAG(a);
   a.cnt = ar.take<int32_t>(B * 8);
   const size_t head = ar.off;
   a.cls = ar.take<int8_t>(B * R);

@@ -60,6 +60,7 @@ DIAG_SIGNATURES = {
     'odet_debug_conv_tile': (_lib._i, [_lib._i] * 5),
     'odet_debug_x3_tile': (_lib._i, [_lib._i] * 3),
     'odet_debug_cvt_f16': (_lib._i, [_lib._vp, _lib._vp, _lib._vp, _lib.C.c_longlong, _lib._vp]),
+    'odet_debug_tg_key_mask': (_lib._i, [_lib.C.c_ulonglong]),
 }
 _diag_handle = None
 
@@ -86,7 +87,8 @@ def diag_handle():
 
 class diag_library:
     """with tools._diag.diag_library() as lib:  -- every C-ABI call of the block (ops.*, _lib.call) goes to the DIAGNOSTIC build,
-    which alone has odet_debug_conv_tile / odet_debug_x3_tile; any forced tile is cleared on the way out and the product
+    which alone has odet_debug_conv_tile / odet_debug_x3_tile / odet_debug_tg_key_mask; any forced tile and the key mask are
+    cleared on the way out and the product
     library is back afterwards.  Both libraries are stateless apart from that override, so buffers made by one work with the other."""
 
     def __enter__(self):
@@ -100,6 +102,7 @@ class diag_library:
             _lib._lib.odet_debug_conv_tile(0, 0, 0, 0, 0)
             _lib._lib.odet_debug_conv_tile(1, 0, 0, 0, 0)
             _lib._lib.odet_debug_x3_tile(0, 0, 0)
+            _lib._lib.odet_debug_tg_key_mask(0xFFFFFFFFFFFFFFFF)
         finally:
             _lib._lib = self.prev
         return False
