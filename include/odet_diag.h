@@ -12,11 +12,50 @@ extern "C" {
 
 /* forces the workgroup tile of this process's next float16 3x3 (form 0; the fused bottleneck tail included) / pointwise (form 1)
  * launches -- {nw waves, wn waves along the channels, mt 16-pixel tiles per wave, ns LDS stages}: (nw / wn) * 16 * mt pixels x
- * 64 * wn channels; ns == 2 the half-step-pipelined loop, ns > 2 the ring forms for launches with few pixels.  nw = 0 clears. */
+ * 64 * wn channels; ns == 2 the half-step-pipelined loop, ns > 2 the ring forms for launches with few pixels.  nw = 0 clears.
+ * Form 0 also reaches the fused RpnHead launch (tiles with wn = 4, mt 4 .. 8, two stages) and the pooled launch (two-stage
+ * tiles).  A tile that does not fit a launch (channels that do not divide cout, a form without that kernel) is not applied: the
+ * launch keeps its own pick, and odet_debug_last_plan shows which. */
 int odet_debug_conv_tile(int form, int nw, int wn, int mt, int ns);
 /* the same for the split-precision float32 launches (csrc/conv_x3.hip): (mt, wn) of its tile list and the K split (workgroups
  * per tile, 1 = none); mt = 0 clears */
 int odet_debug_x3_tile(int mt, int wn, int ksplit);
+/* the same for the exact-float32 launches (csrc/conv_f32.hip): (mt, wn) of its tile list; mt = 0 clears.  A tile whose channels
+ * do not divide cout is not applied (the last plan shows it). */
+int odet_debug_f32_tile(int mt, int wn);
+
+/* ---- which kernel ran.  Families: the three files that build the implicit-GEMM tile many times over. */
+#define ODET_DIAG_FAMILY_F16 0   /* csrc/conv3x3.hip: float16 */
+#define ODET_DIAG_FAMILY_F32 1   /* csrc/conv_f32.hip: exact float32 */
+#define ODET_DIAG_FAMILY_SPLIT 2 /* csrc/conv_x3.hip: three bfloat16 limbs / two float16 limbs */
+#define ODET_DIAG_FORM_PLAIN 0     /* 3x3 */
+#define ODET_DIAG_FORM_POINTWISE 1 /* 1x1 / dense / lateral merge / two sources */
+#define ODET_DIAG_FORM_TAIL 2      /* 3x3 + the bottleneck's last 1x1 (float16 only) */
+#define ODET_DIAG_FORM_RPN 3       /* 3x3 + the RpnHead's two 1x1 (float16 only) */
+#define ODET_DIAG_FORM_POOLED 4    /* 3x3 + ReLU + 2x2 max-pooling (float16 only; the plain form's kernel) */
+typedef struct odet_debug_plan {
+  int family, form;
+  int nw, wn, mt, ns; /* waves, waves along the channels, 16-pixel tiles per wave, LDS stages */
+  int limbs;          /* 3 / 2 for the split forms, 1 otherwise */
+  int ksplit;         /* workgroups per output tile (1 = no K split) */
+  int forced;         /* 1 when an override of this header chose the tile */
+  int reserved;
+  long long blocks;   /* workgroups of the launch, the padded ones included */
+  long long count;    /* launches of this family recorded by this process so far */
+} odet_debug_plan_t;
+/* the plan of this process's latest launch of `family`, written by the launcher just before it launches, with or without an
+ * override; ODET_E_INVALID before the first one */
+int odet_debug_last_plan(int family, odet_debug_plan_t* out);
+typedef struct odet_debug_tile {
+  int nw, wn, mt, ns, limbs;
+  int forms; /* bit f set: form f (ODET_DIAG_FORM_*) has a kernel for this tile */
+} odet_debug_tile_t;
+/* entry `index` of the family's tile list, read from the table the launchers dispatch on (kTiles / F32_FOR_TILES / X3_FOR_TILES
+ * then X2_FOR_TILES); returns 1 past the end */
+int odet_debug_tile_table(int family, int index, odet_debug_tile_t* out);
+/* on: the launchers of the three files check their arguments, plan, record and return ODET_OK before any HIP call (the kernels'
+ * one-time set-up included) -- plans can be read on a machine without a GPU, with pointer-valued integers for the arrays */
+int odet_debug_plan_only(int on);
 /* the float32 -> float16 conversion of the library's epilogues on its own (the packed conversion of csrc/odet_internal.h under
  * the product's compiler flags): n float32 values (n % 8 == 0, device, 16-byte aligned) -> their float16 bits, once through
  * d_cvt8_f16 (out_pk) and once through d_cvt_pk_f16 + d_pack8_f16 (out_pack8); values 2k / 2k + 1 share one packed instruction */

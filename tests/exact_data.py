@@ -845,7 +845,9 @@ for shape in ((1, 13, 21, 256, 512), (3, 7, 5, 128, 256), (2, 31, 45, 64, 192), 
 CASES['conv3x3-1-1-1-64-64'] = functools.partial(draws_case, conv3x3_case, 12, 1, 1, 1, 64, 64, k_eff=64)
 CASES['conv3x3_pool-1-1-1-64-64'] = functools.partial(draws_case, conv3x3_pool_case, 24, 1, 1, 1, 64, 64, k_eff=64)
 CASES['rgb-3-1-1-True'] = functools.partial(draws_case, rgb_case, 8, 3, 1, 1, True)                                                # (one pixel: the centre tap only)
-for H, W, mt in ((20, 84, 4), (328, 100, 5), (209, 200, 6), (300, 167, 7), (349, 167, 8)):      # test_conv3x3_f16_every_tile_height
+# test_conv3x3_f16_every_tile_height: shapes that pick the 256-channel tiles of 4 .. 8 pixel tiles per wave themselves (asserted
+# from the launcher's recorded plan: tests/conv_tile_cases.py EVERY_TILE_HEIGHT), then the shapes that test ran before
+for H, W in ((128, 250), (100, 334), (191, 250), (170, 334), (191, 334), (20, 84), (328, 100), (209, 200), (300, 167), (349, 167)):
     _add(conv3x3_case, 1, H, W, 64, 256, full=False)
 _add(conv3x3_levels_case, 2, ((25, 42), (13, 21), (7, 11), (4, 6)), 128, 256)
 for shape in ((2, 37, 45, 64, 64), (1, 64, 96, 64, 128), (3, 9, 7, 128, 256)):

@@ -700,33 +700,33 @@ def test_conv3x3_f16_implicit_gemm(B, H, W, cin, cout):
     assert torch.equal(out, got)
 
 
-def _conv3x3_tile_height(Ms, tiles_n):
-    """mirror of conv3x3_launch's choice of the pixel-tile height (csrc/conv3x3.hip): 16-pixel tiles per wave"""
-    best, mt_best = 1e300, 8
-    for mt in range(8, 3, -1):
-        slabs = sum((M + 32 * mt - 1) // (32 * mt) for M in Ms)
-        blocks = (slabs + 7) // 8 * 8 * tiles_n
-        cost = ((blocks + 255) // 256) * (mt + 2)
-        if cost < best * 0.97:
-            best, mt_best = cost, mt
-    return mt_best
-
-
 @pytest.mark.gpu
-@pytest.mark.parametrize('H,W,mt', [(20, 84, 4), (328, 100, 5), (209, 200, 6), (300, 167, 7), (349, 167, 8)])
-def test_conv3x3_f16_every_tile_height(H, W, mt):
-    """the five instantiations of k_conv3x3_f16 (128 / 160 / 192 / 224 / 256-pixel workgroup tiles, picked per launch
-    so that the slabs fill whole rounds of the 256 CUs): exact on integer-valued data, the last slab ending inside a
-    tile, zero padding at the borders"""
+def test_conv3x3_f16_every_tile_height():
+    """the five 256-channel instantiations of k_conv3x3_f16 (128 / 160 / 192 / 224 / 256-pixel workgroup tiles, picked per launch
+    so that the slabs fill whole rounds of the 256 CUs), each on a shape for which the launcher picks it itself: the tile is the
+    one the launcher RECORDED for the launch (the diagnostic build's last plan, include/odet_diag.h), five distinct ones; exact
+    on integer-valued data, the last slab ending inside a tile, zero padding at the borders.  The shapes this test ran before
+    the small-launch rules (they pick the 8-stage ring, the 160-pixel tile and three times the 128 x 128 tile) stay as further
+    cases; tests/conv_tile_cases.py holds both lists."""
+    import conv_tile_cases as ct
     from tf_eager_object_detection_amd import ops
-    assert _conv3x3_tile_height([H * W], 1) == mt
-    g = torch.Generator(device='cuda')
-    g.manual_seed(H)
-    x = torch.randint(-3, 4, (1, H, W, 64), device='cuda', generator=g).half()
-    w = torch.randint(-2, 3, (256, 64, 3, 3), device='cuda', generator=g).half().contiguous(memory_format=torch.channels_last)
-    got = ops.conv3x3_f16(x, w)
-    want = F.conv2d(x.permute(0, 3, 1, 2).float(), w.float(), None, 1, 1).permute(0, 2, 3, 1)
-    assert torch.equal(got.float(), want.half().float())
+    from tools._diag import diag_library, last_plan
+    recorded = []
+    for (H, W), tile in ct.EVERY_TILE_HEIGHT + ct.EARLIER_TILE_HEIGHT_SHAPES:
+        g = torch.Generator(device='cuda')
+        g.manual_seed(H)
+        x = torch.randint(-3, 4, (1, H, W, 64), device='cuda', generator=g).half()
+        w = torch.randint(-2, 3, (256, 64, 3, 3), device='cuda', generator=g).half().contiguous(memory_format=torch.channels_last)
+        want = F.conv2d(x.permute(0, 3, 1, 2).float(), w.float(), None, 1, 1).permute(0, 2, 3, 1)
+        with diag_library() as lib:
+            before = ct.plan_count(lib, 'f16')
+            got = ops.conv3x3_f16(x, w)
+            plan = last_plan('f16', lib)
+        assert plan['count'] == before + 1 and plan['form'] == 'plain' and not plan['forced'] and plan['tile'] == tile, ((H, W), plan)
+        recorded.append(plan['tile'])
+        assert torch.equal(got.float(), want.half().float()), (H, W)
+        assert torch.equal(ops.conv3x3_f16(x, w), got), (H, W)               # (the shipped library: the same kernel, the same bits)
+    assert sorted(set(recorded[:5])) == [(8, 4, mt, 2) for mt in (4, 5, 6, 7, 8)]
 
 
 @pytest.mark.gpu

@@ -13,7 +13,7 @@ OBJ_DIR = os.path.join(CSRC, '_obj')
 LIB = os.path.join(PKG, 'libodet_hip.so')
 SOURCES = ['boxes.hip', 'sort.hip', 'nms.hip', 'roi.hip', 'roi_half.hip', 'postops.hip', 'neck.hip', 'epilogue.hip', 'conv1x1.hip', 'conv3x3.hip', 'conv_f32.hip', 'conv_x3.hip', 'rpn_tail.hip',
            'calib.hip', 'stem.hip', 'executor.hip', 'preprocess.hip', 'coco_eval.hip', 'voc_eval.hip', 'targets.hip', 'losses.hip']
-HEADERS = [os.path.join(CSRC, 'odet_internal.h'), os.path.join(CSRC, 'conv_f32_common.h'), os.path.join(INCLUDE, 'odet.h')]
+HEADERS = [os.path.join(CSRC, 'odet_internal.h'), os.path.join(CSRC, 'conv_f32_common.h'), os.path.join(CSRC, 'conv_diag.h'), os.path.join(INCLUDE, 'odet.h')]
 
 # -ffp-contract=off: the parity contract is "one IEEE float32 operation per reference
 # operation"; an FMA would change low bits of box coordinates and bilinear taps.
@@ -74,7 +74,7 @@ def build(force=False, verbose=False):
 # (include/odet_diag.h).
 # Test / tool infrastructure (tools/_diag.py loads it explicitly); the product never loads it and the shipped library has no hook.
 DIAG_LIB = os.path.join(os.path.dirname(PKG), 'tools', 'libodet_hip_diag.so')
-DIAG_SOURCES = ['conv3x3.hip', 'conv_x3.hip', 'targets.hip']
+DIAG_SOURCES = ['conv3x3.hip', 'conv_f32.hip', 'conv_x3.hip', 'targets.hip']
 
 
 def build_diag(force=False, verbose=False):

@@ -36,6 +36,7 @@
 #include <mutex>
 
 #include "odet_internal.h"
+#include "conv_diag.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
@@ -795,6 +796,18 @@ static const TileEntry kTiles[] = {
 #undef C3_LEGACY
 #undef C3_RING
 static constexpr int kNumTiles = (int)(sizeof(kTiles) / sizeof(kTiles[0]));
+// the fused RpnHead form (TAIL): 256-channel tiles of 4 .. 8 pixel tiles per wave, two stages
+struct TailEntry { int mt; conv_kernel_t k; };
+static const TailEntry kTailTiles[] = {
+    {4, k_conv3x3_f16<4, 4, true>}, {5, k_conv3x3_f16<5, 4, true>}, {6, k_conv3x3_f16<6, 4, true>},
+    {7, k_conv3x3_f16<7, 4, true>}, {8, k_conv3x3_f16<8, 4, true>},
+};
+static conv_kernel_t find_tail_tile(const ConvTile& t) {
+  if (t.nw != 8 || t.wn != 4 || t.ns != 2) return nullptr;
+  for (const TailEntry& e : kTailTiles)
+    if (e.mt == t.mt) return e.k;
+  return nullptr;
+}
 
 static const TileEntry* find_tile(const ConvTile& t) {
   for (const TileEntry& e : kTiles)
@@ -816,9 +829,7 @@ static hipError_t tiles_init() {                // (more than the default 64 KB 
       set((const void*)e.plain); set((const void*)e.pw);
       if (e.blk) set((const void*)e.blk);
     }
-    set((const void*)k_conv3x3_f16<4, 4, true>); set((const void*)k_conv3x3_f16<5, 4, true>);
-    set((const void*)k_conv3x3_f16<6, 4, true>); set((const void*)k_conv3x3_f16<7, 4, true>);
-    set((const void*)k_conv3x3_f16<8, 4, true>);
+    for (const TailEntry& e : kTailTiles) set((const void*)e.k);
     return rc;
   });
 }
@@ -892,13 +903,55 @@ extern "C" int odet_debug_conv_tile(int form, int nw, int wn, int mt, int ns) {
   g_tile_override[form].store((unsigned)nw << 24 | (unsigned)wn << 16 | (unsigned)mt << 8 | (unsigned)ns);
   return ODET_OK;
 }
-static bool tile_override(int form, int cout, int need_wn, ConvTile* t) {
+// need_wn: the launch's form has kernels for this channel width only; need_two_stage: and no ring form
+static bool tile_override(int form, int cout, int need_wn, ConvTile* t, bool need_two_stage = false) {
   const unsigned v = g_tile_override[form].load();
   if (!v) return false;
   const ConvTile o{(int)(v >> 24), (int)(v >> 16 & 255), (int)(v >> 8 & 255), (int)(v & 255)};
-  if (cout % (64 * o.wn) || (need_wn && o.wn != need_wn)) return false;
+  if (cout % (64 * o.wn) || (need_wn && o.wn != need_wn) || (need_two_stage && o.ns != 2)) return false;
   *t = o;
   return true;
+}
+
+// ---- which kernel ran (include/odet_diag.h): the last plan of every family, the plan-only mode, the tile table.  The three
+// convolution files record through odet_diag_record (conv_diag.h); the state lives here.
+static std::atomic<int> g_plan_only{0};
+static std::mutex g_plan_mutex;
+static odet_debug_plan_t g_last_plan[3];
+bool odet_diag_plan_only() { return g_plan_only.load() != 0; }
+void odet_diag_record(int family, int form, int nw, int wn, int mt, int ns, int limbs, int ksplit, long long blocks, int forced) {
+  std::lock_guard<std::mutex> lock(g_plan_mutex);
+  odet_debug_plan_t& r = g_last_plan[family];
+  const long long count = r.count + 1;
+  r = odet_debug_plan_t{family, form, nw, wn, mt, ns, limbs, ksplit, forced, 0, blocks, count};
+}
+extern "C" int odet_debug_plan_only(int on) {
+  g_plan_only.store(on ? 1 : 0);
+  return ODET_OK;
+}
+extern "C" int odet_debug_last_plan(int family, odet_debug_plan_t* out) {
+  ODET_REQUIRE(family >= 0 && family < 3 && out, "odet_debug_last_plan: family 0 .. 2, non-null record");
+  std::lock_guard<std::mutex> lock(g_plan_mutex);
+  ODET_REQUIRE(g_last_plan[family].count > 0, "odet_debug_last_plan: family %d has not launched yet", family);
+  *out = g_last_plan[family];
+  return ODET_OK;
+}
+int odet_diag_tile_table_f32(int index, odet_debug_tile_t* out);       // conv_f32.hip
+int odet_diag_tile_table_split(int index, odet_debug_tile_t* out);     // conv_x3.hip
+extern "C" int odet_debug_tile_table(int family, int index, odet_debug_tile_t* out) {
+  ODET_REQUIRE(family >= 0 && family < 3 && index >= 0 && out, "odet_debug_tile_table: family 0 .. 2, index >= 0, non-null record");
+  if (family == ODET_DIAG_FAMILY_F32) return odet_diag_tile_table_f32(index, out);
+  if (family == ODET_DIAG_FAMILY_SPLIT) return odet_diag_tile_table_split(index, out);
+  if (index >= kNumTiles) return 1;
+  const TileEntry& e = kTiles[index];
+  int forms = 0;
+  if (e.plain) forms |= 1 << ODET_DIAG_FORM_PLAIN;
+  if (e.pw) forms |= 1 << ODET_DIAG_FORM_POINTWISE;
+  if (e.blk) forms |= 1 << ODET_DIAG_FORM_TAIL;
+  if (find_tail_tile(e.t)) forms |= 1 << ODET_DIAG_FORM_RPN;
+  if (e.plain && e.t.ns == 2) forms |= 1 << ODET_DIAG_FORM_POOLED;     // (the plain kernel's pooling epilogue; the rings have none)
+  *out = odet_debug_tile_t{e.t.nw, e.t.wn, e.t.mt, e.t.ns, 1, forms};
+  return ODET_OK;
 }
 
 // Diagnostic build only: the float32 -> float16 conversion of every epilogue of this library (d_cvt_pk_f16 / d_cvt8_f16 /
@@ -931,7 +984,7 @@ extern "C" int odet_debug_cvt_f16(const float* src, void* out_pk, void* out_pack
   return ODET_OK;
 }
 #else
-static inline bool tile_override(int, int, int, ConvTile*) { return false; }   // (the shipped library: no process-global override)
+static inline bool tile_override(int, int, int, ConvTile*, bool = false) { return false; }   // (the shipped library: no process-global override)
 #endif
 
 struct Conv3x3Tail {             // the fused RpnHead tail (nullable in conv3x3_launch)
@@ -951,7 +1004,7 @@ static int conv3x3_launch(const odet_conv_level_t* levels, int num_levels, const
   ODET_REQUIRE(cout > 0 && cout % 64 == 0, "odet_conv3x3_f16: cout %d must be a multiple of 64", cout);
   ODET_REQUIRE((unsigned long long)cout * 9ull * cin * 2ull < 0x7FFFFFFFull, "odet_conv3x3_f16: weights too large");
   ODET_REQUIRE(((uintptr_t)w | (uintptr_t)bias) % 16 == 0, "odet_conv3x3_f16: weights and bias must be 16-byte aligned");
-  ODET_HIP(tiles_init());
+  ODET_DIAG_SETUP(tiles_init());
   Conv3x3Params p;
   long long total = 0;
   for (int l = 0; l < ODET_MAX_LEVELS; ++l) {
@@ -1027,11 +1080,18 @@ static int conv3x3_launch(const odet_conv_level_t* levels, int num_levels, const
     }
   }
   ConvTile tile{8, wn_sel, mt_best, 2};
+  bool forced = false;
+  (void)forced;                                           // (read by the diagnostic build's plan record only)
   if (!tail && !pool) {
     // few pixels (conv4 / conv5 / the small neck levels at batch 1 .. 2): the ring form
     if (!blk) tile = pick_small(p.M, num_levels, cout, refine_sub_round(p.M, num_levels, cout, 9 * (cin / C3_BK), tile));
-    tile_override(0, cout, blk ? wn_sel : 0, &tile);
+    forced = tile_override(0, cout, blk ? wn_sel : 0, &tile);
     ODET_REQUIRE(!blk || tile.ns == 2, "odet_bottleneck_tail_f16: the fused tail has no ring form");
+  } else if (tail) {
+    ConvTile o = tile;                                    // (diagnostic build: the five tiles this form has kernels for)
+    if (tile_override(0, cout, 4, &o, true) && find_tail_tile(o)) { tile = o; forced = true; }
+  } else {
+    forced = tile_override(0, cout, 0, &tile, true);      // (diagnostic build: the pooling epilogue is the two-stage kernels')
   }
   const TileEntry* te = find_tile(tile);
   ODET_REQUIRE(te != nullptr, "odet_conv3x3_f16: internal: no kernel for the picked tile");
@@ -1048,15 +1108,11 @@ static int conv3x3_launch(const odet_conv_level_t* levels, int num_levels, const
   const long long groups = (total + 7) / 8;
   const long long blocks = groups * 8 * (tail ? 1 : p.tiles_n);
   ODET_REQUIRE(blocks < (1ll << 31), "odet_conv3x3_f16: too many workgroups");
+  ODET_DIAG_PLAN(ODET_DIAG_FAMILY_F16, tail ? ODET_DIAG_FORM_RPN : blk ? ODET_DIAG_FORM_TAIL : pool ? ODET_DIAG_FORM_POOLED : ODET_DIAG_FORM_PLAIN,
+                 tile.nw, tile.wn, tile.mt, tile.ns, 1, 1, blocks, forced);
   if (tail) {
-    conv_kernel_t kt = k_conv3x3_f16<8, 4, true>;
-    switch (mt_best) {
-      case 4: kt = k_conv3x3_f16<4, 4, true>; break;
-      case 5: kt = k_conv3x3_f16<5, 4, true>; break;
-      case 6: kt = k_conv3x3_f16<6, 4, true>; break;
-      case 7: kt = k_conv3x3_f16<7, 4, true>; break;
-      default: break;
-    }
+    const conv_kernel_t kt = find_tail_tile(tile);
+    ODET_REQUIRE(kt != nullptr, "odet_rpn_head_fused_f16: internal: no kernel for the picked tile");
     // (the K loop's stages + 128 bytes per pixel for the sums over the channel tiles)
     return launch_tile(kt, tile, (unsigned)blocks, C3_LDS_BYTES + (unsigned)TMsel * 128u, p, st);
   }
@@ -1121,7 +1177,7 @@ static int pointwise_launch(const char* who, const void* x, const void* w, const
                "%s: pointers must be 16-byte aligned", who);
   ODET_REQUIRE(!(epi.res && epi.top), "%s: shortcut and top-down merge exclude each other", who);
   ODET_REQUIRE(!epi.top || (stride == 1 && epi.th > 0 && epi.tw > 0 && !relu), "%s: bad merge arguments", who);
-  ODET_HIP(tiles_init());
+  ODET_DIAG_SETUP(tiles_init());
   const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
   const long long M = (long long)batch * Ho * Wo;
   const long long Min = epi.x2 ? M : (long long)batch * H * W;       // (two sources: x has the OUTPUT's rows)
@@ -1165,7 +1221,7 @@ static int pointwise_launch(const char* who, const void* x, const void* w, const
   // fewer workgroups than the chip holds (few pixels: batch 1 .. 4 on the small maps, the RoI head's dense layers at 1000
   // rows): the ring forms
   tile = pick_small(&M, 1, cout, refine_sub_round(&M, 1, cout, (cin + (epi.x2 ? epi.cin2 : 0)) / C3_BK, tile));
-  tile_override(1, cout, 0, &tile);
+  const bool forced = tile_override(1, cout, 0, &tile);
   const TileEntry* te = find_tile(tile);
   ODET_REQUIRE(te != nullptr, "%s: internal: no kernel for the picked tile", who);
   const int TMsel = tile_tm(tile);
@@ -1177,6 +1233,7 @@ static int pointwise_launch(const char* who, const void* x, const void* w, const
   p.num_levels = 1; p.cin = cin; p.cout = cout; p.relu = relu ? 1 : 0;
   const long long blocks = (total + 7) / 8 * 8 * p.tiles_n;
   ODET_REQUIRE(blocks < (1ll << 31), "%s: too many workgroups", who);
+  ODET_DIAG_PLAN(ODET_DIAG_FAMILY_F16, ODET_DIAG_FORM_POINTWISE, tile.nw, tile.wn, tile.mt, tile.ns, 1, 1, blocks, forced);
   return launch_tile(te->pw, tile, (unsigned)blocks, tile_lds(tile), p, st);
 }
 

@@ -24,6 +24,7 @@
 #include <mutex>
 
 #include "conv_f32_common.h"
+#include "conv_diag.h"
 
 typedef __amdgpu_buffer_rsrc_t f32_rsrc_t;
 typedef __attribute__((address_space(3))) void* f32_lds_ptr;
@@ -273,6 +274,45 @@ static void f32_pick_tile(const long long* M, int num_levels, int cout, int* wn_
   *wn_out = wn_best; *mt_out = mt_best;
 }
 
+#ifdef ODET_DIAG
+// Diagnostic build only (-DODET_DIAG: tools/libodet_hip_diag.so, include/odet_diag.h; the shipped library has neither the entry
+// points nor the override): force the tile of this process's exact-float32 launches -- (mt, wn) of F32_FOR_TILES; mt = 0 clears.
+#include <atomic>
+static bool f32_has_tile(int mt, int wn) {
+#define F32_H(MT_, WN_) if (mt == MT_ && wn == WN_) return true;
+  F32_FOR_TILES(F32_H)
+#undef F32_H
+  return false;
+}
+static std::atomic<unsigned> g_f32_override{0u};
+extern "C" int odet_debug_f32_tile(int mt, int wn) {
+  if (mt == 0) { g_f32_override.store(0u); return ODET_OK; }
+  ODET_REQUIRE(f32_has_tile(mt, wn), "odet_debug_f32_tile: no such tile (mt %d, wn %d)", mt, wn);
+  g_f32_override.store((unsigned)mt << 8 | (unsigned)wn);
+  return ODET_OK;
+}
+static bool f32_tile_override(int cout, int* wn, int* mt) {
+  const unsigned o = g_f32_override.load();
+  if (!o || cout % (64 * (int)(o & 255))) return false;
+  *mt = (int)(o >> 8); *wn = (int)(o & 255);
+  return true;
+}
+int odet_diag_tile_table_f32(int index, odet_debug_tile_t* out) {
+  static const int tiles[][2] = {
+#define F32_T(MT_, WN_) {MT_, WN_},
+      F32_FOR_TILES(F32_T)
+#undef F32_T
+  };
+  if (index >= (int)(sizeof(tiles) / sizeof(tiles[0]))) return 1;
+  const int mt = tiles[index][0], wn = tiles[index][1], tm = (8 / wn) * 16 * mt, tn = 64 * wn;
+  *out = odet_debug_tile_t{8, wn, mt, (int)(f32_lds_bytes(tm, tn) / ((unsigned)(tm + tn) * 128u)), 1,
+                           1 << ODET_DIAG_FORM_PLAIN | 1 << ODET_DIAG_FORM_POINTWISE};
+  return ODET_OK;
+}
+#else
+static inline bool f32_tile_override(int, int*, int*) { return false; }   // (the shipped library: no process-global override)
+#endif
+
 template <bool PW>
 static void f32_launch_tile(int wn, int mt, dim3 grid, unsigned lds_bytes, hipStream_t st, const ConvF32Params& p) {
 #define F32_L(MT_, WN_)                                                                                     \
@@ -288,13 +328,16 @@ static void f32_launch_tile(int wn, int mt, dim3 grid, unsigned lds_bytes, hipSt
 // a filled plan -> the kernels' LDS limit, the tile, the plan's tile-dependent rest, the launch
 template <bool PW>
 static int f32_launch(const char* who, ConvF32Params* p, hipStream_t st) {
-  ODET_HIP(f32_prepare_kernels());
+  ODET_DIAG_SETUP(f32_prepare_kernels());
   int wn, mt;
   f32_pick_tile(p->M, p->num_levels, p->cout, &wn, &mt);
+  const bool forced = f32_tile_override(p->cout, &wn, &mt);
   const int TMsel = (8 / wn) * 16 * mt;
   long long blocks;
   const int rt = conv_f32_plan_tiles(who, F32_RULES, TMsel, wn, p, &blocks);
   if (rt != ODET_OK) return rt;
+  ODET_DIAG_PLAN(ODET_DIAG_FAMILY_F32, PW ? ODET_DIAG_FORM_POINTWISE : ODET_DIAG_FORM_PLAIN, 8, wn, mt,
+                 (int)(f32_lds_bytes(TMsel, 64 * wn) / ((unsigned)(TMsel + 64 * wn) * 128u)), 1, 1, blocks, forced);
   f32_launch_tile<PW>(wn, mt, dim3((unsigned)blocks), f32_lds_bytes(TMsel, 64 * wn), st, *p);
   ODET_LAUNCH_CHECK();
   return ODET_OK;

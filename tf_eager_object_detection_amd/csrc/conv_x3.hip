@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "conv_f32_common.h"
+#include "conv_diag.h"
 
 typedef __bf16 x3b8 __attribute__((ext_vector_type(8)));
 typedef __bf16 x3b2 __attribute__((ext_vector_type(2)));
@@ -539,6 +540,21 @@ extern "C" int odet_debug_x3_tile(int mt, int wn, int ksplit) {
   g_x3_override.store(mt > 0 ? ((unsigned)(ksplit > 1 ? ksplit : 1) << 16 | (unsigned)mt << 8 | (unsigned)wn) : 0u);
   return ODET_OK;
 }
+// the tile lists as include/odet_diag.h enumerates them: the three-limb tiles, then the two-limb ones
+int odet_diag_tile_table_split(int index, odet_debug_tile_t* out) {
+  static const int tiles[][3] = {
+#define X3_T(MT_, WN_) {3, MT_, WN_},
+#define X2_T(MT_, WN_) {2, MT_, WN_},
+      X3_FOR_TILES(X3_T) X2_FOR_TILES(X2_T)
+#undef X3_T
+#undef X2_T
+  };
+  if (index >= (int)(sizeof(tiles) / sizeof(tiles[0]))) return 1;
+  const int nl = tiles[index][0];
+  *out = odet_debug_tile_t{8, tiles[index][2], tiles[index][1], nl == 2 ? 3 : 2, nl,
+                           1 << ODET_DIAG_FORM_PLAIN | 1 << ODET_DIAG_FORM_POINTWISE};
+  return ODET_OK;
+}
 #endif
 
 // ---- tile and split-K selection --------------------------------------------------------------------------------------------
@@ -551,7 +567,8 @@ extern "C" int odet_debug_x3_tile(int mt, int wn, int ksplit) {
 // a deep-K, few-row layer is a latency chain of its K-steps (conv5's 3 x 3 at batch 1: 144 steps of 1.5 us on 18 workgroups).
 #define X3_TICKETS 4096                                  // tiles of a split-K launch (the workspace's ticket words)
 struct X3Pick { int mt, wn, ksplit; };
-static X3Pick x3_pick_tile(const long long* M, int num_levels, int cout, int ksteps, size_t part_bytes_max, int nl) {
+static X3Pick x3_pick_tile(const long long* M, int num_levels, int cout, int ksteps, size_t part_bytes_max, int nl,
+                           bool* forced = nullptr) {
   static const int cand[][2] = {{4, 2}, {2, 2}, {4, 4}, {2, 1}, {1, 1}};       // (mt, wn)
   X3Pick best_pick{0, 0, 1};
   double best = 1e300;
@@ -585,6 +602,7 @@ static X3Pick x3_pick_tile(const long long* M, int num_levels, int cout, int kst
   const unsigned o = g_x3_override.load();
   if (o && cout % (64 * (int)(o & 255)) == 0 && !(nl == 2 && (o >> 8 & 255) == 4 && (o & 255) == 2)) {
     best_pick = X3Pick{(int)(o >> 8 & 255), (int)(o & 255), std::max(1, (int)(o >> 16))};
+    if (forced) *forced = true;
     const int tm = x3_tile_pixels(best_pick.mt, best_pick.wn), tn = 64 * best_pick.wn;
     long long slabs = 0;
     for (int l = 0; l < num_levels; ++l) slabs += (M[l] + tm - 1) / tm;
@@ -646,9 +664,10 @@ static unsigned* x3_status_word(const X3Form& form, void* ws, size_t ws_bytes) {
 // a filled plan -> the kernels' LDS limit, the tile and the K split, the plan's tile-dependent rest, the form's extras, the launch
 template <bool PW>
 static int x3_launch(const char* who, const X3Form& form, ConvF32Params* p, void* ws, size_t ws_bytes, hipStream_t st) {
-  ODET_HIP(x3_prepare_kernels());
+  ODET_DIAG_SETUP(x3_prepare_kernels());
   const int ksteps = ((PW ? 1 : 9) * p->cin + p->cin2) / X3_BK;
-  const X3Pick pick = x3_pick_tile(p->M, p->num_levels, p->cout, ksteps, x3_part_bytes(ws, ws_bytes), form.nl);
+  bool forced = false;
+  const X3Pick pick = x3_pick_tile(p->M, p->num_levels, p->cout, ksteps, x3_part_bytes(ws, ws_bytes), form.nl, &forced);
   const int TMsel = x3_tile_pixels(pick.mt, pick.wn);
   long long blocks;
   const int rt = conv_f32_plan_tiles(who, X3_RULES, TMsel, pick.wn, p, &blocks);
@@ -657,6 +676,8 @@ static int x3_launch(const char* who, const X3Form& form, ConvF32Params* p, void
   p->status = x3_status_word(form, ws, ws_bytes);
   const int rs = x3_apply_split(p, pick, blocks, TMsel, ws, ws_bytes, who);
   if (rs != ODET_OK) return rs;
+  ODET_DIAG_PLAN(ODET_DIAG_FAMILY_SPLIT, PW ? ODET_DIAG_FORM_POINTWISE : ODET_DIAG_FORM_PLAIN, 8, pick.wn, pick.mt, form.nl == 2 ? 3 : 2,
+                 form.nl, p->ksplit > 1 ? p->ksplit : 1, blocks * (p->ksplit > 1 ? p->ksplit : 1), forced);
   const int rc = x3_launch_tile<PW>(form.nl, pick.wn, pick.mt, dim3((unsigned)(blocks * (p->ksplit > 1 ? p->ksplit : 1))),
                                     x3_lds_bytes(TMsel, 64 * pick.wn, form.nl), st, *p);
   if (rc != ODET_OK) return rc;

@@ -56,9 +56,28 @@ def build_variant(out_path, extra_flags=(), sources=None, patch=None, only=None)
 
 
 # ---- the diagnostic build of the library (tools/libodet_hip_diag.so: _build.build_diag(), include/odet_diag.h) ----------------
+class DebugPlan(_lib.C.Structure):
+    """odet_debug_plan_t"""
+    _fields_ = [(n, _lib.C.c_int) for n in ('family', 'form', 'nw', 'wn', 'mt', 'ns', 'limbs', 'ksplit', 'forced', 'reserved')] + \
+               [('blocks', _lib.C.c_longlong), ('count', _lib.C.c_longlong)]
+
+
+class DebugTile(_lib.C.Structure):
+    """odet_debug_tile_t"""
+    _fields_ = [(n, _lib.C.c_int) for n in ('nw', 'wn', 'mt', 'ns', 'limbs', 'forms')]
+
+
+FAMILY_F16, FAMILY_F32, FAMILY_SPLIT = 0, 1, 2
+FAMILIES = ('f16', 'f32', 'split')
+FORMS = ('plain', 'pointwise', 'tail', 'rpn', 'pooled')
+
 DIAG_SIGNATURES = {
     'odet_debug_conv_tile': (_lib._i, [_lib._i] * 5),
     'odet_debug_x3_tile': (_lib._i, [_lib._i] * 3),
+    'odet_debug_f32_tile': (_lib._i, [_lib._i] * 2),
+    'odet_debug_last_plan': (_lib._i, [_lib._i, _lib.C.POINTER(DebugPlan)]),
+    'odet_debug_tile_table': (_lib._i, [_lib._i, _lib._i, _lib.C.POINTER(DebugTile)]),
+    'odet_debug_plan_only': (_lib._i, [_lib._i]),
     'odet_debug_cvt_f16': (_lib._i, [_lib._vp, _lib._vp, _lib._vp, _lib.C.c_longlong, _lib._vp]),
     'odet_debug_tg_key_mask': (_lib._i, [_lib.C.c_ulonglong]),
 }
@@ -85,11 +104,34 @@ def diag_handle():
     return _diag_handle
 
 
+def last_plan(family, handle=None):
+    """the latest launch of `family` ('f16' / 'f32' / 'split' or its number) as a dict: form by name, tile = (nw, wn, mt, ns)"""
+    h = handle or diag_handle()
+    fam = FAMILIES.index(family) if isinstance(family, str) else family
+    p = DebugPlan()
+    _lib.check(h.odet_debug_last_plan(fam, _lib.C.byref(p)))
+    return {'family': FAMILIES[p.family], 'form': FORMS[p.form], 'tile': (p.nw, p.wn, p.mt, p.ns), 'limbs': p.limbs,
+            'ksplit': p.ksplit, 'forced': bool(p.forced), 'blocks': p.blocks, 'count': p.count}
+
+
+def tile_table(family, handle=None):
+    """the family's tile list as the launchers dispatch on it: [{'tile': (nw, wn, mt, ns), 'limbs': n, 'forms': (names)}]"""
+    h = handle or diag_handle()
+    fam = FAMILIES.index(family) if isinstance(family, str) else family
+    out, t = [], DebugTile()
+    while True:
+        rc = h.odet_debug_tile_table(fam, len(out), _lib.C.byref(t))
+        if rc == 1:
+            return out
+        _lib.check(rc)
+        out.append({'tile': (t.nw, t.wn, t.mt, t.ns), 'limbs': t.limbs,
+                    'forms': tuple(f for i, f in enumerate(FORMS) if t.forms >> i & 1)})
+
+
 class diag_library:
     """with tools._diag.diag_library() as lib:  -- every C-ABI call of the block (ops.*, _lib.call) goes to the DIAGNOSTIC build,
-    which alone has odet_debug_conv_tile / odet_debug_x3_tile / odet_debug_tg_key_mask; any forced tile and the key mask are
-    cleared on the way out and the product
-    library is back afterwards.  Both libraries are stateless apart from that override, so buffers made by one work with the other."""
+    which alone has the odet_debug_* hooks of include/odet_diag.h; any forced tile, the plan-only mode and the key mask are
+    cleared on the way out and the product library is back afterwards.  Both libraries are stateless apart from that override, so buffers made by one work with the other."""
 
     def __enter__(self):
         _lib.lib()                                    # (the product library first: it stays the process's RTLD_GLOBAL one)
@@ -102,6 +144,8 @@ class diag_library:
             _lib._lib.odet_debug_conv_tile(0, 0, 0, 0, 0)
             _lib._lib.odet_debug_conv_tile(1, 0, 0, 0, 0)
             _lib._lib.odet_debug_x3_tile(0, 0, 0)
+            _lib._lib.odet_debug_f32_tile(0, 0)
+            _lib._lib.odet_debug_plan_only(0)
             _lib._lib.odet_debug_tg_key_mask(0xFFFFFFFFFFFFFFFF)
         finally:
             _lib._lib = self.prev
