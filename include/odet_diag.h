@@ -53,9 +53,28 @@ typedef struct odet_debug_tile {
 /* entry `index` of the family's tile list, read from the table the launchers dispatch on (kTiles / F32_FOR_TILES / X3_FOR_TILES
  * then X2_FOR_TILES); returns 1 past the end */
 int odet_debug_tile_table(int family, int index, odet_debug_tile_t* out);
-/* on: the launchers of the three files check their arguments, plan, record and return ODET_OK before any HIP call (the kernels'
+/* on: the launchers of the three files and the RoI launcher (csrc/roi.hip) check their arguments, plan, record and return ODET_OK before any HIP call (the kernels'
  * one-time set-up included) -- plans can be read on a machine without a GPU, with pointer-valued integers for the arrays */
 int odet_debug_plan_only(int on);
+/* ---- which RoI launch ran (csrc/roi.hip).  odet_roi_pool_batch -- behind every odet_roi_pool* entry point and the RoI stage of
+ * odet_fpn_step_enqueue[_batch] -- plans a launch from (B, C, n, P) alone; f16 / pool_mode / norm_mode pick the kernel
+ * instantiation.  The fields from `waves` to `xcds_per_img` are the ones k_roi_pool reads from its parameter block. */
+typedef struct odet_debug_roi_plan {
+  int B, C, n, P, f16, pool_mode, norm_mode;
+  int waves;          /* waves (= output rows) per workgroup: P, or 8 rows of whatever RoIs when P > 16 */
+  int slices;         /* > 1: C / 256 workgroups per RoI */
+  int roi_groups;     /* > 0: an XCD serves one slice of one of roi_groups parts of the processing order; 0: slice-major */
+  int rois_per_xcd, blocks_per_xcd, nblocks;
+  int xcd_images;     /* 1: the image comes from the XCD slot (B = 2, 4, 8), 0: from blockIdx.y */
+  int xcds_per_img;
+  int grid_x, grid_y, threads;
+  long long count;    /* RoI launches recorded by this process so far (0 from odet_debug_roi_plan) */
+} odet_debug_roi_plan_t;
+/* the plan of this process's latest RoI launch, written by the launcher just before it launches (in plan-only mode: before it
+ * returns); count == 0 and all else zero before the first one */
+int odet_debug_last_roi_plan(odet_debug_roi_plan_t* out);
+/* the same planning function on its own: what a launch of B images, n RoIs each, would be */
+int odet_debug_roi_plan(int B, int C, int n, int pool_size, int f16, int pool_mode, int norm_mode, odet_debug_roi_plan_t* out);
 /* the float32 -> float16 conversion of the library's epilogues on its own (the packed conversion of csrc/odet_internal.h under
  * the product's compiler flags): n float32 values (n % 8 == 0, device, 16-byte aligned) -> their float16 bits, once through
  * d_cvt8_f16 (out_pk) and once through d_cvt_pk_f16 + d_pack8_f16 (out_pack8); values 2k / 2k + 1 share one packed instruction */

@@ -391,10 +391,13 @@ def test_roi_pooling_layers_match_oracle_bit_exact():
 
 @pytest.mark.parametrize('C,n', [(4, 40), (256, 40), (512, 40), (1024, 40), (512, 2100), (768, 2050), (260, 40)])
 def test_roi_pool_channel_counts(C, n):
-    """channel counts around the kernel's 256-channel slices: one slice; several slices with one workgroup per
-    (RoI, slice) (launches of fewer than 2048 RoIs) or one workgroup per RoI looping over them (n >= 2048), both with
-    the register carry between neighbouring bins; a count that is not a multiple of 256 (the plain walk); float16 maps
-    take the same launch shapes."""
+    """channel counts around the kernel's 256-channel slices, at pool_size 7 (so waves == P): one slice (C <= 256); C = 512 /
+    1024 with one workgroup per (RoI, 256-channel slice) whatever n is -- a single image has 8 XCDs, so an XCD serves one slice
+    of one of 8 / slices contiguous parts of the RoIs (roi_groups 4 / 2), and at C = 768, whose three slices do not divide the
+    8 XCDs, every XCD walks all slices of its RoIs slice-major --, float32 with the register carry between neighbouring bins;
+    a count that is not a multiple of 256 (one workgroup per RoI, the plain walk looping over the 256-channel passes); float16
+    maps take the same launch shapes.  (P > 16 with its in-wave slice loop and the batched deals are not reached here:
+    tests/test_roi_paths_gpu.py runs them with the plan asserted.)"""
     rng = np.random.default_rng(C + n)
     feat = _feat((20, 30), C, rng)
     rois = syn.random_boxes(n, (320, 480), rng, 8, 300)

@@ -41,7 +41,7 @@
 #include <mutex>
 #include <type_traits>
 
-#include "odet_internal.h"
+#include "conv_diag.h"   // (odet_internal.h; in the diagnostic build the plan-only switch)
 
 struct RoiParams {
   const void* data[ODET_MAX_BATCH][ODET_MAX_LEVELS];    // [image of the batch][pyramid level]; float32 or float16
@@ -609,7 +609,10 @@ __global__ void __launch_bounds__(1024) k_roi_pool(RoiParams p) {
     return;
   }
   // every sample of the row inside the map (boxes clipped to the image: nearly always)?
-  const bool x_inside = __builtin_amdgcn_ballot_w64(lane < P && xok_l != 3) == 0;
+  // (a reversed box, x1 > x2: a bin whose second sample column lies LEFT of its first would need a negative column offset
+  // from c0, which the unsigned per-lane buffer offset cannot carry -- the load would fall outside the descriptor's range and
+  // read 0.  Such rows take the guarded form, which addresses each tap by itself: same values, same operations.)
+  const bool x_inside = __builtin_amdgcn_ballot_w64(lane < P && (xok_l != 3 || tx1.lo < tx0.lo)) == 0;
   if (yok != 3 || !x_inside) {
     roi_row_guarded<POOL, FT>(rc, out, P, C, ch0, ch1, cabs_l, xok_l, xw0_l, xw1_l, yok);
     return;
@@ -691,6 +694,91 @@ static void roi_launch_norm(int norm_mode, dim3 grid, int threads, hipStream_t s
   }
 }
 
+// ---- the launch plan ------------------------------------------------------------------------------------------
+// Everything odet_roi_pool_batch decides about a launch, from the shapes alone (host; the diagnostic build records it,
+// include/odet_diag.h).  The element type, the pooling and the normalisation pick the kernel instantiation, not the plan.
+struct RoiPlan {
+  int B, C, n, P, f16, pool_mode, norm_mode;
+  int waves;          // RoiParams::waves ... xcds_per_img: as the kernel reads them
+  int slices, roi_groups, rois_per_xcd, blocks_per_xcd, nblocks, xcd_images, xcds_per_img;
+  int grid_x, grid_y, threads;
+};
+
+static int roi_plan(int B, int C, int n, int pool_size, int f16, int pool_mode, int norm_mode, RoiPlan* out) {
+  RoiPlan p;
+  p.B = B; p.C = C; p.n = n; p.P = pool_size; p.f16 = f16 ? 1 : 0; p.pool_mode = pool_mode; p.norm_mode = norm_mode;
+  // one wave per output row; a workgroup = the P rows of one RoI (8 rows of whatever RoIs when P > 16)
+  p.waves = pool_size <= 16 ? pool_size : 8;
+  const int64_t rows = (int64_t)n * pool_size;
+  // a launch of a few hundred RoIs over 512 / 1024-channel maps (the C4 and VGG16 detectors: 300 RoIs) would leave
+  // most CUs with one workgroup: split every RoI's channels over C / 256 workgroups
+  p.slices = (p.waves == pool_size && (C & 255) == 0 && C > 256) ? C / 256 : 1;
+  const int64_t blocks = p.slices > 1 ? (int64_t)n * p.slices : (rows + p.waves - 1) / p.waves;
+  ODET_REQUIRE(blocks < (1ll << 30), "odet_roi_pool: too many workgroups");
+  p.nblocks = (int)blocks;
+  p.xcd_images = (B == 2 || B == 4 || B == 8) ? 1 : 0;
+  p.xcds_per_img = p.xcd_images ? 8 / B : 8;
+  p.blocks_per_xcd = (p.nblocks + p.xcds_per_img - 1) / p.xcds_per_img;   // per XCD of an image
+  p.rois_per_xcd = 0;
+  p.roi_groups = 0;
+  if (p.slices > 1) {
+    if (p.xcds_per_img % p.slices == 0) {                 // an XCD = one slice of one part of the RoIs
+      p.roi_groups = p.xcds_per_img / p.slices;
+      p.rois_per_xcd = (n + p.roi_groups - 1) / p.roi_groups;
+      p.blocks_per_xcd = p.rois_per_xcd;
+    } else {                                              // an XCD = all slices of its RoIs, slice-major
+      p.rois_per_xcd = (n + p.xcds_per_img - 1) / p.xcds_per_img;
+      p.blocks_per_xcd = p.rois_per_xcd * p.slices;
+    }
+    p.nblocks = p.blocks_per_xcd * p.xcds_per_img;        // (slots beyond the last RoI leave at `ri >= n`)
+  }
+  p.grid_x = p.blocks_per_xcd * 8;
+  p.grid_y = p.xcd_images ? 1 : B;
+  p.threads = p.waves * 64;
+  *out = p;
+  return ODET_OK;
+}
+
+#ifdef ODET_DIAG
+// Diagnostic build only (include/odet_diag.h): the plan of the latest RoI launch, written just before it is launched, and the
+// plan-only mode of csrc/conv_diag.h (the switch lives in conv3x3.hip).  The shipped library has neither.
+static std::mutex g_roi_plan_mutex;
+static odet_debug_roi_plan_t g_last_roi_plan;
+static void roi_plan_to_record(const RoiPlan& p, odet_debug_roi_plan_t* r, long long count) {
+  *r = odet_debug_roi_plan_t{p.B, p.C, p.n, p.P, p.f16, p.pool_mode, p.norm_mode, p.waves, p.slices, p.roi_groups,
+                             p.rois_per_xcd, p.blocks_per_xcd, p.nblocks, p.xcd_images, p.xcds_per_img, p.grid_x,
+                             p.grid_y, p.threads, count};
+}
+static void roi_diag_record(const RoiPlan& p) {
+  std::lock_guard<std::mutex> lock(g_roi_plan_mutex);
+  roi_plan_to_record(p, &g_last_roi_plan, g_last_roi_plan.count + 1);
+}
+extern "C" int odet_debug_last_roi_plan(odet_debug_roi_plan_t* out) {
+  ODET_REQUIRE(out, "odet_debug_last_roi_plan: null record");
+  std::lock_guard<std::mutex> lock(g_roi_plan_mutex);
+  *out = g_last_roi_plan;       // (count == 0, everything else zero: nothing launched yet)
+  return ODET_OK;
+}
+extern "C" int odet_debug_roi_plan(int B, int C, int n, int pool_size, int f16, int pool_mode, int norm_mode,
+                                   odet_debug_roi_plan_t* out) {
+  ODET_REQUIRE(out && B >= 1 && B <= ODET_MAX_BATCH && n > 0 && C > 0 && pool_size > 0 && pool_size <= 64,
+               "odet_debug_roi_plan: bad arguments");
+  RoiPlan p;
+  const int rc = roi_plan(B, C, n, pool_size, f16, pool_mode, norm_mode, &p);
+  if (rc == ODET_OK) roi_plan_to_record(p, out, 0);
+  return rc;
+}
+#define ODET_DIAG_ROI_PLAN(plan)              \
+  do {                                        \
+    roi_diag_record(plan);                    \
+    if (odet_diag_plan_only()) return ODET_OK; \
+  } while (0)
+#else
+#define ODET_DIAG_ROI_PLAN(plan) \
+  do {                           \
+  } while (0)
+#endif
+
 // B images in one launch; all images share shapes and parameters
 int odet_roi_pool_batch(const RoiImageIO* io, int B, int num_levels, int C, int n, int norm_mode, int image_h,
                         int image_w, int pool_size, int pool_mode, hipStream_t st, RoiEvents ev, int f16) {
@@ -731,33 +819,15 @@ int odet_roi_pool_batch(const RoiImageIO* io, int B, int num_levels, int C, int 
   p.num_levels = num_levels;
   p.C = C; p.n = n; p.P = pool_size;
   p.image_h = (float)image_h; p.image_w = (float)image_w;
-  // one wave per output row; a workgroup = the P rows of one RoI (8 rows of whatever RoIs when P > 16)
-  p.waves = pool_size <= 16 ? pool_size : 8;
-  const int64_t rows = (int64_t)n * pool_size;
-  // a launch of a few hundred RoIs over 512 / 1024-channel maps (the C4 and VGG16 detectors: 300 RoIs) would leave
-  // most CUs with one workgroup: split every RoI's channels over C / 256 workgroups
-  p.slices = (p.waves == pool_size && (C & 255) == 0 && C > 256) ? C / 256 : 1;
-  const int64_t blocks = p.slices > 1 ? (int64_t)n * p.slices : (rows + p.waves - 1) / p.waves;
-  ODET_REQUIRE(blocks < (1ll << 30), "odet_roi_pool: too many workgroups");
-  p.nblocks = (int)blocks;
-  p.xcd_images = (B == 2 || B == 4 || B == 8) ? 1 : 0;
-  p.xcds_per_img = p.xcd_images ? 8 / B : 8;
-  p.blocks_per_xcd = (p.nblocks + p.xcds_per_img - 1) / p.xcds_per_img;   // per XCD of an image
-  p.rois_per_xcd = 0;
-  p.roi_groups = 0;
-  if (p.slices > 1) {
-    if (p.xcds_per_img % p.slices == 0) {                 // an XCD = one slice of one part of the RoIs
-      p.roi_groups = p.xcds_per_img / p.slices;
-      p.rois_per_xcd = (n + p.roi_groups - 1) / p.roi_groups;
-      p.blocks_per_xcd = p.rois_per_xcd;
-    } else {                                              // an XCD = all slices of its RoIs, slice-major
-      p.rois_per_xcd = (n + p.xcds_per_img - 1) / p.xcds_per_img;
-      p.blocks_per_xcd = p.rois_per_xcd * p.slices;
-    }
-    p.nblocks = p.blocks_per_xcd * p.xcds_per_img;        // (slots beyond the last RoI leave at `ri >= n`)
-  }
-  dim3 grid(p.blocks_per_xcd * 8, p.xcd_images ? 1 : B);
-  const int threads = p.waves * 64;
+  RoiPlan plan;
+  const int prc = roi_plan(B, C, n, pool_size, f16, pool_mode, norm_mode, &plan);
+  if (prc != ODET_OK) return prc;
+  p.waves = plan.waves; p.slices = plan.slices; p.roi_groups = plan.roi_groups; p.rois_per_xcd = plan.rois_per_xcd;
+  p.blocks_per_xcd = plan.blocks_per_xcd; p.nblocks = plan.nblocks; p.xcd_images = plan.xcd_images;
+  p.xcds_per_img = plan.xcds_per_img;
+  ODET_DIAG_ROI_PLAN(plan);
+  const dim3 grid(plan.grid_x, plan.grid_y);
+  const int threads = plan.threads;
   if (pool_mode == ODET_ROI_POOL_NONE) roi_launch_norm<ODET_ROI_POOL_NONE>(norm_mode, grid, threads, st, p, ev, f16);
   else if (pool_mode == ODET_ROI_POOL_MAX2) roi_launch_norm<ODET_ROI_POOL_MAX2>(norm_mode, grid, threads, st, p, ev, f16);
   else roi_launch_norm<ODET_ROI_POOL_AVG2>(norm_mode, grid, threads, st, p, ev, f16);

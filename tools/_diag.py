@@ -62,9 +62,18 @@ class DebugPlan(_lib.C.Structure):
                [('blocks', _lib.C.c_longlong), ('count', _lib.C.c_longlong)]
 
 
+ROI_PLAN_FIELDS = ('B', 'C', 'n', 'P', 'f16', 'pool_mode', 'norm_mode', 'waves', 'slices', 'roi_groups', 'rois_per_xcd',
+                   'blocks_per_xcd', 'nblocks', 'xcd_images', 'xcds_per_img', 'grid_x', 'grid_y', 'threads')
+
+
 class DebugTile(_lib.C.Structure):
     """odet_debug_tile_t"""
     _fields_ = [(n, _lib.C.c_int) for n in ('nw', 'wn', 'mt', 'ns', 'limbs', 'forms')]
+
+
+class DebugRoiPlan(_lib.C.Structure):
+    """odet_debug_roi_plan_t"""
+    _fields_ = [(n, _lib.C.c_int) for n in ROI_PLAN_FIELDS] + [('count', _lib.C.c_longlong)]
 
 
 FAMILY_F16, FAMILY_F32, FAMILY_SPLIT = 0, 1, 2
@@ -78,6 +87,8 @@ DIAG_SIGNATURES = {
     'odet_debug_last_plan': (_lib._i, [_lib._i, _lib.C.POINTER(DebugPlan)]),
     'odet_debug_tile_table': (_lib._i, [_lib._i, _lib._i, _lib.C.POINTER(DebugTile)]),
     'odet_debug_plan_only': (_lib._i, [_lib._i]),
+    'odet_debug_last_roi_plan': (_lib._i, [_lib.C.POINTER(DebugRoiPlan)]),
+    'odet_debug_roi_plan': (_lib._i, [_lib._i] * 7 + [_lib.C.POINTER(DebugRoiPlan)]),
     'odet_debug_cvt_f16': (_lib._i, [_lib._vp, _lib._vp, _lib._vp, _lib.C.c_longlong, _lib._vp]),
     'odet_debug_tg_key_mask': (_lib._i, [_lib.C.c_ulonglong]),
 }
@@ -112,6 +123,22 @@ def last_plan(family, handle=None):
     _lib.check(h.odet_debug_last_plan(fam, _lib.C.byref(p)))
     return {'family': FAMILIES[p.family], 'form': FORMS[p.form], 'tile': (p.nw, p.wn, p.mt, p.ns), 'limbs': p.limbs,
             'ksplit': p.ksplit, 'forced': bool(p.forced), 'blocks': p.blocks, 'count': p.count}
+
+
+def last_roi_plan(handle=None):
+    """the latest RoI launch (csrc/roi.hip) as a dict of odet_debug_roi_plan_t's fields; 'count' is 0 before the first one"""
+    h = handle or diag_handle()
+    p = DebugRoiPlan()
+    _lib.check(h.odet_debug_last_roi_plan(_lib.C.byref(p)))
+    return dict([(n, getattr(p, n)) for n in ROI_PLAN_FIELDS] + [('count', p.count)])
+
+
+def roi_plan(B, C, n, P, f16=0, pool_mode=0, norm_mode=0, handle=None):
+    """what the RoI launcher plans for B images of n RoIs each (the planning function alone: no launch, no record)"""
+    h = handle or diag_handle()
+    p = DebugRoiPlan()
+    _lib.check(h.odet_debug_roi_plan(B, C, n, P, int(f16), int(pool_mode), int(norm_mode), _lib.C.byref(p)))
+    return {n_: getattr(p, n_) for n_ in ROI_PLAN_FIELDS}
 
 
 def tile_table(family, handle=None):
