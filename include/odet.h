@@ -38,7 +38,8 @@ extern "C" {
  * separate -DODET_DIAG build).  Added within 103: odet_preprocess_images (the eval loaders' input front end),
  * odet_eval_detect_topk, the odet_coco_* evaluation, the odet_voc_* evaluation and the fused training targets
  * (odet_anchor_target, odet_proposal_target) and the fused training losses with their gradients (odet_rpn_loss,
- * odet_rpn_loss_backward, odet_roi_loss); no existing entry point or struct changed. */
+ * odet_rpn_loss_backward, odet_roi_loss) and odet_preprocess_train (the training input stage); no existing entry point or
+ * struct changed. */
 #define ODET_VERSION 103
 
 #define ODET_OK 0
@@ -506,6 +507,53 @@ int odet_preprocess_images(const void* const* images, const int* raw_h, const in
                            int B, int H, int W, int pipeline, int preprocessing, int rgb, const double* means, void* out,
                            int f16, odet_stream_t stream);
 
+/* ---- training input front end (added within 103) -------------------------------------- */
+
+#define ODET_PREP_MAX_BOXES 1024     /* ground-truth boxes per image (the fused targets' limit) */
+/* The reference's TRAINING input stage for a batch: decoded uint8 RGB HWC images + normalised boxes -> exactly what
+ * odet_anchor_target / odet_proposal_target take, in ONE launch (H row workgroups per image as odet_preprocess_images, plus
+ * one workgroup per image for its boxes); no allocation, no host read.  The reference parts:
+ *   image_argument_with_imgaug with the default iaa.Fliplr(0.5)   dataset/utils/tf_dataset_utils.py:10-52
+ *   preprocessing_training_func                                   dataset/utils/tf_dataset_utils.py:55-80, 83-126
+ *     (called from dataset/pascal_tf_dataset_generator.py:83-98 and dataset/coco_tf_dataset_generator.py:187-200)
+ *   the column swap of train_one_epoch                            scripts/train.py:84-96
+ * images, raw_h, raw_w, row_pitch, H, W, preprocessing, means, out, f16: as odet_preprocess_images with
+ * pipeline = ODET_PREP_COCO (the same float32 rule, :109-117), whose limits and argument errors apply.
+ *
+ * Flip.  augment = 1 and flip == NULL: image b is mirrored iff w0 >> 31 == 1, w0 the first word of
+ * philox((0, image_id, 5, 0), (seed low word, seed high word)), image_id = first_image_id + b (mod 2^32): stream 5 of the
+ * sampling rule under "training targets" below, a function of (seed, image_id) alone.  flip (HOST int[B], each 0 or 1)
+ * overrides the rule (tests, replaying a recorded epoch).  augment = 0 (the reference's argument=False): no flip, no
+ * truncation.  The decision is taken on the HOST and travels in the kernel's parameters: the call captures into a graph,
+ * and a replay repeats the flags of the capturing call.  flipped (HOST int[B], nullable) receives them.
+ * Image.  A mirrored image is the raw uint8 image with its columns reversed (image[:, ::-1]), BEFORE normalisation and
+ * resize: TF 1.x resize_bilinear is not mirror-symmetric, the other order gives other pixels.
+ * Boxes.  boxes_yxyx: device float32 [sum G, 4] rows (ymin, xmin, ymax, xmax) in [0, 1] units of the raw h x w image, finite
+ * (the reference's int() raises on anything else; here such a value is clamped to +-2^62 before the truncation); gt_offsets:
+ * HOST int [B + 1], image b owns rows gt_offsets[b] .. gt_offsets[b + 1]; G = 0 is legal.  With augment = 1, EVERY image,
+ * mirrored or not (:30-33, :47-52):
+ *   iy1 = int(float64(ymin) * h), likewise ix1 (* w), iy2, ix2: a float64 product truncated toward zero (the reference's
+ *     numpy promotes float32 scalar * int to float64: float32(0.7) * 10 truncates to 6, not to 7);
+ *   ix1 > ix2 are swapped, likewise y (imgaug's BoundingBox constructor);
+ *   mirrored: (ix1, ix2) -> (w - ix2, w - ix1) -- imgaug's x' = width - x on both corners, the rule of imgaug 0.2.8 and
+ *     later.  UNPINNED: imgaug was not at hand when this was written, the rule is taken from its source as remembered; there
+ *     is no switch for the older width - 1 - x;
+ *   float64(i) / float64(size), clipped to [0, 1], rounded once to float32.
+ * With augment = 0 the input values are taken as they are.  Then, in float32: y * float32(H - 1), x * float32(W - 1)
+ * (:119-124), written x first: gt_boxes_xyxy device [sum G, 4] rows (xmin, ymin, xmax, ymax) (train.py:89-93).
+ * gt_offsets_dev: device int32 [B + 1], written by the kernel from its parameters (no separate copy).  Labels need no
+ * kernel (tf.to_int32, train.py:96).
+ * B == 0 is a no-op.  Errors: those of odet_preprocess_images; ODET_E_INVALID for augment outside {0, 1}, flip given with
+ * augment = 0 or holding anything but 0 / 1, offsets that do not start at 0 or that decrease, a null pointer;
+ * ODET_E_LIMIT for an image with more than ODET_PREP_MAX_BOXES boxes (refused on the host: the offsets are host values). */
+int odet_preprocess_train(const void* const* images, const int* raw_h, const int* raw_w, const long long* row_pitch,
+                          int B, int H, int W, int preprocessing, const double* means,
+                          const float* boxes_yxyx /* device [sum G,4] */, const int* gt_offsets /* HOST [B+1] */,
+                          int augment, const int* flip /* HOST [B], nullable */, uint64_t seed, uint32_t first_image_id,
+                          void* out, int f16, float* gt_boxes_xyxy /* device [sum G,4] */,
+                          int32_t* gt_offsets_dev /* device [B+1] */, int* flipped /* HOST [B], out, nullable */,
+                          odet_stream_t stream);
+
 /* ---- FPN neck: top-down merge -------------------------------------- */
 
 /* model/fpn/resnet_fpn.py:385-398 (ResnetFpnNeck.call): P_k = Add([resize_bilinear(P_{k+1},
@@ -881,7 +929,7 @@ const char* odet_exec_last_error(odet_exec_t* ex);
  * random k-subset like the reference's shuffle-and-slice, and a function of (seed, image_id, i) alone.  Streams: 0 anchor
  * foreground, 1 anchor background, 2 RoI foreground, 3 RoI background; i = index into ALL anchors resp. the RoI's row.
  * With replacement (proposal_target.py:73-76): draw j picks bg_ascending[(uint64(w0) * n_bg) >> 32], w0 of
- * philox((j, image_id, 4, 0), seed). */
+ * philox((j, image_id, 4, 0), seed).  Stream 5 is the flip decision of odet_preprocess_train (i = 0). */
 
 size_t odet_anchor_target_workspace_bytes(int num_anchors, int batch, int total_num_samples);
 /* anchors [num_anchors,4] shared by the batch (one image shape).  In the reference's order: inside = bboxes_range_filter;

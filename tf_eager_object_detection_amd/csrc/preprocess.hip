@@ -12,6 +12,11 @@
 // row with 16-byte stores; the (at most V - 1) elements before the first and after the last 16-byte boundary of the row are
 // single stores.  The launch is bound by its output writes (12 or 6 bytes per output pixel against <= 4 staged source bytes
 // per output pixel at the flagship sizes).
+//
+// Training input front end (odet_preprocess_train): the same row workgroups, with the horizontal flip of
+// image_argument_with_imgaug (dataset/utils/tf_dataset_utils.py:16-52, iaa.Fliplr) folded into the LDS staging -- source
+// column x lands at w - 1 - x, BEFORE normalisation and resize, as the reference orders them -- plus one more workgroup per
+// image (blockIdx.x == H) for its ground-truth boxes and its row of the offsets.
 #include <hip/hip_fp16.h>
 
 #include "odet_internal.h"
@@ -108,10 +113,9 @@ __device__ __forceinline__ float prep_value(const PrepRow& r, int e) {
   return h0 * r.b0 + h1 * r.b1;
 }
 
-template <typename T>
-__global__ void __launch_bounds__(PREP_THREADS) k_preprocess(PrepParams p) {
-  extern __shared__ float prep_lds[];
-  const int dy = blockIdx.x, b = blockIdx.y;
+// One output row of one image.  flip (the training launch only) mirrors the source columns while they are staged.
+template <typename T, bool TRAIN>
+__device__ __forceinline__ void prep_row(const PrepParams& p, float* prep_lds, int dy, int b, bool flip) {
   const int h = p.h[b], w = p.w[b];
   const int H = p.H, W = p.W;
   PrepRow r;
@@ -192,7 +196,7 @@ __global__ void __launch_bounds__(PREP_THREADS) k_preprocess(PrepParams p) {
         const int x = j / 3;
         const int sc = j - 3 * x;
         const int c = p.src_ch[sc];      // (src_ch is the identity or the reversal: its own inverse)
-        L[3 * x + c] = prep_norm(p, (q[r][i >> 2] >> (8 * (i & 3))) & 255u, c);
+        L[3 * ((TRAIN && flip) ? w - 1 - x : x) + c] = prep_norm(p, (q[r][i >> 2] >> (8 * (i & 3))) & 255u, c);
       }
     }
   }
@@ -219,6 +223,81 @@ __global__ void __launch_bounds__(PREP_THREADS) k_preprocess(PrepParams p) {
   if (t >= 64 && t - 64 < n - tail) PrepOut<T>::put1(row + tail + (t - 64), prep_value(r, tail + (t - 64)));
 }
 
+template <typename T>
+__global__ void __launch_bounds__(PREP_THREADS) k_preprocess(PrepParams p) {
+  extern __shared__ float prep_lds[];
+  prep_row<T, false>(p, prep_lds, blockIdx.x, blockIdx.y, false);
+}
+
+// ---- training: the boxes of image_argument_with_imgaug + preprocessing_training_func + train_one_epoch ------------------
+struct PrepTrain {
+  unsigned long long flip_mask;           // bit b: image b is mirrored (decided on the host: baked into a captured graph)
+  int augment;
+  int32_t gt_off[ODET_PREP_MAX_BATCH + 1];
+  const float* boxes_in;                  // [sum G, 4] (ymin, xmin, ymax, xmax), normalised to the raw image
+  float* boxes_out;                       // [sum G, 4] (xmin, ymin, xmax, ymax), pixels of the resized image
+  int32_t* off_out;                       // [B + 1]
+};
+
+// int(bbox[k] * size) (tf_dataset_utils.py:31-32): the float32 scalar times a Python int is a float64 product, truncated
+// toward zero.  (Python's int is unbounded; the clamp keeps the conversion defined, and everything that far out clips.)
+__device__ __forceinline__ long long prep_trunc(float v, int size) {
+  const double lim = 4611686018427387904.0;   // 2^62
+  const double d = (double)v * (double)size;
+  return (long long)fmin(fmax(d, -lim), lim);
+}
+// iaa_bbox.y1 / height in float64, clipped to [0, 1], .astype(np.float32) (:48-52)
+__device__ __forceinline__ float prep_unit(long long i, int size) {
+  double q = (double)i / (double)size;
+  q = q < 0.0 ? 0.0 : q;
+  q = q > 1.0 ? 1.0 : q;
+  return (float)q;
+}
+
+__device__ __forceinline__ void prep_boxes(const PrepParams& p, const PrepTrain& t, int b, bool flip) {
+  const int lo = t.gt_off[b], hi = t.gt_off[b + 1];
+  if (threadIdx.x == 0) {
+    t.off_out[b] = lo;
+    if (b == (int)gridDim.y - 1) t.off_out[b + 1] = hi;
+  }
+  const int h = p.h[b], w = p.w[b];
+  const float sy = (float)(p.H - 1), sx = (float)(p.W - 1);      // tf.to_float(n_height - 1), (n_width - 1) (:120-123)
+  for (int g = lo + (int)threadIdx.x; g < hi; g += PREP_THREADS) {
+    const float* in = t.boxes_in + 4ll * g;
+    float y1 = in[0], x1 = in[1], y2 = in[2], x2 = in[3];
+    if (t.augment) {
+      long long iy1 = prep_trunc(y1, h), ix1 = prep_trunc(x1, w), iy2 = prep_trunc(y2, h), ix2 = prep_trunc(x2, w);
+      if (ix1 > ix2) { const long long s = ix1; ix1 = ix2; ix2 = s; }      // ia.BoundingBox.__init__
+      if (iy1 > iy2) { const long long s = iy1; iy1 = iy2; iy2 = s; }
+      if (flip) {                                                           // Fliplr: x' = width - x on both corners
+        const long long a = (long long)w - ix2, c = (long long)w - ix1;
+        ix1 = a;
+        ix2 = c;
+      }
+      y1 = prep_unit(iy1, h);
+      x1 = prep_unit(ix1, w);
+      y2 = prep_unit(iy2, h);
+      x2 = prep_unit(ix2, w);
+    }
+    float* o = t.boxes_out + 4ll * g;
+    o[0] = x1 * sx;                                                         // x first: scripts/train.py:89-93
+    o[1] = y1 * sy;
+    o[2] = x2 * sx;
+    o[3] = y2 * sy;
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(PREP_THREADS) k_preprocess_train(PrepParams p, PrepTrain t) {
+  extern __shared__ float prep_lds[];
+  const int b = blockIdx.y;
+  const bool flip = (t.flip_mask >> b) & 1ull;
+  if ((int)blockIdx.x == p.H)
+    prep_boxes(p, t, b, flip);
+  else
+    prep_row<T, true>(p, prep_lds, blockIdx.x, b, flip);
+}
+
 static const unsigned PREP_LDS_MAX = 2u * 3u * ODET_PREP_MAX_RAW_W * 4u;
 
 static hipError_t prep_prepare_kernels() {
@@ -227,40 +306,48 @@ static hipError_t prep_prepare_kernels() {
     hipError_t e = hipFuncSetAttribute((const void*)k_preprocess<float>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                        PREP_LDS_MAX);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)k_preprocess<__half>, hipFuncAttributeMaxDynamicSharedMemorySize, PREP_LDS_MAX);
+    e = hipFuncSetAttribute((const void*)k_preprocess<__half>, hipFuncAttributeMaxDynamicSharedMemorySize, PREP_LDS_MAX);
+    if (e != hipSuccess) return e;
+    e = hipFuncSetAttribute((const void*)k_preprocess_train<float>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            PREP_LDS_MAX);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute((const void*)k_preprocess_train<__half>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               PREP_LDS_MAX);
   });
 }
 
-extern "C" int odet_preprocess_images(const void* const* images, const int* raw_h, const int* raw_w,
-                                      const long long* row_pitch, int B, int H, int W, int pipeline, int preprocessing,
-                                      int rgb, const double* means, void* out, int f16, odet_stream_t stream) {
-  ODET_REQUIRE(B >= 0, "odet_preprocess_images: negative batch %d", B);
-  if (B > ODET_PREP_MAX_BATCH)
-    return odet_set_error(ODET_E_LIMIT, "odet_preprocess_images: batch %d exceeds %d", B, ODET_PREP_MAX_BATCH);
-  ODET_REQUIRE(H > 0 && W > 0, "odet_preprocess_images: non-positive output size %d x %d", H, W);
+// The argument checks and the parameter block both entry points share.  *empty = 1: B == 0, nothing to launch.
+static int prep_setup(const char* who, const void* const* images, const int* raw_h, const int* raw_w,
+                      const long long* row_pitch, int B, int H, int W, int pipeline, int preprocessing, int rgb,
+                      const double* means, void* out, int f16, PrepParams* pp, int* max_w_out, int* empty) {
+  PrepParams& p = *pp;
+  *empty = 0;
+  ODET_REQUIRE(B >= 0, "%s: negative batch %d", who, B);
+  if (B > ODET_PREP_MAX_BATCH) return odet_set_error(ODET_E_LIMIT, "%s: batch %d exceeds %d", who, B, ODET_PREP_MAX_BATCH);
+  ODET_REQUIRE(H > 0 && W > 0, "%s: non-positive output size %d x %d", who, H, W);
   if (H > ODET_PREP_MAX_OUT || W > ODET_PREP_MAX_OUT)
-    return odet_set_error(ODET_E_LIMIT, "odet_preprocess_images: output size %d x %d exceeds %d", H, W, ODET_PREP_MAX_OUT);
-  ODET_REQUIRE(pipeline == ODET_PREP_VOC || pipeline == ODET_PREP_COCO, "odet_preprocess_images: unknown pipeline %d",
-               pipeline);
-  ODET_REQUIRE(preprocessing == ODET_PREP_CAFFE || preprocessing == ODET_PREP_TF,
-               "odet_preprocess_images: unknown preprocessing %d", preprocessing);
+    return odet_set_error(ODET_E_LIMIT, "%s: output size %d x %d exceeds %d", who, H, W, ODET_PREP_MAX_OUT);
+  ODET_REQUIRE(pipeline == ODET_PREP_VOC || pipeline == ODET_PREP_COCO, "%s: unknown pipeline %d", who, pipeline);
+  ODET_REQUIRE(preprocessing == ODET_PREP_CAFFE || preprocessing == ODET_PREP_TF, "%s: unknown preprocessing %d", who,
+               preprocessing);
   ODET_REQUIRE(rgb == 0 || (rgb == 1 && pipeline == ODET_PREP_VOC),
-               "odet_preprocess_images: rgb must be 0 or 1, and 1 only for the voc pipeline");
-  ODET_REQUIRE(f16 == 0 || f16 == 1, "odet_preprocess_images: f16 must be 0 or 1");
-  if (B == 0) return ODET_OK;
-  ODET_REQUIRE(images && raw_h && raw_w && row_pitch && out, "odet_preprocess_images: null pointer");
-  ODET_REQUIRE(means || preprocessing == ODET_PREP_TF, "odet_preprocess_images: null pointer (means)");
-  ODET_REQUIRE(((uintptr_t)out & 15) == 0, "odet_preprocess_images: out must be 16-byte aligned");
-  PrepParams p;
+               "%s: rgb must be 0 or 1, and 1 only for the voc pipeline", who);
+  ODET_REQUIRE(f16 == 0 || f16 == 1, "%s: f16 must be 0 or 1", who);
+  if (B == 0) {
+    *empty = 1;
+    return ODET_OK;
+  }
+  ODET_REQUIRE(images && raw_h && raw_w && row_pitch && out, "%s: null pointer", who);
+  ODET_REQUIRE(means || preprocessing == ODET_PREP_TF, "%s: null pointer (means)", who);
+  ODET_REQUIRE(((uintptr_t)out & 15) == 0, "%s: out must be 16-byte aligned", who);
   int max_w = 0;
   for (int i = 0; i < B; ++i) {
-    ODET_REQUIRE(images[i], "odet_preprocess_images: null pointer (image %d)", i);
-    ODET_REQUIRE(raw_h[i] > 0 && raw_w[i] > 0, "odet_preprocess_images: image %d has size %d x %d", i, raw_h[i], raw_w[i]);
+    ODET_REQUIRE(images[i], "%s: null pointer (image %d)", who, i);
+    ODET_REQUIRE(raw_h[i] > 0 && raw_w[i] > 0, "%s: image %d has size %d x %d", who, i, raw_h[i], raw_w[i]);
     if (raw_w[i] > ODET_PREP_MAX_RAW_W || raw_h[i] > ODET_PREP_MAX_RAW_H)
-      return odet_set_error(ODET_E_LIMIT, "odet_preprocess_images: image %d (%d x %d) exceeds %d x %d", i, raw_h[i],
-                            raw_w[i], ODET_PREP_MAX_RAW_H, ODET_PREP_MAX_RAW_W);
-    ODET_REQUIRE(row_pitch[i] >= 3ll * raw_w[i], "odet_preprocess_images: image %d row pitch %lld < 3 * %d", i,
-                 row_pitch[i], raw_w[i]);
+      return odet_set_error(ODET_E_LIMIT, "%s: image %d (%d x %d) exceeds %d x %d", who, i, raw_h[i], raw_w[i],
+                            ODET_PREP_MAX_RAW_H, ODET_PREP_MAX_RAW_W);
+    ODET_REQUIRE(row_pitch[i] >= 3ll * raw_w[i], "%s: image %d row pitch %lld < 3 * %d", who, i, row_pitch[i], raw_w[i]);
     p.src[i] = (const uint8_t*)images[i];
     p.pitch[i] = row_pitch[i];
     p.h[i] = raw_h[i];
@@ -280,12 +367,78 @@ extern "C" int odet_preprocess_images(const void* const* images, const int* raw_
     p.mean_f[c] = (float)m;
   }
   p.out = out;
+  *max_w_out = max_w;
+  return ODET_OK;
+}
+
+extern "C" int odet_preprocess_images(const void* const* images, const int* raw_h, const int* raw_w,
+                                      const long long* row_pitch, int B, int H, int W, int pipeline, int preprocessing,
+                                      int rgb, const double* means, void* out, int f16, odet_stream_t stream) {
+  PrepParams p;
+  int max_w = 0, empty = 0;
+  const int rc = prep_setup("odet_preprocess_images", images, raw_h, raw_w, row_pitch, B, H, W, pipeline, preprocessing, rgb,
+                            means, out, f16, &p, &max_w, &empty);
+  if (rc != ODET_OK || empty) return rc;
   ODET_HIP(prep_prepare_kernels());
   const size_t lds = (size_t)2 * 3 * max_w * sizeof(float);
   if (f16)
     hipLaunchKernelGGL(k_preprocess<__half>, dim3(H, B), dim3(PREP_THREADS), lds, (hipStream_t)stream, p);
   else
     hipLaunchKernelGGL(k_preprocess<float>, dim3(H, B), dim3(PREP_THREADS), lds, (hipStream_t)stream, p);
+  ODET_LAUNCH_CHECK();
+  return ODET_OK;
+}
+
+extern "C" int odet_preprocess_train(const void* const* images, const int* raw_h, const int* raw_w,
+                                     const long long* row_pitch, int B, int H, int W, int preprocessing,
+                                     const double* means, const float* boxes_yxyx, const int* gt_offsets, int augment,
+                                     const int* flip, uint64_t seed, uint32_t first_image_id, void* out, int f16,
+                                     float* gt_boxes_xyxy, int32_t* gt_offsets_dev, int* flipped, odet_stream_t stream) {
+  static const char* who = "odet_preprocess_train";
+  ODET_REQUIRE(augment == 0 || augment == 1, "%s: augment must be 0 or 1", who);
+  ODET_REQUIRE(!flip || augment == 1, "%s: flip flags given with augment = 0", who);
+  PrepParams p;
+  int max_w = 0, empty = 0;
+  const int rc = prep_setup(who, images, raw_h, raw_w, row_pitch, B, H, W, ODET_PREP_COCO, preprocessing, 0, means, out, f16,
+                            &p, &max_w, &empty);
+  if (rc != ODET_OK || empty) return rc;
+  ODET_REQUIRE(gt_offsets && gt_offsets_dev, "%s: null pointer (gt_offsets)", who);
+  ODET_REQUIRE(gt_offsets[0] == 0, "%s: gt_offsets[0] = %d, must be 0", who, gt_offsets[0]);
+  PrepTrain t;
+  t.flip_mask = 0ull;
+  t.augment = augment;
+  t.gt_off[0] = 0;
+  for (int i = 0; i < B; ++i) {
+    const int g = gt_offsets[i + 1] - gt_offsets[i];
+    ODET_REQUIRE(gt_offsets[i + 1] >= gt_offsets[i], "%s: gt_offsets decrease at image %d (%d -> %d)", who, i, gt_offsets[i],
+                 gt_offsets[i + 1]);
+    if (g > ODET_PREP_MAX_BOXES)
+      return odet_set_error(ODET_E_LIMIT, "%s: image %d has %d boxes, exceeds %d", who, i, g, ODET_PREP_MAX_BOXES);
+    t.gt_off[i + 1] = gt_offsets[i + 1];
+    int f = 0;
+    if (flip) {
+      ODET_REQUIRE(flip[i] == 0 || flip[i] == 1, "%s: flip[%d] = %d, must be 0 or 1", who, i, flip[i]);
+      f = flip[i];
+    } else if (augment) {                  // stream 5 of the sampling rule (include/odet.h "training targets")
+      uint32_t w0, w1;
+      odet_philox2(0u, first_image_id + (uint32_t)i, TG_STREAM_IMAGE_FLIP, 0u, (uint32_t)seed, (uint32_t)(seed >> 32),
+                   &w0, &w1);
+      f = (int)(w0 >> 31);
+    }
+    if (f) t.flip_mask |= 1ull << i;
+  }
+  ODET_REQUIRE(gt_offsets[B] == 0 || (boxes_yxyx && gt_boxes_xyxy), "%s: null pointer (boxes)", who);
+  if (flipped)
+    for (int i = 0; i < B; ++i) flipped[i] = (int)((t.flip_mask >> i) & 1ull);
+  t.boxes_in = boxes_yxyx;
+  t.boxes_out = gt_boxes_xyxy;
+  t.off_out = gt_offsets_dev;
+  ODET_HIP(prep_prepare_kernels());
+  const size_t lds = (size_t)2 * 3 * max_w * sizeof(float);
+  if (f16)
+    hipLaunchKernelGGL(k_preprocess_train<__half>, dim3(H + 1, B), dim3(PREP_THREADS), lds, (hipStream_t)stream, p, t);
+  else
+    hipLaunchKernelGGL(k_preprocess_train<float>, dim3(H + 1, B), dim3(PREP_THREADS), lds, (hipStream_t)stream, p, t);
   ODET_LAUNCH_CHECK();
   return ODET_OK;
 }

@@ -15,7 +15,7 @@
 #define TG_SEL_THREADS 1024
 #define TG_BINS 4096
 
-enum { TG_STREAM_ANCHOR_FG = 0, TG_STREAM_ANCHOR_BG = 1, TG_STREAM_ROI_FG = 2, TG_STREAM_ROI_BG = 3, TG_STREAM_ROI_REPLACE = 4 };
+// (the Philox streams TG_STREAM_* and the generator itself, odet_philox2: odet_internal.h, shared with preprocess.hip)
 // per-candidate class byte in the workspace
 enum { TG_FG = 1, TG_BG = 0, TG_IGNORE = -1, TG_OUTSIDE = -2 };
 
@@ -42,27 +42,14 @@ struct TgSeed { uint32_t lo, hi; };
 #endif
 struct TgThr { unsigned long long key; uint32_t idx; int32_t none; };   // selected  <=>  !none && (key64, i) <= (key, idx)
 
-// Philox4x32-10 (Salmon et al., SC'11); only the first two output words are used anywhere here.
-__device__ __forceinline__ void d_philox2(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                          uint32_t* w0, uint32_t* w1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  *w0 = c0; *w1 = c1;
-}
-
 __device__ __forceinline__ unsigned long long d_key64(uint32_t stream, uint32_t image, uint32_t i, TgSeed s) {
   uint32_t w0, w1;
-  d_philox2(i, image, stream, 0u, s.lo, s.hi, &w0, &w1);
+  odet_philox2(i, image, stream, 0u, s.lo, s.hi, &w0, &w1);
   return TG_KEY_MASK(s, ((unsigned long long)w0 << 32) | w1);
 }
 __device__ __forceinline__ uint32_t d_key_hi(uint32_t stream, uint32_t image, uint32_t i, TgSeed s) {
   uint32_t w0, w1;
-  d_philox2(i, image, stream, 0u, s.lo, s.hi, &w0, &w1);
+  odet_philox2(i, image, stream, 0u, s.lo, s.hi, &w0, &w1);
   return TG_KEY_MASK_HI(s, w0);
 }
 
@@ -546,7 +533,7 @@ __global__ void __launch_bounds__(TG_SEL_THREADS) k_pt_sample(PtArgs a) {
     __syncthreads();
     if (t < want) {
       uint32_t w0, w1;
-      d_philox2((uint32_t)t, image, TG_STREAM_ROI_REPLACE, 0u, a.seed.lo, a.seed.hi, &w0, &w1);
+      odet_philox2((uint32_t)t, image, TG_STREAM_ROI_REPLACE, 0u, a.seed.lo, a.seed.hi, &w0, &w1);
       s_keep[k_fg + t] = s_idx[(int)(((unsigned long long)w0 * (unsigned long long)n_bg) >> 32)];
     }
     __syncthreads();
