@@ -38,8 +38,9 @@ extern "C" {
  * separate -DODET_DIAG build).  Added within 103: odet_preprocess_images (the eval loaders' input front end),
  * odet_eval_detect_topk, the odet_coco_* evaluation, the odet_voc_* evaluation and the fused training targets
  * (odet_anchor_target, odet_proposal_target) and the fused training losses with their gradients (odet_rpn_loss,
- * odet_rpn_loss_backward, odet_roi_loss) and odet_preprocess_train (the training input stage); no existing entry point or
- * struct changed. */
+ * odet_rpn_loss_backward, odet_roi_loss) and odet_preprocess_train (the training input stage) and the training step
+ * (odet_opt_step, odet_l2_loss, odet_opt_partials_bytes with the odet_opt_*_t records); no existing entry point or struct
+ * changed. */
 #define ODET_VERSION 103
 
 #define ODET_OK 0
@@ -1023,6 +1024,105 @@ int odet_roi_loss(const float* scores, const float* deltas, int num_rows, int nu
                   const int32_t* final_labels, const float* targets, const float* inside, const float* outside,
                   const int32_t* counts, int total_num_samples, const int32_t* row_map, float sigma,
                   const float* upstream, float* losses, float* grad_scores, float* grad_deltas, odet_stream_t stream);
+
+/* ---- training step (added within 103) ------------------------------------------------------------------------------
+ * The other end of train_one_epoch (scripts/train.py:22-50, 101-103) for the WHOLE variable list in one update launch plus
+ * a one-workgroup finish launch: the L2 regulariser of every regularised kernel (keras regularizers.l2: tf.add_n(model.losses)),
+ * the bias-gradient doubling of train_step, tf.train.piecewise_constant on the global step, and MomentumOptimizer /
+ * AdamOptimizer.apply_gradients (TF r1.13 training_ops.cc ApplyMomentum / ApplyAdam).  No workspace beyond the caller's
+ * partials buffer, no allocation, no host read (graph-capturable), no float atomics.  The update launch only reads the state
+ * block; the finish launch, after it in stream order, is its only writer.
+ *
+ * Tables (DEVICE memory, built by the caller; the library cannot check their contents on the host, so the kernels skip what
+ * does not fit: a chunk whose tensor index or offset is out of range, a float16 variable without a master, a tensor without
+ * the slots its optimizer needs):
+ *   tensors   odet_opt_tensor_t [num_tensors], one record per variable;
+ *   grads     const void* [num_tensors], the gradient pointer column (float32, or float16 with ODET_OPT_GRAD_F16): a column of
+ *             its own so that a step whose gradients moved re-uploads 8 bytes per variable.  A NULL entry means the gradient
+ *             is None this step: the variable, its slots and its master are left untouched (its L2 loss is still computed);
+ *   chunks    odet_opt_chunk_t [num_chunks]: chunk c covers elements offset .. min(offset + ODET_OPT_CHUNK, numel) of ONE
+ *             tensor, offset a multiple of ODET_OPT_CHUNK; the chunks of tensor t are first_chunk .. first_chunk +
+ *             ceil(numel / ODET_OPT_CHUNK) - 1 in ascending offset (a tensor of 0 elements has none);
+ *   state     odet_opt_state_t: global_step (0 on the first step), the Adam beta powers (the caller initialises them to beta1,
+ *             beta2) and the schedule.
+ * Limits (ODET_E_LIMIT): num_tensors <= ODET_OPT_MAX_TENSORS, num_chunks <= ODET_OPT_MAX_CHUNKS, num_boundaries <=
+ * ODET_OPT_MAX_BOUNDARIES.  A chunk goes through 16-byte loads and stores (8-byte for float16 arrays) when every array it
+ * touches is 16-byte (8-byte) aligned, else element by element: any 4-byte (2-byte) aligned view works, with the same bits.
+ *
+ * Arithmetic.  Every operation below is ONE float32 operation, in this order, no FMA contraction; divide and sqrt are
+ * correctly rounded.  w is the float32 variable, or the float32 master of a float16 variable.
+ *   lr     = values[i], i = the number of boundaries strictly below global_step (piecewise_constant: x <= boundaries[0]
+ *            still takes values[0]);
+ *   g      = gradient (a float16 gradient is widened, exactly); if weight_decay != 0: g = g + weight_decay * (2 * w), w the
+ *            pre-update value; then g = g * grad_scale;
+ *   momentum (no Nesterov): a' = a * momentum + g;  w' = w - a' * lr;
+ *   adam:  alpha = lr * sqrt(1 - beta2_power) / (1 - beta1_power), left to right;  m' = m + (g - m) * (1 - beta1);
+ *          v' = v + (g * g - v) * (1 - beta2);  w' = w - (m' * alpha) / (sqrt(v') + epsilon);
+ *   float16 variable: the master takes w', the variable takes w' rounded to nearest-even once;
+ *   finish: global_step += 1; adam: beta1_power *= beta1, beta2_power *= beta2 (float32).
+ * L2 loss of a tensor = float32(weight_decay * float32(S)) (0 when weight_decay == 0), S the FLOAT64 sum of the float32 squares
+ * w * w of the PRE-update values in this order, a function of the tensor alone (not of its place in the table, the other
+ * tensors, the grid or the alignment).  Cut the tensor into chunks of ODET_OPT_CHUNK = 4096 elements (the last one padded with
+ * zeros).  In a chunk, element j belongs to lane (j / 4) % 256; a lane adds its 16 squares in ascending j (numpy:
+ * sq.reshape(4, 256, 4).transpose(1, 0, 2).reshape(256, 16), cumsum along the last axis).  The 64 lane sums of each of the 4
+ * waves (lanes 64 v .. 64 v + 63) are folded in halves: v = v[:32] + v[32:], then [:16] + [16:], ... down to one value; the
+ * chunk sum is wave 0 + wave 1 + wave 2 + wave 3, left to right.  Over the chunks: 64 sums, sum l adding chunks l, l + 64, ...
+ * in ascending order, then the same fold in halves of the 64.
+ * total loss = the float32 left-to-right sum of the per-tensor losses in table order (tf.add_n). */
+#define ODET_OPT_CHUNK 4096            /* elements per chunk */
+#define ODET_OPT_MAX_TENSORS 4096
+#define ODET_OPT_MAX_CHUNKS (1 << 24)  /* 2^36 elements */
+#define ODET_OPT_MAX_BOUNDARIES 16
+#define ODET_OPT_MOMENTUM 1
+#define ODET_OPT_ADAM 2
+#define ODET_OPT_VAR_F16 1             /* flags: var is float16 (master required) */
+#define ODET_OPT_GRAD_F16 2            /* flags: the gradient is float16 */
+
+typedef struct odet_opt_tensor_t {
+  void* var;            /* float32, or float16 with ODET_OPT_VAR_F16 */
+  float* slot0;         /* momentum: accum; adam: m */
+  float* slot1;         /* adam: v; momentum: unused (NULL) */
+  float* master;        /* float32 master of a float16 variable, else NULL */
+  int64_t numel;
+  float weight_decay;   /* 0 = unregularised */
+  float grad_scale;     /* 1, or 2 for a bias under learning_rate_bias_double */
+  int32_t flags;
+  int32_t first_chunk;  /* index of the tensor's first chunk in the chunk table (and in the partials buffer) */
+  int64_t reserved;     /* 0 */
+} odet_opt_tensor_t;    /* 64 bytes */
+
+typedef struct odet_opt_chunk_t {
+  int64_t offset;       /* first element, a multiple of ODET_OPT_CHUNK */
+  int32_t tensor;
+  int32_t reserved;     /* 0 */
+} odet_opt_chunk_t;     /* 16 bytes */
+
+typedef struct odet_opt_state_t {
+  int64_t global_step;
+  float beta1_power, beta2_power;
+  int64_t boundaries[ODET_OPT_MAX_BOUNDARIES];
+  float values[ODET_OPT_MAX_BOUNDARIES + 1];
+  float reserved;       /* 0 */
+} odet_opt_state_t;     /* 216 bytes */
+
+typedef struct odet_opt_config_t {   /* HOST */
+  int32_t kind;         /* ODET_OPT_MOMENTUM / ODET_OPT_ADAM (odet_l2_loss ignores it) */
+  int32_t num_tensors, num_chunks, num_boundaries;
+  float momentum, beta1, beta2, epsilon;
+} odet_opt_config_t;
+
+/* bytes of the partials buffer (one float64 per chunk; 8-byte aligned); only the chunks of regularised tensors are used */
+size_t odet_opt_partials_bytes(int num_chunks);
+/* One training step.  cfg: HOST.  tensor_losses float32 [num_tensors] and total_loss float32 [1] are each nullable; with both
+ * NULL no L2 sum is formed and partials may be NULL.  Errors, all before any GPU work: ODET_E_INVALID (null cfg / state /
+ * table, unknown kind, a beta outside [0, 1), negative epsilon or count, L2 outputs without partials), ODET_E_LIMIT (above),
+ * ODET_E_WORKSPACE (partials too small). */
+int odet_opt_step(const odet_opt_config_t* cfg, const odet_opt_tensor_t* tensors, const void* const* grads,
+                  const odet_opt_chunk_t* chunks, odet_opt_state_t* state, void* partials, size_t partials_bytes,
+                  float* tensor_losses, float* total_loss, odet_stream_t stream);
+/* The same L2 reduction with no update (the forward value of l2_loss): nothing but the two outputs and partials is written. */
+int odet_l2_loss(const odet_opt_config_t* cfg, const odet_opt_tensor_t* tensors, const odet_opt_chunk_t* chunks, void* partials,
+                 size_t partials_bytes, float* tensor_losses, float* total_loss, odet_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,40 @@ class OdetFpnStep(C.Structure):
     ]
 
 
+# ---- the training step's records (include/odet.h "training step") ----
+OPT_CHUNK = 4096
+OPT_MAX_TENSORS = 4096
+OPT_MAX_CHUNKS = 1 << 24
+OPT_MAX_BOUNDARIES = 16
+OPT_MOMENTUM, OPT_ADAM = 1, 2
+OPT_VAR_F16, OPT_GRAD_F16 = 1, 2
+
+
+class OdetOptTensor(C.Structure):
+    """odet_opt_tensor_t (64 bytes)"""
+    _fields_ = [('var', C.c_void_p), ('slot0', C.c_void_p), ('slot1', C.c_void_p), ('master', C.c_void_p),
+                ('numel', C.c_int64), ('weight_decay', C.c_float), ('grad_scale', C.c_float), ('flags', C.c_int32),
+                ('first_chunk', C.c_int32), ('reserved', C.c_int64)]
+
+
+class OdetOptChunk(C.Structure):
+    """odet_opt_chunk_t (16 bytes)"""
+    _fields_ = [('offset', C.c_int64), ('tensor', C.c_int32), ('reserved', C.c_int32)]
+
+
+class OdetOptState(C.Structure):
+    """odet_opt_state_t (216 bytes)"""
+    _fields_ = [('global_step', C.c_int64), ('beta1_power', C.c_float), ('beta2_power', C.c_float),
+                ('boundaries', C.c_int64 * OPT_MAX_BOUNDARIES), ('values', C.c_float * (OPT_MAX_BOUNDARIES + 1)),
+                ('reserved', C.c_float)]
+
+
+class OdetOptConfig(C.Structure):
+    """odet_opt_config_t (host)"""
+    _fields_ = [('kind', C.c_int32), ('num_tensors', C.c_int32), ('num_chunks', C.c_int32), ('num_boundaries', C.c_int32),
+                ('momentum', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('epsilon', C.c_float)]
+
+
 # name -> (restype, argtypes); mirrors include/odet.h one to one
 SIGNATURES = {
     'odet_version': (_i, []),
@@ -185,6 +219,9 @@ SIGNATURES = {
     'odet_rpn_loss': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
     'odet_rpn_loss_backward': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'odet_roi_loss': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    'odet_opt_partials_bytes': (_sz, [_i]),
+    'odet_opt_step': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    'odet_l2_loss': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
 }
 
 

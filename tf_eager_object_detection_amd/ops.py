@@ -1354,3 +1354,135 @@ def roi_losses(scores, deltas, final_labels, targets, inside, outside, counts, s
            L.dptr(row_map, torch.int32, 'row_map'), float(sigma), L.dptr(upstream, torch.float32, 'upstream'),
            *[L.dptr(t) for t in out], L.stream())
     return out
+
+
+# ---- the training step (csrc/optimizer.hip) -------------------------------------------------------------------------------------
+OPT_CHUNK = L.OPT_CHUNK
+OPT_MAX_TENSORS, OPT_MAX_CHUNKS, OPT_MAX_BOUNDARIES = L.OPT_MAX_TENSORS, L.OPT_MAX_CHUNKS, L.OPT_MAX_BOUNDARIES
+
+OptimizerOutputs = collections.namedtuple('OptimizerOutputs', ['l2_loss', 'tensor_l2_losses'])
+
+
+def opt_chunk_table(numels):
+    """numel per variable -> (first_chunk per variable, [(tensor, offset)]): chunks of OPT_CHUNK elements, none spanning two
+    tensors, a tensor's chunks consecutive in ascending offset (host arithmetic only)"""
+    first, chunks = [], []
+    for t, n in enumerate(numels):
+        first.append(len(chunks))
+        chunks.extend((t, o) for o in range(0, int(n), OPT_CHUNK))
+    return first, chunks
+
+
+def _bytes_tensor(obj, device):
+    return torch.frombuffer(bytearray(bytes(obj)), dtype=torch.uint8).to(device)
+
+
+class OptimizerTables:
+    """The device tables of one variable list (include/odet.h "training step"), built once: the tensor records, the chunk
+    table, the gradient pointer column with its pinned staging copy, the partials buffer and the two L2 outputs.
+    records: one dict per variable with var, slot0, slot1, master (tensors or None), weight_decay, grad_scale, grad_f16."""
+
+    def __init__(self, records, device):
+        self.device = torch.device(device)
+        T = len(records)
+        if T > OPT_MAX_TENSORS:
+            raise ValueError('%d variables exceed the limit of %d' % (T, OPT_MAX_TENSORS))
+        first, chunks = opt_chunk_table([r['var'].numel() for r in records])
+        if len(chunks) > OPT_MAX_CHUNKS:
+            raise ValueError('%d chunks exceed the limit of %d' % (len(chunks), OPT_MAX_CHUNKS))
+        self.num_tensors, self.num_chunks = T, len(chunks)
+        self._keep = records                                   # (the tables hold raw pointers into these tensors)
+        self._first = first
+        ctab = (L.OdetOptChunk * max(len(chunks), 1))()
+        for i, (t, o) in enumerate(chunks):
+            ctab[i].offset, ctab[i].tensor = o, t
+        self.chunks = _bytes_tensor(ctab, self.device)
+        self.tensors = torch.empty(max(T, 1) * C.sizeof(L.OdetOptTensor), dtype=torch.uint8, device=self.device)
+        self.write_tensors()
+        self.grads = torch.zeros(max(T, 1), dtype=torch.int64, device=self.device)
+        self._grads_host = torch.zeros(max(T, 1), dtype=torch.int64).pin_memory()
+        self._grads_now = None
+        self._copied = None
+        self.partials = L.workspace(L.lib().odet_opt_partials_bytes(self.num_chunks), self.device)
+        self.tensor_l2_losses = torch.zeros(max(T, 1), dtype=torch.float32, device=self.device)[:T]
+        self.l2_loss = torch.zeros((), dtype=torch.float32, device=self.device)
+
+    def _ptr(self, t, dtype, name):
+        if t is None:
+            return None
+        if t.device != self.device:
+            raise L.OdetError('%s lives on %s, the tables on %s' % (name, t.device, self.device))
+        if dtype is not None and t.dtype != dtype:
+            raise TypeError('%s must be %s, got %s' % (name, dtype, t.dtype))
+        return t.data_ptr()
+
+    def write_tensors(self):
+        """(re)writes the tensor records from the record dicts: a copy to the device on the current stream"""
+        tab = (L.OdetOptTensor * max(self.num_tensors, 1))()
+        for i, r in enumerate(self._keep):
+            v = r['var']
+            if v.dtype not in (torch.float32, torch.float16):
+                raise TypeError('variable %d must be float32 or float16, got %s' % (i, v.dtype))
+            if v.dtype == torch.float16 and r.get('master') is None:
+                raise ValueError('float16 variable %d has no float32 master' % i)
+            e = tab[i]
+            e.var = self._ptr(v, None, 'variable %d' % i)
+            e.slot0 = self._ptr(r.get('slot0'), torch.float32, 'slot0 of variable %d' % i)
+            e.slot1 = self._ptr(r.get('slot1'), torch.float32, 'slot1 of variable %d' % i)
+            e.master = self._ptr(r.get('master'), torch.float32, 'master of variable %d' % i) if v.dtype == torch.float16 else None
+            e.numel = v.numel()
+            e.weight_decay = float(r.get('weight_decay', 0.0))
+            e.grad_scale = float(r.get('grad_scale', 1.0))
+            e.flags = (L.OPT_VAR_F16 if v.dtype == torch.float16 else 0) | (L.OPT_GRAD_F16 if r.get('grad_f16') else 0)
+            e.first_chunk = self._first[i]
+        host = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8)
+        if torch.cuda.is_current_stream_capturing():
+            raise L.OdetError('the tensor table changed inside a graph capture')
+        self.tensors.copy_(host)                               # (pageable: the copy has completed on return)
+
+    def set_gradients(self, pointers):
+        """pointers: one int per variable (0 = None this step).  Unchanged -> nothing happens.  Changed -> the pointer column is
+        re-uploaded from pinned memory on the current stream (nothing is read back); inside a graph capture that is an error."""
+        pointers = tuple(int(p) for p in pointers)
+        if len(pointers) != self.num_tensors:
+            raise ValueError('%d gradient pointers for %d variables' % (len(pointers), self.num_tensors))
+        if pointers == self._grads_now:
+            return False
+        if torch.cuda.is_current_stream_capturing():
+            raise L.OdetError('the gradient pointers changed inside a graph capture: bind the gradients the graph will use '
+                              '(set_gradients / Optimizer.prepare) before capturing, and write new gradients into them')
+        if self._copied is not None:
+            self._copied.synchronize()                         # (the previous upload has left the pinned buffer)
+        if pointers:
+            self._grads_host[:len(pointers)] = torch.tensor(pointers, dtype=torch.int64)
+        self.grads.copy_(self._grads_host, non_blocking=True)
+        self._copied = torch.cuda.Event()
+        self._copied.record()
+        self._grads_now = pointers
+        return True
+
+
+def _opt_config(tables, kind=0, num_boundaries=0, momentum=0.0, beta1=0.0, beta2=0.0, epsilon=0.0):
+    return L.OdetOptConfig(int(kind), tables.num_tensors, tables.num_chunks, int(num_boundaries), float(momentum),
+                           float(beta1), float(beta2), float(epsilon))
+
+
+def optimizer_step(tables, state, kind, num_boundaries=0, momentum=0.0, beta1=0.9, beta2=0.999, epsilon=1e-8, l2=True):
+    """odet_opt_step over `tables` (whose gradient column the caller has set) and the device state block `state` (uint8
+    [sizeof odet_opt_state_t]).  l2: also write tables.l2_loss / tables.tensor_l2_losses (of the pre-update values).  Two
+    launches, nothing is read back."""
+    if state.dtype != torch.uint8 or state.numel() != C.sizeof(L.OdetOptState) or state.device != tables.device:
+        raise ValueError('state must be a uint8 tensor of %d bytes on %s' % (C.sizeof(L.OdetOptState), tables.device))
+    cfg = _opt_config(tables, kind, num_boundaries, momentum, beta1, beta2, epsilon)
+    L.call('odet_opt_step', C.byref(cfg), L.dptr(tables.tensors), L.dptr(tables.grads), L.dptr(tables.chunks), L.dptr(state),
+           L.dptr(tables.partials), tables.partials.numel(), L.dptr(tables.tensor_l2_losses) if l2 else None,
+           L.dptr(tables.l2_loss) if l2 else None, L.stream())
+    return OptimizerOutputs(tables.l2_loss, tables.tensor_l2_losses) if l2 else None
+
+
+def l2_loss(tables):
+    """odet_l2_loss: the regulariser's forward value (total, per tensor) over `tables`, nothing else written"""
+    cfg = _opt_config(tables)
+    L.call('odet_l2_loss', C.byref(cfg), L.dptr(tables.tensors), L.dptr(tables.chunks), L.dptr(tables.partials),
+           tables.partials.numel(), L.dptr(tables.tensor_l2_losses), L.dptr(tables.l2_loss), L.stream())
+    return OptimizerOutputs(tables.l2_loss, tables.tensor_l2_losses)
