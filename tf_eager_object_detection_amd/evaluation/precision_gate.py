@@ -219,7 +219,6 @@ def fit_readout_heads(model, scenes, rpn_gain=2.0, cls_gain=8.0, pos_iou=0.7, ne
         tb = _ridge(Gp[a] / npos[a], Bt[a] / npos[a], max(ridge, 1e-2)).float()        # [cin + 1, 4]
         for k in range(4):
             wb[4 * a + k, :, 0, 0], bb[4 * a + k] = tb[:cin, k], tb[cin, k]
-    model._rpn_pair = None
     # ---- RoI head on the proposals of the fitted RPN (ProposalTarget's labels: IoU >= 0.5 with an object -> its class)
     ncls = model.num_classes
     dh = model.score.in_features + 1

@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..derived import derived
 from ..pipeline import FpnHotPath, FpnStepBatch
 
 __all__ = ['ResNetFpnDetector', 'tf_legacy_resize_bilinear']
@@ -130,6 +131,37 @@ _FUSED_TAIL_MIN_SLABS = 200
 _PATCH_BYTES_MAX = 0xF0000000
 
 
+def _patch_weight(weight, kpad):
+    """a [cout, cin, kh, kw] convolution weight as the patch-matrix GEMM's float32 [cout, kpad]: rows in (dy, dx, channel) order,
+    zero columns from kh * kw * cin on"""
+    with torch.no_grad():
+        cout = int(weight.shape[0])
+        k = weight.numel() // cout
+        w = torch.zeros((cout, kpad), dtype=torch.float32, device=weight.device)
+        w[:, :k] = weight.permute(0, 2, 3, 1).reshape(cout, k)
+    return w
+
+
+def _patch_gemm(images_nhwc, per_image, patches, w, bias=None, relu=False, tail=None):
+    """tail?(ops.pointwise(patches(images), w, bias, relu)) as a channels_last [B,C,h,w] map.  The patch matrix (`per_image` bytes
+    an image) is addressed with 32-bit byte offsets: the images go through in groups that keep it below 4 GiB"""
+    B = int(images_nhwc.shape[0])
+    step = max(1, min(B, _PATCH_BYTES_MAX // per_image))
+    parts = []
+    for i in range(0, B, step):
+        y = ops.pointwise(patches(images_nhwc[i:i + step]), w, bias, None, relu)
+        parts.append(y if tail is None else tail(y))
+    y = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+    return y.permute(0, 3, 1, 2)
+
+
+def _pad_rows64(t):
+    """t [rows, ...] with zero rows up to the next multiple of 64 (the GEMM kernel's output-channel granule)"""
+    out = torch.zeros(((int(t.shape[0]) + 63) // 64 * 64,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    out[:t.shape[0]] = t
+    return out
+
+
 def _stem(conv1, images_nhwc, dtype):
     """conv1_pad + 7x7/2 'valid' + folded BN + ReLU + pool1_pad + 3x3/2 max-pooling (resnet_fpn.py:262-289).  float16: ONE
     launch from the image (ops.stem_conv7_pool3: the 64-channel convolution output, 273 MB at batch 8, never goes to
@@ -138,31 +170,14 @@ def _stem(conv1, images_nhwc, dtype):
     ok = (images_nhwc.is_cuda and images_nhwc.is_contiguous() and conv1.out_channels == 64
           and tuple(conv1.kernel_size) == (7, 7) and tuple(conv1.stride) == (2, 2))
     if ok and dtype == torch.float16 and images_nhwc.dtype in (torch.float32, torch.float16):
-        key = (conv1.weight.data_ptr(), conv1.weight._version)
-        packed = getattr(conv1, '_odet_packed', None)
-        if packed is None or packed[0] != key:
-            packed = (key, ops.stem_pack_weights(conv1.weight))
-            conv1._odet_packed = packed
-        return ops.stem_conv7_pool3(images_nhwc, packed[1], conv1.bias).permute(0, 3, 1, 2)
+        packed = derived(conv1, 'stem_f16', (conv1.weight,), ops.stem_pack_weights)
+        return ops.stem_conv7_pool3(images_nhwc, packed, conv1.bias).permute(0, 3, 1, 2)
     if ok and dtype == torch.float32 and images_nhwc.dtype == torch.float32:
-        key = (conv1.weight.data_ptr(), conv1.weight._version)
-        packed = getattr(conv1, '_odet_packed32', None)
-        if packed is None or packed[0] != key:
-            with torch.no_grad():
-                w = torch.zeros((64, 160), dtype=torch.float32, device=conv1.weight.device)
-                w[:, :147] = conv1.weight.permute(0, 2, 3, 1).reshape(64, 147)
-            packed = (key, w)
-            conv1._odet_packed32 = packed
-        # (the patch matrix is addressed with 32-bit byte offsets: images go through in groups that keep it below 4 GiB)
-        B, H, W = (int(v) for v in images_nhwc.shape[:3])
+        w = derived(conv1, 'stem_f32', (conv1.weight,), lambda weight: _patch_weight(weight, 160))
+        H, W = int(images_nhwc.shape[1]), int(images_nhwc.shape[2])
         per_image = ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1) * 160 * 4
-        step = max(1, min(B, _PATCH_BYTES_MAX // per_image))
-        parts = []
-        for i in range(0, B, step):
-            y = ops.pointwise(ops.stem_patches_f32(images_nhwc[i:i + step]), packed[1], None)
-            parts.append(ops.bias_relu_maxpool(y, conv1.bias, 3, 2, 1, False))
-        y = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
-        return y.permute(0, 3, 1, 2)
+        return _patch_gemm(images_nhwc, per_image, ops.stem_patches_f32, w,
+                           tail=lambda y: ops.bias_relu_maxpool(y, conv1.bias, 3, 2, 1, False))
     raise _no_kernel('stem', conv1, images_nhwc)
 
 
@@ -212,18 +227,14 @@ class _Block(nn.Module):
             self.c3.weight.mul_(0.2)
 
     def _dual_weights(self):
-        """[w3 | w_shortcut] along K and b3 + b_shortcut (ops.pointwise_dual), cached until a parameter changes"""
-        ps = (self.c3.weight, self.c3.bias, self.short.weight, self.short.bias)
-        key = tuple((t._version, t.data_ptr(), t.dtype) for t in ps)
-        c = getattr(self, '_dual_cache', None)
-        if c is None or c[0] != key:
+        """[w3 | w_shortcut] along K and b3 + b_shortcut (ops.pointwise_dual), derived from the four parameters"""
+        def build(*ps):
             with torch.no_grad():
                 n = self.c3.out_channels
                 w = torch.cat([ps[0].reshape(n, -1), ps[2].reshape(n, -1)], 1).contiguous()
                 b = (ps[1].float() + ps[3].float()).to(ps[1].dtype).contiguous()
-            c = (key, w, b)
-            self._dual_cache = c
-        return c[1], c[2]
+            return w, b
+        return derived(self, 'dual', (self.c3.weight, self.c3.bias, self.short.weight, self.short.bias), build)
 
     def forward(self, x):
         y = _conv_epi(self.c1, x, relu=True)
@@ -285,31 +296,22 @@ def tf_legacy_resize_bilinear(x, out_hw):
 
 def rpn_pair_weights(m):
     """[6A, 512, 1, 1] weight and [6A] bias of m.rpn_score and m.rpn_bbox concatenated along the output channel
-    (the RpnHead's two 1x1 convolutions as one contraction); cached on the module, rebuilt when either parameter
+    (the RpnHead's two 1x1 convolutions as one contraction); derived on the module: rebuilt when a parameter
     was modified (weight loading, an optimiser step) or moved."""
-    ps = (m.rpn_score.weight, m.rpn_score.bias, m.rpn_bbox.weight, m.rpn_bbox.bias)
-    key = tuple((t._version, t.data_ptr(), t.dtype) for t in ps)
-    cached = getattr(m, '_rpn_pair', None)
-    if cached is None or cached[0] != key:
+    def build(*ps):
         with torch.no_grad():
             w = torch.cat([ps[0], ps[2]], 0).contiguous(memory_format=torch.channels_last)
             b = torch.cat([ps[1], ps[3]], 0).contiguous()
-        cached = (key, w, b)
-        m._rpn_pair = cached
-    return cached[1], cached[2]
+        return w, b
+    return derived(m, 'rpn_pair', (m.rpn_score.weight, m.rpn_score.bias, m.rpn_bbox.weight, m.rpn_bbox.bias), build)
 
 
 def rpn_pair_padded(m, w):
-    """the concatenated [6A, cin, 1, 1] RpnHead weight as [64 k, cin] with zero rows (the GEMM kernel's channel granule)"""
-    c = getattr(m, '_rpn_pad', None)
-    if c is None or c[0] is not w:
+    """the concatenated [6A, cin, 1, 1] RpnHead weight (rpn_pair_weights' own tensor) as [64 k, cin] with zero rows"""
+    def build(w):
         with torch.no_grad():
-            rows = (int(w.shape[0]) + 63) // 64 * 64
-            wp = torch.zeros((rows, w.shape[1]), dtype=w.dtype, device=w.device)
-            wp[:w.shape[0]] = w.reshape(w.shape[0], -1)
-        c = (w, wp)
-        m._rpn_pad = c
-    return c[1]
+            return _pad_rows64(w.reshape(w.shape[0], -1))
+    return derived(m, 'rpn_pad', (w,), build)
 
 
 def check_caller_f32_form(form):
@@ -368,22 +370,14 @@ class _FinalLayer:
     1 % of a softmax score)."""
 
     def _final_layer(self):
-        ps = (self.score.weight, self.score.bias, self.bbox.weight, self.bbox.bias)
-        key = tuple((t._version, t.data_ptr(), t.dtype) for t in ps)
-        c = getattr(self, '_final_cache', None)
-        if c is None or c[0] != key:
+        def build(*ps):
             with torch.no_grad():
                 wc = torch.cat([ps[0], ps[2]], 0)
-                bc = torch.cat([ps[1], ps[3]], 0).float()
-                rows = (wc.shape[0] + 63) // 64 * 64
-                wpad = torch.zeros((rows, wc.shape[1]), dtype=wc.dtype, device=wc.device)
-                wpad[:wc.shape[0]] = wc
-                b = torch.zeros(rows, dtype=torch.float32, device=wc.device)
-                b[:bc.shape[0]] = bc
+                wpad = _pad_rows64(wc)
+                b = _pad_rows64(torch.cat([ps[1], ps[3]], 0).float())
             gran = 64 if wc.dtype == torch.float16 else 32
-            c = (key, wpad if wc.shape[1] % gran == 0 and wc.shape[1] >= 2 * gran else None, b.contiguous())
-            self._final_cache = c
-        return c[1], c[2]
+            return wpad if wc.shape[1] % gran == 0 and wc.shape[1] >= 2 * gran else None, b.contiguous()
+        return derived(self, 'final', (self.score.weight, self.score.bias, self.bbox.weight, self.bbox.bias), build)
 
     def _final_outputs(self, x):
         """x [rows, K] (the head's last activation) -> (class logits [rows, Ccls], box regressions [rows, 4 Ccls])"""
@@ -575,7 +569,6 @@ class ResNetFpnDetector(_NmsCompleteness, _FinalLayer, nn.Module):
         self._hot_kwargs = dict(blind_chunks=DEFAULT_BLIND_CHUNKS)
         self._hot_kwargs.update(hot_kwargs)
         self._hot = []
-        self._rpn_pair = None
         self._max_batch = max_batch
 
     def prepare(self, device='cuda'):
@@ -584,9 +577,8 @@ class ResNetFpnDetector(_NmsCompleteness, _FinalLayer, nn.Module):
         `blind_chunks` chunks: the first one shared by the batch, the others per image); `batched=False` in
         the hot-path keywords selects the per-image path (FpnHotPath per image)."""
         self.to(device=device, dtype=self.dtype, memory_format=torch.channels_last).eval()
-        ops.invalidate_planes(self)                   # (cached limb planes of weights that may have been rewritten through .data)
+        ops.invalidate_planes(self)                   # (every derived tensor: the weights may have been rewritten through .data)
         fd = torch.float16 if self.dtype == torch.float16 else torch.float32
-        self._rpn_pair = None
         self._steps = None
         if self._max_batch <= 64 and self._hot_kwargs.pop('batched', True):
             self._steps = FpnStepBatch(self._max_batch, *self._hot_args, feature_dtype=fd, **self._hot_kwargs)
@@ -651,7 +643,7 @@ class ResNetFpnDetector(_NmsCompleteness, _FinalLayer, nn.Module):
         if not _own_conv3x3(self.rpn_conv, p0) or self.rpn_conv.out_channels % 256:
             raise _no_kernel('RpnHead', self.rpn_conv, p0)
         # the two 1x1 convolutions run as ONE contraction (weights concatenated: the 512-channel activation is read once)
-        w, b = self._rpn_pair_weights()
+        w, b = rpn_pair_weights(self)
         B = p0.shape[0]
         n = sum(int(p.shape[2]) * int(p.shape[3]) for p in p_list) * self.A
         scores = torch.empty((B, n, 2), dtype=torch.float32, device=p0.device)
@@ -670,16 +662,10 @@ class ResNetFpnDetector(_NmsCompleteness, _FinalLayer, nn.Module):
         heads = ops.conv3x3_f32_levels(xs, self.rpn_conv.weight, self.rpn_conv.bias, relu=True)
         off = 0
         for h in heads:
-            sd = ops.pointwise(h, self._rpn_pair_padded(w), None)[..., :6 * self.A]
+            sd = ops.pointwise(h, rpn_pair_padded(self, w), None)[..., :6 * self.A]
             ops.rpn_pack_pair(sd if sd.is_contiguous() else sd.contiguous(), b, self.A, scores, deltas, off)
             off += int(h.shape[1]) * int(h.shape[2]) * self.A
         return scores, deltas
-
-    def _rpn_pair_weights(self):
-        return rpn_pair_weights(self)
-
-    def _rpn_pair_padded(self, w):
-        return rpn_pair_padded(self, w)
 
     def head_activation(self, roi_features):
         """flatten(7,7,256) -> fc 1024 -> fc 1024 (resnet_fpn.py:292-326): the input of the score / bbox layers; the Dense

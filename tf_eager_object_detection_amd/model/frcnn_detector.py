@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..derived import derived
 from ..pipeline import FrcnnHotPath, FrcnnStepBatch
 from . import fpn_detector as fpn
 from .fpn_detector import _BLOCKS, DEFAULT_BLIND_CHUNKS, ResNetFpnDetector, _NmsCompleteness, _FinalLayer, _conv, _conv_epi, _stem, \
@@ -64,7 +65,7 @@ class ResNetC4Detector(_NmsCompleteness, _FinalLayer, nn.Module):
         kernel launches (FrcnnStepBatch: odet_fpn_step_t.single_level) and through the RoI head as one batch;
         `batched=False` in the hot-path keywords selects one FrcnnHotPath per image on a stream of its own."""
         self.to(device=device, dtype=self.dtype, memory_format=torch.channels_last).eval()
-        ops.invalidate_planes(self)                   # (cached limb planes of weights that may have been rewritten through .data)
+        ops.invalidate_planes(self)                   # (every derived tensor: the weights may have been rewritten through .data)
         # float16 maps go straight into the RoI kernel (pooled 14x14 + max and un-pooled 7x7 crop alike)
         feat_dtype = torch.float16 if self.dtype == torch.float16 else torch.float32
         self._feature_dtype = feat_dtype
@@ -279,28 +280,13 @@ class Vgg16Detector(ResNetC4Detector):
             raise _no_kernel('first convolution', first, images_nhwc)
         if self.dtype == torch.float16 and images_nhwc.dtype in (torch.float32, torch.float16):
             # conv1_1 straight from the image (ops.conv3x3_rgb: bias + ReLU in the launch, its output written once)
-            key = (first.weight.data_ptr(), first.weight._version)
-            packed = getattr(first, '_odet_packed', None)
-            if packed is None or packed[0] != key:
-                packed = (key, ops.conv3x3_rgb_pack_weights(first.weight))
-                first._odet_packed = packed
-            x = ops.conv3x3_rgb(images_nhwc, packed[1], first.bias, relu=True).permute(0, 3, 1, 2)
+            packed = derived(first, 'rgb_f16', (first.weight,), ops.conv3x3_rgb_pack_weights)
+            x = ops.conv3x3_rgb(images_nhwc, packed, first.bias, relu=True).permute(0, 3, 1, 2)
         elif self.dtype == torch.float32 and images_nhwc.dtype == torch.float32:
             # float32 (parity mode): conv1_1 as the exact-float32 GEMM on its patch matrix (ops.rgb_patches3x3_f32)
-            key = (first.weight.data_ptr(), first.weight._version)
-            packed = getattr(first, '_odet_packed32', None)
-            if packed is None or packed[0] != key:
-                with torch.no_grad():
-                    w = torch.zeros((64, 64), dtype=torch.float32, device=first.weight.device)
-                    w[:, :27] = first.weight.permute(0, 2, 3, 1).reshape(64, 27)
-                packed = (key, w)
-                first._odet_packed32 = packed
-            # (32-bit byte offsets into the patch matrix: groups of images that keep it below 4 GiB)
-            Bn, Hn, Wn = (int(v) for v in images_nhwc.shape[:3])
-            step = max(1, min(Bn, fpn._PATCH_BYTES_MAX // (Hn * Wn * 64 * 4)))
-            parts = [ops.pointwise(ops.rgb_patches3x3_f32(images_nhwc[i:i + step]), packed[1], first.bias, None, True)
-                     for i in range(0, Bn, step)]
-            x = (parts[0] if len(parts) == 1 else torch.cat(parts, 0)).permute(0, 3, 1, 2)
+            w = derived(first, 'rgb_f32', (first.weight,), lambda weight: fpn._patch_weight(weight, 64))
+            Hn, Wn = int(images_nhwc.shape[1]), int(images_nhwc.shape[2])
+            x = fpn._patch_gemm(images_nhwc, Hn * Wn * 64 * 4, ops.rgb_patches3x3_f32, w, first.bias, True)
         else:
             raise _no_kernel('first convolution', first, images_nhwc)
         i = 0

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .derived import derived, invalidate
 
 # constants of include/odet.h
 RPN_LAYOUT_FPN, RPN_LAYOUT_FRCNN = 0, 1
@@ -95,30 +96,6 @@ def split_f16x2(w, w_exp=None):
     return planes, int(w_exp)
 
 
-def _plane_key(w):
-    """cache key of a weight's limb planes; None (= split again, every time) for tensors without a version counter (inference
-    tensors: torch raises on ._version)"""
-    try:
-        return (w.data_ptr(), w._version, tuple(w.shape))
-    except RuntimeError:
-        return None
-
-
-def _limb_planes(holder, w, attr, split):
-    """the limb planes `split(w)` of the (contiguous, float32) weight `w`, kept ON the tensor object the caller passed (`holder`:
-    the layer's parameter, or a module's cached concatenation) under `attr` until that tensor is modified: the planes live exactly
-    as long as the weight they belong to -- no global cache that could outlive or be cleared under a captured HIP graph.  A caller
-    that passes a fresh temporary every time pays the split every time (correct, slow): keep weights in stable tensors.
-    (split_f16x2 reads its exponent from the weights -- one host synchronisation per weight tensor, at its first use: a warm-up
-    pass before a HIP-graph capture, as for the workspace)"""
-    key = _plane_key(w)
-    hit = holder.__dict__.get(attr) if key is not None else None
-    if hit is None or hit[0] != key:
-        hit = (key, split(w), w)
-        holder.__dict__[attr] = hit
-    return hit[1]
-
-
 class X3Workspace:
     """The caller-owned workspace of the split-precision launches (include/odet.h): split-K ticket words (zero-filled once; every
     launch leaves them zero), the two-limb form's RANGE STATUS word, the split-K parts.  One workspace serves launches that are
@@ -169,42 +146,33 @@ def _x3_workspace(device):
     return ws
 
 
-def invalidate_planes(module_or_tensor):
-    """drops the cached limb planes of a weight tensor / of every parameter and cached concatenation of a module: call after
-    writing weights in a way that does not bump the tensor version (`.data` writes, set_()); load_state_dict() and the
-    detectors' prepare() do.  (In-place ops through the tensor itself bump the version and need nothing.)"""
-    import torch.nn as nn
-    objs = [module_or_tensor]
-    if isinstance(module_or_tensor, nn.Module):
-        objs = list(module_or_tensor.parameters()) + list(module_or_tensor.buffers())
-        for m in module_or_tensor.modules():
-            for v in list(m.__dict__.values()):
-                if isinstance(v, torch.Tensor):
-                    objs.append(v)
-                elif isinstance(v, (tuple, list)):
-                    objs += [t for t in v if isinstance(t, torch.Tensor)]
-    for t in objs:
-        t.__dict__.pop('_odet_x3', None)
-        t.__dict__.pop('_odet_x2', None)
+# the name DESIGN.md knows derived.invalidate by: after `.data` / set_() writes (no version bump); drops EVERY derived tensor
+invalidate_planes = invalidate
 
 
-# form -> entry-point suffix, the attribute a weight's limb planes are cached under, their splitter, and how the cached value reads
+# form -> entry-point suffix, the name a weight's limb planes are derived under, their splitter, and how the derived value reads
 # as (planes, extra arguments ahead of the workspace's)
 _F32_FORMS = {
     'exact': ('f32', None, None, None),
-    'x3': ('x3', '_odet_x3', split_bf16x3, lambda planes: (planes, ())),
-    'x2': ('x2', '_odet_x2', split_f16x2, lambda planes_exp: (planes_exp[0], (planes_exp[1],))),
+    'x3': ('x3', 'x3', split_bf16x3, lambda planes: (planes, ())),
+    'x2': ('x2', 'x2', split_f16x2, lambda planes_exp: (planes_exp[0], (planes_exp[1],))),
 }
 
 
 def _f32_sym(pattern, w, holder=None):
     """(form, entry point, weight pointer, extra arguments before the stream) of a float32 layer in the current form: `pattern` %
-    the form's suffix; `holder` = the caller's weight tensor object"""
+    the form's suffix.  The limb planes are derived FROM and kept ON the tensor object the caller passed (`holder`: the layer's
+    parameter, or a module's derived concatenation; `w` itself when None) until that tensor is modified (derived.py: they live
+    exactly as long as the weight they belong to -- no global cache that could outlive or be cleared under a captured HIP
+    graph); `w`, the holder's contiguous float32 view, is read only when they are built.  (split_f16x2 reads its exponent from
+    the weights -- one host synchronisation per weight tensor, at its first use: a warm-up pass before a HIP-graph capture, as
+    for the workspace)"""
     form = _F32_CTX.get()[0]
-    sfx, attr, split, read = _F32_FORMS[form]
-    if attr is None:
+    sfx, name, split, read = _F32_FORMS[form]
+    if name is None:
         return form, pattern % sfx, L.dptr(w), ()
-    planes, extra = read(_limb_planes(w if holder is None else holder, w, attr, split))
+    holder = w if holder is None else holder
+    planes, extra = read(derived(holder, name, (holder,), lambda _: split(w)))
     return form, pattern % sfx, C.c_void_p(planes.data_ptr()), extra + _x3_workspace(w.device).args()
 
 

@@ -17,7 +17,10 @@ its gradient has to have the same shape and strides.
 Graph capture: bind the gradient tensors first (`prepare(grads_and_vars)` uploads the tables), capture `apply_gradients`
 with the same tensors, and write later gradients INTO them.  A capture that meets other gradient pointers raises.  The
 version counters of the updated parameters are bumped when `apply_gradients` is called, not when a graph replays: after a
-replay call `mark_updated()` so that caches keyed on `_version` (the detectors' weight packs) rebuild.
+replay call `mark_updated()` so that the tensors the detectors derive from their weights rebuild.  The one rule (derived.py):
+a derived tensor is valid while every source is the same object with the same (data_ptr, version, dtype, device, shape,
+stride) -- in-place ops through the tensor, load_state_dict and this step rebuild by themselves; `.data` / set_() writes need
+derived.invalidate (ops.invalidate_planes, the detectors' prepare()); a captured graph keeps the derived tensors it was captured with.
 """
 import collections
 import ctypes as C
