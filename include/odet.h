@@ -39,8 +39,8 @@ extern "C" {
  * odet_eval_detect_topk, the odet_coco_* evaluation, the odet_voc_* evaluation and the fused training targets
  * (odet_anchor_target, odet_proposal_target) and the fused training losses with their gradients (odet_rpn_loss,
  * odet_rpn_loss_backward, odet_roi_loss) and odet_preprocess_train (the training input stage) and the training step
- * (odet_opt_step, odet_l2_loss, odet_opt_partials_bytes with the odet_opt_*_t records); no existing entry point or struct
- * changed. */
+ * (odet_opt_step, odet_l2_loss, odet_opt_partials_bytes with the odet_opt_*_t records) and the float32 Dense backward
+ * (odet_dense_dgrad_f32, odet_dense_wgrad_f32, odet_dense_grad_workspace_bytes); no existing entry point or struct changed. */
 #define ODET_VERSION 103
 
 #define ODET_OK 0
@@ -1123,6 +1123,30 @@ int odet_opt_step(const odet_opt_config_t* cfg, const odet_opt_tensor_t* tensors
 /* The same L2 reduction with no update (the forward value of l2_loss): nothing but the two outputs and partials is written. */
 int odet_l2_loss(const odet_opt_config_t* cfg, const odet_opt_tensor_t* tensors, const odet_opt_chunk_t* chunks, void* partials,
                  size_t partials_bytes, float* tensor_losses, float* total_loss, odet_stream_t stream);
+
+/* ---- Dense backward, float32 (added within 103) --------------------------------------------------------------------
+ * The gradients of a keras Dense layer y = relu?(x . w^T + b) (resnet_fpn.py:292-336, the FPN RoI head) on the exact-float32
+ * matrix instruction of odet_pointwise_f32.  All tensors float32, row-major, in the forward's own layouts -- nothing is
+ * transposed in memory: x [rows, cin], w [cout, cin], y / dy [rows, cout].  y_relu (nullable) is the layer's own forward
+ * output: the operand is dz = y_relu > 0 ? dy : 0 (TF ReluGrad: strict '>', a select), formed while staging; no dz is written.
+ *   odet_dense_dgrad_f32: dx [rows, cin] = dz . w (contraction along cout); x_relu (nullable, [rows, cin], the forward output of
+ *     the layer below) keeps dx only where x_relu > 0, in the epilogue.
+ *   odet_dense_wgrad_f32: dw [cout, cin] = dz^T . x (contraction along rows, any positive count); db (nullable) [cout] = the
+ *     column sums of dz, from a second small launch.
+ * Shapes (ODET_E_INVALID otherwise, as every error here before any GPU work): rows >= 1, cin a multiple of 32 and >= 64,
+ * cout a multiple of 64; pointers 16-byte aligned (db: 4).  ODET_E_WORKSPACE: a workspace smaller than
+ * odet_dense_grad_workspace_bytes(wgrad = 0 | 1, rows, cin, cout) -- 0 for most shapes; non-zero when the launch splits its
+ * contraction (few output tiles, contraction >= 256), 16-byte aligned, contents arbitrary.
+ * Order of sums: a function of the shape alone, no atomics -- an element adds its products in ascending k, four per matrix
+ * instruction (each product and sum rounded to float32 once); a split launch leaves its parts (equal runs of whole 32-k steps)
+ * in the workspace and adds them in ascending order; db adds the rows r = p, p + 4, ... in ascending r for p = 0 .. 3, then the
+ * four sums left to right.  Exact on integer data whose partial sums stay below 2^24.  No allocation, no host read
+ * (graph-capturable after one eager call per device, which raises the kernels' LDS limit). */
+size_t odet_dense_grad_workspace_bytes(int wgrad, int rows, int cin, int cout);
+int odet_dense_dgrad_f32(const float* dy, const float* w, const float* y_relu, const float* x_relu, float* dx, int rows, int cin,
+                         int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream);
+int odet_dense_wgrad_f32(const float* dy, const float* x, const float* y_relu, float* dw, float* db, int rows, int cin, int cout,
+                         void* workspace, size_t workspace_bytes, odet_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -222,6 +222,9 @@ SIGNATURES = {
     'odet_opt_partials_bytes': (_sz, [_i]),
     'odet_opt_step': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     'odet_l2_loss': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    'odet_dense_grad_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'odet_dense_dgrad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    'odet_dense_wgrad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
 }
 
 

@@ -1,0 +1,299 @@
+// The float32 backward of a Dense layer y = relu?(x . w^T + b) (resnet_fpn.py:292-336, the FPN RoI head) on the exact-float32
+// matrix instruction of conv_f32.hip (v_mfma_f32_16x16x4_f32: every product and every sum rounded to float32 once):
+//
+//   odet_dense_dgrad_f32   dx[rows, cin]  = dz . w          contraction along cout   (* (x_relu > 0) in the epilogue)
+//   odet_dense_wgrad_f32   dw[cout, cin]  = dz^T . x        contraction along rows;  db[cout] = column sums of dz
+//
+// with dz = y_relu > 0 ? dy : 0 formed while the operand is staged (TF's ReluGrad: strict '>', a select -- no dz tensor).
+// All tensors row-major in the forward's own layouts: x [rows, cin], w [cout, cin], y / dy [rows, cout]; nothing is transposed
+// in memory.  Both are ONE kernel, C[n][m] = sum_k A[k][m] * B(k, n) with m = cin in both (the output's contiguous axis):
+//
+//            A [K][M]                 B                              C [N][M]
+//   wgrad    x  [rows][cin]           dz [rows][cout]  (K-major)     dw [cout][cin]
+//   dgrad    w  [cout][cin]           dz [rows][cout]  (N-major)     dx [rows][cin]
+//
+// Tiling.  A workgroup of 4 waves (2 along m x 2 along n) owns a (32 WT)^2 tile, WT = 4 (128 x 128) or 2 (64 x 64); a wave
+// holds WT x WT MFMA tiles.  A is the MFMA's first operand, so a lane ends with four CONSECUTIVE m of one output row n: the
+// four lanes of a row store 64 contiguous bytes per instruction and every element of C is written once.  A K-step is 32: the
+// tile's rows go global -> registers (16-byte loads, the mask applied there) -> LDS while the previous step's MFMAs run (two
+// LDS stages, one barrier per step).  LDS rows are padded (K-major: row stride T + 16 floats, N-major: 32 + 4) so that the 64
+// lanes of an operand read hit 64 different banks.  Everything outside the matrices (the K tail of wgrad, whose `rows` is
+// whatever the sampler delivered; the row edge of dgrad; cin = 96 or 160 against a 64-wide tile) is staged as zeros and
+// never stored.
+//
+// Order of sums (a function of the shape alone; no atomics): an element adds its products in ascending k, four per matrix
+// instruction.  A launch with few tiles and a long contraction is SPLIT along k into `ksplit` equal parts of whole K-steps
+// (dg_plan: a rule on (M, N, K) only); each part leaves its float32 partial tile in the caller's workspace and a second
+// launch adds the parts in the order 0 .. ksplit - 1 and applies the epilogue mask.  db: a column's rows r = p, p + 4, ... are
+// added in ascending r for p = 0 .. 3, then the four sums left to right.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "conv_f32_common.h"
+
+#define DG_BK 32                  // k per K-step
+#define DG_PADK 16                // K-major LDS rows: T + 16 floats
+#define DG_STRN (DG_BK + 4)       // N-major LDS rows: 36 floats
+#define DG_LDS_MAX (80 * 1024)
+
+struct DenseGradParams {
+  const float* a;                 // [K][M]
+  const float* b;                 // dy: [K][N] (wgrad) or [N][K] (dgrad)
+  const float* bmask;             // y_relu in dy's layout (nullable)
+  const float* omask;             // x_relu [N][M] (nullable; a split launch leaves it to the reduction)
+  float* out;                     // [N][M], or the parts [ksplit][N][M]
+  int M, N, K, kper;              // part z of a launch takes k in [z * kper, min(K, (z + 1) * kper)); kper % DG_BK == 0
+};
+
+template <int WT, bool BKMAJOR>
+__global__ void __launch_bounds__(256) k_dense_grad_f32(DenseGradParams p) {
+  constexpr int T = 32 * WT;                              // tile edge (m and n)
+  constexpr int STRK = T + DG_PADK;
+  constexpr int A_ST = DG_BK * STRK;                      // floats per stage and operand (N-major: T * 36 <= A_ST for T <= 128)
+  constexpr int PER = T / 32;                             // 16-byte loads per thread, operand and K-step
+  extern __shared__ __align__(16) float dg_lds[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
+  const int wv = tid >> 6, wm = wv & 1, wn = wv >> 1;
+  const int tiles_m = (p.M + T - 1) / T;
+  const int m0 = (int)(blockIdx.x % (unsigned)tiles_m) * T, n0 = (int)(blockIdx.x / (unsigned)tiles_m) * T;
+  const int kbeg = (int)blockIdx.z * p.kper;
+  const int kend = min(p.K, kbeg + p.kper);
+  const int M = p.M, N = p.N;
+  const long long ldb = BKMAJOR ? N : p.K;
+
+  c3f4 ra[PER], rb[PER];
+  auto fetch = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int idx = tid + 256 * i;
+      {
+        const int k = idx / (T / 4), c = (idx % (T / 4)) * 4;
+        const int gk = k0 + k, gm = m0 + c;
+        ra[i] = (c3f4){0.0f, 0.0f, 0.0f, 0.0f};
+        if (gk < kend && gm < M) ra[i] = *reinterpret_cast<const c3f4*>(p.a + (long long)gk * M + gm);
+      }
+      int gk, gn;
+      if constexpr (BKMAJOR) {
+        gk = k0 + idx / (T / 4); gn = n0 + (idx % (T / 4)) * 4;
+      } else {
+        gn = n0 + idx / (DG_BK / 4); gk = k0 + (idx % (DG_BK / 4)) * 4;
+      }
+      rb[i] = (c3f4){0.0f, 0.0f, 0.0f, 0.0f};
+      if (gk < kend && gn < N) {
+        const long long off = BKMAJOR ? (long long)gk * ldb + gn : (long long)gn * ldb + gk;
+        c3f4 v = *reinterpret_cast<const c3f4*>(p.b + off);
+        if (p.bmask) {
+          const c3f4 y = *reinterpret_cast<const c3f4*>(p.bmask + off);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = y[j] > 0.0f ? v[j] : 0.0f;
+        }
+        rb[i] = v;
+      }
+    }
+  };
+  auto stash = [&](int stage) {
+    float* sa = dg_lds + stage * 2 * A_ST;
+    float* sb = sa + A_ST;
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int idx = tid + 256 * i;
+      *reinterpret_cast<c3f4*>(sa + (idx / (T / 4)) * STRK + (idx % (T / 4)) * 4) = ra[i];
+      if constexpr (BKMAJOR) *reinterpret_cast<c3f4*>(sb + (idx / (T / 4)) * STRK + (idx % (T / 4)) * 4) = rb[i];
+      else *reinterpret_cast<c3f4*>(sb + (idx / (DG_BK / 4)) * DG_STRN + (idx % (DG_BK / 4)) * 4) = rb[i];
+    }
+  };
+
+  c3f4 acc[WT][WT];
+#pragma unroll
+  for (int mt = 0; mt < WT; ++mt)
+#pragma unroll
+    for (int nt = 0; nt < WT; ++nt) acc[mt][nt] = (c3f4){0.0f, 0.0f, 0.0f, 0.0f};
+
+  const int aoff = wm * (T / 2) + l15;
+  const int boff = BKMAJOR ? wn * (T / 2) + l15 : (wn * (T / 2) + l15) * DG_STRN;
+  const int steps = (kend - kbeg + DG_BK - 1) / DG_BK;    // (>= 1: the host gives every part at least one k)
+  fetch(kbeg);
+  stash(0);
+  __syncthreads();
+  for (int s = 0; s < steps; ++s) {
+    const int stage = s & 1;
+    if (s + 1 < steps) fetch(kbeg + (s + 1) * DG_BK);
+    const float* sa = dg_lds + stage * 2 * A_ST;
+    const float* sb = sa + A_ST;
+#pragma unroll
+    for (int kk = 0; kk < DG_BK / 4; ++kk) {
+      const int k = kk * 4 + lq;                          // lane (l15, lq) feeds k = lq of the instruction's four
+      float af[WT], bf[WT];
+#pragma unroll
+      for (int mt = 0; mt < WT; ++mt) af[mt] = sa[k * STRK + aoff + mt * 16];
+#pragma unroll
+      for (int nt = 0; nt < WT; ++nt) bf[nt] = BKMAJOR ? sb[k * STRK + boff + nt * 16] : sb[boff + nt * 16 * DG_STRN + k];
+#pragma unroll
+      for (int mt = 0; mt < WT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < WT; ++nt)
+          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[mt], bf[nt], acc[mt][nt], 0, 0, 0);
+    }
+    if (s + 1 < steps) stash(stage ^ 1);                  // (the stage read in step s - 1: everyone passed the barrier since)
+    __syncthreads();
+  }
+
+  // lane: output row n = .. + l15, columns m = .. + 4 lq .. + 3 of every MFMA tile
+  float* out = p.out + (long long)blockIdx.z * N * M;
+#pragma unroll
+  for (int nt = 0; nt < WT; ++nt) {
+    const int n = n0 + wn * (T / 2) + nt * 16 + l15;
+    if (n >= N) continue;
+#pragma unroll
+    for (int mt = 0; mt < WT; ++mt) {
+      const int m = m0 + wm * (T / 2) + mt * 16 + lq * 4;
+      if (m >= M) continue;
+      c3f4 v = acc[mt][nt];
+      if (p.omask) {
+        const c3f4 y = *reinterpret_cast<const c3f4*>(p.omask + (long long)n * M + m);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = y[j] > 0.0f ? v[j] : 0.0f;
+      }
+      *reinterpret_cast<c3f4*>(out + (long long)n * M + m) = v;
+    }
+  }
+}
+
+// the parts of a split launch, added in the order 0 .. ksplit - 1, and the epilogue mask
+__global__ void __launch_bounds__(256) k_dense_grad_reduce(const float* __restrict__ parts, int ksplit, long long total4,
+                                                           const float* __restrict__ omask, float* __restrict__ out) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long long)gridDim.x * 256) {
+    c3f4 v = reinterpret_cast<const c3f4*>(parts)[i];
+    for (int z = 1; z < ksplit; ++z) {
+      const c3f4 q = reinterpret_cast<const c3f4*>(parts)[(long long)z * total4 + i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = v[j] + q[j];
+    }
+    if (omask) {
+      const c3f4 y = reinterpret_cast<const c3f4*>(omask)[i];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = y[j] > 0.0f ? v[j] : 0.0f;
+    }
+    reinterpret_cast<c3f4*>(out)[i] = v;
+  }
+}
+
+// db[c] = sum over the rows of dz[:, c]: thread (c, p) adds rows p, p + 4, ... in ascending order, then p = 0 .. 3 left to right
+__global__ void __launch_bounds__(256) k_dense_bias_grad(const float* __restrict__ dy, const float* __restrict__ y, float* __restrict__ db,
+                                                         int rows, int cout) {
+  __shared__ float part[4][64];
+  const int c = (int)blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6;
+  float s = 0.0f;
+  if (c < cout) {
+    for (int r = ph; r < rows; r += 4) {
+      const long long off = (long long)r * cout + c;
+      float v = dy[off];
+      if (y) v = y[off] > 0.0f ? v : 0.0f;
+      s = s + v;
+    }
+  }
+  part[ph][threadIdx.x & 63] = s;
+  __syncthreads();
+  if (ph == 0 && c < cout) db[c] = ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------------
+struct DenseGradPlan { int wt, ksplit, kper; long long tiles; };
+
+// tile and split of C [N][M] with contraction K -- a function of the shape alone.  128 x 128 tiles where they still give every
+// CU one; else 64 x 64, and when even those leave half the machine idle and the contraction is long, up to 8 parts of at
+// least 64 k each (whole K-steps)
+static DenseGradPlan dg_plan(int M, int N, int K) {
+  DenseGradPlan pl;
+  const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
+  pl.wt = t128 >= 256 ? 4 : 2;
+  const int T = 32 * pl.wt;
+  pl.tiles = (long long)((M + T - 1) / T) * ((N + T - 1) / T);
+  int ks = 1;
+  if (pl.tiles <= 128 && K >= 256) ks = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(256 / pl.tiles, K / 64), 8));
+  pl.kper = ((K + ks - 1) / ks + DG_BK - 1) / DG_BK * DG_BK;
+  pl.ksplit = (K + pl.kper - 1) / pl.kper;
+  return pl;
+}
+
+static int dg_check_shape(const char* who, int rows, int cin, int cout) {
+  ODET_REQUIRE(rows >= 1, "%s: rows %d must be positive", who, rows);
+  ODET_REQUIRE(cin % 32 == 0 && cin >= 64, "%s: cin %d must be a multiple of 32, at least 64", who, cin);
+  ODET_REQUIRE(cout > 0 && cout % 64 == 0, "%s: cout %d must be a multiple of 64", who, cout);
+  return ODET_OK;
+}
+
+extern "C" size_t odet_dense_grad_workspace_bytes(int wgrad, int rows, int cin, int cout) {
+  if (rows < 1 || cin < 1 || cout < 1) return 0;
+  const DenseGradPlan pl = wgrad ? dg_plan(cin, cout, rows) : dg_plan(cin, rows, cout);
+  return pl.ksplit > 1 ? (size_t)pl.ksplit * (size_t)(wgrad ? cout : rows) * (size_t)cin * sizeof(float) : 0;
+}
+
+static hipError_t dg_prepare_kernels() {
+  static const void* const kernels[] = {(const void*)k_dense_grad_f32<4, true>, (const void*)k_dense_grad_f32<4, false>,
+                                        (const void*)k_dense_grad_f32<2, true>, (const void*)k_dense_grad_f32<2, false>};
+  static OdetPerDeviceOnce once;
+  return conv_f32_raise_lds_limit(&once, kernels, sizeof(kernels) / sizeof(kernels[0]), DG_LDS_MAX);
+}
+
+// C [N][M] = A^T-free contraction of the file comment; every argument already checked
+template <bool BKMAJOR>
+static int dg_launch(const char* who, const float* a, const float* b, const float* bmask, const float* omask, float* out, int M, int N,
+                     int K, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  const DenseGradPlan pl = dg_plan(M, N, K);
+  ODET_REQUIRE(pl.tiles < (1ll << 31), "%s: too many workgroups", who);
+  const size_t need = pl.ksplit > 1 ? (size_t)pl.ksplit * (size_t)N * (size_t)M * sizeof(float) : 0;
+  if (need) {
+    if (!workspace || workspace_bytes < need)
+      return odet_set_error(ODET_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (odet_dense_grad_workspace_bytes)", who,
+                            workspace ? workspace_bytes : (size_t)0, need);
+    ODET_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: the workspace must be 16-byte aligned", who);
+  }
+  ODET_HIP(dg_prepare_kernels());
+  DenseGradParams p;
+  p.a = a; p.b = b; p.bmask = bmask; p.omask = need ? nullptr : omask; p.out = need ? (float*)workspace : out;
+  p.M = M; p.N = N; p.K = K; p.kper = pl.kper;
+  const int T = 32 * pl.wt;
+  const unsigned lds = (unsigned)(2 * 2 * DG_BK * (T + DG_PADK) * sizeof(float));
+  const dim3 grid((unsigned)pl.tiles, 1, (unsigned)pl.ksplit);
+  if (pl.wt == 4) hipLaunchKernelGGL((k_dense_grad_f32<4, BKMAJOR>), grid, dim3(256), lds, st, p);
+  else hipLaunchKernelGGL((k_dense_grad_f32<2, BKMAJOR>), grid, dim3(256), lds, st, p);
+  ODET_LAUNCH_CHECK();
+  if (need) {
+    const long long total4 = (long long)N * M / 4;
+    const unsigned blocks = (unsigned)std::min<long long>((total4 + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(k_dense_grad_reduce, dim3(blocks), dim3(256), 0, st, (const float*)workspace, pl.ksplit, total4, omask, out);
+    ODET_LAUNCH_CHECK();
+  }
+  return ODET_OK;
+}
+
+extern "C" int odet_dense_dgrad_f32(const float* dy, const float* w, const float* y_relu, const float* x_relu, float* dx, int rows,
+                                    int cin, int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
+  const char* who = "odet_dense_dgrad_f32";
+  ODET_REQUIRE(dy && w && dx, "%s: null pointer", who);
+  const int rs = dg_check_shape(who, rows, cin, cout);
+  if (rs != ODET_OK) return rs;
+  ODET_REQUIRE(((uintptr_t)dy | (uintptr_t)w | (uintptr_t)y_relu | (uintptr_t)x_relu | (uintptr_t)dx) % 16 == 0,
+               "%s: pointers must be 16-byte aligned", who);
+  return dg_launch<false>(who, w, dy, y_relu, x_relu, dx, cin, rows, cout, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" int odet_dense_wgrad_f32(const float* dy, const float* x, const float* y_relu, float* dw, float* db, int rows, int cin,
+                                    int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
+  const char* who = "odet_dense_wgrad_f32";
+  ODET_REQUIRE(dy && x && dw, "%s: null pointer", who);
+  const int rs = dg_check_shape(who, rows, cin, cout);
+  if (rs != ODET_OK) return rs;
+  ODET_REQUIRE(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)y_relu | (uintptr_t)dw) % 16 == 0 && (uintptr_t)db % 4 == 0,
+               "%s: pointers must be 16-byte aligned (db: 4)", who);
+  const int rl = dg_launch<true>(who, x, dy, y_relu, nullptr, dw, cin, cout, rows, workspace, workspace_bytes, (hipStream_t)stream);
+  if (rl != ODET_OK) return rl;
+  if (db) {
+    hipLaunchKernelGGL(k_dense_bias_grad, dim3((unsigned)(cout / 64)), dim3(256), 0, (hipStream_t)stream, dy, y_relu, db, rows, cout);
+    ODET_LAUNCH_CHECK();
+  }
+  return ODET_OK;
+}

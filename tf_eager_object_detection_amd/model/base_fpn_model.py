@@ -10,7 +10,9 @@ batch of one image (model/roi_pooling.py:28).  It is the drop-in reading of "bas
 static-shape, sync-free arrangement of the same stages for throughput is model/fpn_detector.py + pipeline.FpnHotPath.
 Every tensor op between the layers that the reference delegates to TF (softmax, gather, concat, reshape) is a torch op on
 the GPU; every detection op is a HIP kernel behind the C ABI.  Training (`training=True`) returns the four losses of the
-forward pass (:232-264) on the target layers of this package; the dense kernels are inference kernels (no backward)."""
+forward pass (:232-264) on the target layers of this package; the dense kernels are inference kernels (no backward), except
+the FPN RoI head with `train_roi_head=True` (float32, exact form): its four Dense layers then run ops.dense_trainable and the two
+RoI losses carry a graph into fc1, fc2, score and bbox."""
 import torch
 
 from .. import ops
@@ -83,9 +85,11 @@ class BaseFPN(torch.nn.Module):
                  roi_training_total_num_samples=128, roi_training_max_pos_samples=32,
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0., training_targets='torch',
-                 training_losses='torch'):
+                 training_losses='torch', train_roi_head=False):
         super().__init__()
         self._training_losses = check_training_losses(training_losses, training_targets)
+        # True: the training branches run the RoI head with a backward pass (the two RoI losses carry a graph into its layers)
+        self._train_roi_head = bool(train_roi_head)
         self.roi_feature_size = roi_feature_size
         self.num_classes = num_classes
         self.weight_decay = weight_decay
@@ -200,9 +204,7 @@ class BaseFPN(torch.nn.Module):
             final_rois, roi_labels, roi_bbox_target, roi_in_weights, roi_out_weights = self._proposal_target(
                 (rois, gt_bboxes, gt_labels), training)
             rois_list, selected_idx = self._assign_levels(final_rois)
-            with torch.no_grad():
-                roi_features = self._get_roi_features(rois_list, p_list, image_shape)
-                roi_score, roi_bboxes_txtytwth = self._roi_head(roi_features, training=training)
+            roi_score, roi_bboxes_txtytwth = self._training_roi_head(rois_list, p_list, image_shape, training)
             roi_cls_loss, roi_reg_loss = self._get_roi_loss(roi_score, roi_bboxes_txtytwth, roi_labels[selected_idx],
                                                             roi_bbox_target[selected_idx], roi_in_weights[selected_idx],
                                                             roi_out_weights[selected_idx])
@@ -240,12 +242,22 @@ class BaseFPN(torch.nn.Module):
                                     strict=False)
         pt._next_image_id += 1
         rois_list, selected_idx = self._assign_levels(proposal_targets.final_rois[0])
-        with torch.no_grad():
-            roi_features = self._get_roi_features(rois_list, p_list, image_shape)
-            roi_score, roi_bboxes_txtytwth = self._roi_head(roi_features, training=training)
+        roi_score, roi_bboxes_txtytwth = self._training_roi_head(rois_list, p_list, image_shape, training)
         roi_cls_loss, roi_reg_loss = fused_roi_losses(roi_score.float()[None], roi_bboxes_txtytwth.float()[None],
                                                       proposal_targets, self._roi_sigma, row_map=selected_idx[None])
         return rpn_cls_loss[0], rpn_reg_loss[0], roi_cls_loss[0], roi_reg_loss[0]
+
+    def _training_roi_head(self, rois_list, p_list, image_shape, training):
+        """pooling + RoI head of both training branches: under no_grad, unless train_roi_head -- then the pooling stays under
+        no_grad (it has no backward) and the head runs its trainable form outside it, so the two RoI losses carry a graph"""
+        with torch.no_grad():
+            roi_features = self._get_roi_features(rois_list, p_list, image_shape)
+            if not self._train_roi_head:
+                return self._roi_head(roi_features, training=training)
+        return self._get_trainable_roi_head()(roi_features)
+
+    def _get_trainable_roi_head(self):
+        raise NotImplementedError('train_roi_head=True needs a dense part with a trainable RoI head')
 
     def _get_rpn_loss(self, rpn_score, rpn_bbox_txtytwth, anchor_target_labels, anchor_target_bboxes_txtytwth,
                       anchor_target_in_weights, anchor_target_out_weights):
@@ -347,9 +359,12 @@ class ResnetV1Fpn(BaseFPN):
                  roi_training_total_num_samples=256, roi_training_max_pos_samples=64,
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3, dtype=torch.float32, device='cuda',
-                 f32_form='exact', training_targets='torch', training_losses='torch'):
+                 f32_form='exact', training_targets='torch', training_losses='torch', train_roi_head=False):
         from .fpn_detector import ResNetFpnDetector, check_caller_f32_form
         check_caller_f32_form(f32_form)
+        if train_roi_head and (dtype != torch.float32 or f32_form != 'exact'):
+            raise ValueError("ResnetV1Fpn: train_roi_head=True needs dtype=torch.float32 and f32_form='exact' (the Dense backward "
+                             "has no float16 or split-precision form), got %s, %r" % (dtype, f32_form))
         if top_down_dims != 256 or tuple(roi_feature_size) != (roi_pool_size, roi_pool_size, top_down_dims):
             raise ValueError('ResnetV1Fpn: the dense kernels are built for 256 top-down channels and %dx%dx256 RoI features'
                              % (roi_pool_size, roi_pool_size))
@@ -384,11 +399,14 @@ class ResnetV1Fpn(BaseFPN):
             prediction_max_objects_per_image=prediction_max_objects_per_image,
             prediction_max_objects_per_class=prediction_max_objects_per_class,
             prediction_nms_iou_threshold=prediction_nms_iou_threshold, prediction_score_threshold=prediction_score_threshold,
-            training_targets=training_targets, training_losses=training_losses)
+            training_targets=training_targets, training_losses=training_losses, train_roi_head=train_roi_head)
         self.dense = dense
 
     def _get_roi_head(self):
         return _Part(self._dense_ref.roi_head)
+
+    def _get_trainable_roi_head(self):
+        return self._dense_ref.roi_head_trainable
 
     def _get_extractor(self):
         return _Part(self._dense_ref.extractor)

@@ -392,6 +392,41 @@ class _FinalLayer:
         y = ops.dense(x, wpad, b32) if x.dtype == torch.float32 else ops.dense_f16_out_f32(x, wpad, b32)
         return y[:, :n1], y[:, n1:n5]
 
+    def _final_outputs_trainable(self, x):
+        """_final_outputs with a backward pass (float32): still ONE contraction on the padded concatenated weights; the padded
+        weight gets a gradient [pad64(5 C), K] and the padded bias one [pad64(5 C)], whose row slices are the gradients of
+        score / bbox (the dy of the padding columns is zero, so the padding rows' gradients are zero and go nowhere)"""
+        n1 = self.score.out_features
+        n5 = n1 + self.bbox.out_features
+        wpad, b32 = self._final_layer()
+        if not x.is_cuda or x.dtype != torch.float32 or wpad is None or wpad.dtype != torch.float32:
+            raise RuntimeError('RoI head (trainable): the last layer needs a float32 GPU activation with a multiple of 32 >= 64 '
+                               'channels (got %s %s on %s)' % (tuple(x.shape), x.dtype, x.device))
+        y = _FinalTrainable.apply(x if x.is_contiguous() else x.contiguous(), self.score.weight, self.score.bias, self.bbox.weight,
+                                  self.bbox.bias, wpad, b32)
+        return y[:, :n1], y[:, n1:n5]
+
+
+class _FinalTrainable(torch.autograd.Function):
+    """the padded final layer: ops.dense on the derived (padded, concatenated) weights forward; one ops.dense_wgrad on them
+    backward, handed out as row slices in the order (score.weight, score.bias, bbox.weight, bbox.bias)"""
+
+    @staticmethod
+    def forward(ctx, x, score_w, score_b, bbox_w, bbox_b, wpad, bpad):
+        ctx.save_for_backward(x, wpad)
+        ctx.rows = (int(score_w.shape[0]), int(score_w.shape[0]) + int(bbox_w.shape[0]))
+        return ops.dense(x, wpad, bpad)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, wpad = ctx.saved_tensors
+        n1, n5 = ctx.rows
+        dy = dy if dy.is_contiguous() else dy.contiguous()
+        dw, db = ops.dense_wgrad(dy, x)
+        dx = ops.dense_dgrad(dy, wpad) if ctx.needs_input_grad[0] else None
+        return dx, dw[:n1], db[:n1], dw[n1:n5], db[n1:n5], None, None
+
 
 class _NmsCompleteness:
     """The detectors run the proposal stage sync-free (no host check between kernels; graph-capturable) with a fixed
@@ -678,6 +713,19 @@ class ResNetFpnDetector(_NmsCompleteness, _FinalLayer, nn.Module):
     def roi_head(self, roi_features):
         """RoI features [R,7,7,256] -> (class logits [R,Ccls], box regressions [R,4 Ccls]), float32 (resnet_fpn.py:292-336)"""
         return self._final_outputs(self.head_activation(roi_features))
+
+    @_in_f32_form
+    def roi_head_trainable(self, roi_features):
+        """roi_head with a backward pass into fc1, fc2, score and bbox (float32, f32_form 'exact'): the same four layers through
+        ops.dense_trainable, outputs bit-equal to roi_head's.  The features get no gradient (RoI pooling has no backward), so
+        fc1's input gradient -- a read of its 51 MB of weights -- is never computed."""
+        if self.dtype != torch.float32 or self.f32_form != 'exact':
+            raise ValueError("roi_head_trainable needs dtype=torch.float32 and f32_form='exact' (got %s, %r)"
+                             % (self.dtype, self.f32_form))
+        x = roi_features.reshape(roi_features.shape[0], -1).to(self.dtype)
+        x = ops.dense_trainable(x, self.fc1.weight, self.fc1.bias, relu=True)
+        x = ops.dense_trainable(x, self.fc2.weight, self.fc2.bias, relu=True)
+        return self._final_outputs_trainable(x)
 
     # ---- HIP-graph replay ---------------------------------------------------------------------------
     def capture(self, batch, warmup=3):

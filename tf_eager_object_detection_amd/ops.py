@@ -910,6 +910,106 @@ def dense(x, weight, bias=None, relu=False, out=None):
     return y.view(x.shape[0], -1)
 
 
+def _dense_grad_args(who, dy, other, other_name, other_cols, y_relu):
+    """the checks dense_dgrad / dense_wgrad share (the style of _pw_args): float32 only, the exact form only, contiguous 2-D GPU
+    tensors, the kernels' shape rules -> (rows, cout)"""
+    named = [('dy', dy), (other_name, other)] + ([('y_relu', y_relu)] if y_relu is not None else [])
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError('%s: %s must be a float32 tensor (the Dense backward has no float16 form), got %s'
+                             % (who, name, getattr(t, 'dtype', type(t).__name__)))
+    if current_f32_form() != 'exact':
+        raise ValueError("%s: the Dense backward runs only under f32_form 'exact' (no split-precision backward), not %r"
+                         % (who, current_f32_form()))
+    for name, t in named:
+        if t.dim() != 2 or not t.is_contiguous():
+            raise ValueError('%s: %s must be a contiguous 2-D tensor' % (who, name))
+    for name, t in named:
+        if not t.is_cuda:
+            raise ValueError('%s: %s must be a GPU tensor' % (who, name))
+    rows, cout = int(dy.shape[0]), int(dy.shape[1])
+    if y_relu is not None and tuple(y_relu.shape) != (rows, cout):
+        raise ValueError('%s: y_relu must have the shape of dy %s, got %s' % (who, (rows, cout), tuple(y_relu.shape)))
+    if int(other.shape[0]) != other_cols(rows, cout):
+        raise ValueError('%s: %s %s does not go with dy %s' % (who, other_name, tuple(other.shape), (rows, cout)))
+    cin = int(other.shape[1])
+    if rows < 1 or cin % 32 or cin < 64 or cout % 64 or cout < 64:
+        raise ValueError('%s: rows %d must be positive, cin %d a multiple of 32 (>= 64), cout %d a multiple of 64'
+                         % (who, rows, cin, cout))
+    return rows, cin, cout
+
+
+def _dense_grad_workspace(wgrad, rows, cin, cout, device):
+    n = int(L.lib().odet_dense_grad_workspace_bytes(wgrad, rows, cin, cout))
+    if n == 0:
+        return None, 0
+    ws = L.workspace(n, device)
+    return C.c_void_p(ws.data_ptr()), n
+
+
+def dense_dgrad(dy, weight, y_relu=None, x_relu=None, out=None):
+    """The input gradient of a float32 Dense layer (odet_dense_dgrad_f32): dy [rows, cout], weight [cout, cin] (the forward's
+    own layout) -> dx [rows, cin] = dz . weight, dz = dy where y_relu > 0 else 0 (y_relu: the layer's forward output, when it
+    had a ReLU); x_relu (the forward output of the layer below, [rows, cin]) keeps dx only where it is > 0."""
+    rows, cin, cout = _dense_grad_args('dense_dgrad', dy, weight, 'weight', lambda r, c: c, y_relu)
+    if x_relu is not None and (not isinstance(x_relu, torch.Tensor) or x_relu.dtype != torch.float32 or not x_relu.is_cuda
+                               or tuple(x_relu.shape) != (rows, cin) or not x_relu.is_contiguous()):
+        raise ValueError('dense_dgrad: x_relu must be a contiguous float32 GPU tensor of shape %s' % ((rows, cin),))
+    out = _out(out, (rows, cin), torch.float32, dy.device)
+    wsp, wsn = _dense_grad_workspace(0, rows, cin, cout, dy.device)
+    L.call('odet_dense_dgrad_f32', L.dptr(dy), L.dptr(weight), L.dptr(y_relu), L.dptr(x_relu), L.dptr(out), rows, cin, cout,
+           wsp, wsn, L.stream())
+    return out
+
+
+def dense_wgrad(dy, x, y_relu=None, with_bias=True, out=None):
+    """The parameter gradients of a float32 Dense layer (odet_dense_wgrad_f32): dy [rows, cout], x [rows, cin] (the layer's
+    input) -> (dw [cout, cin] = dz^T . x, db [cout] = column sums of dz, or None without with_bias); dz as in dense_dgrad."""
+    rows, cin, cout = _dense_grad_args('dense_wgrad', dy, x, 'x', lambda r, c: r, y_relu)
+    dw = _out(out, (cout, cin), torch.float32, dy.device)
+    db = torch.empty((cout,), dtype=torch.float32, device=dy.device) if with_bias else None
+    wsp, wsn = _dense_grad_workspace(1, rows, cin, cout, dy.device)
+    L.call('odet_dense_wgrad_f32', L.dptr(dy), L.dptr(x), L.dptr(y_relu), L.dptr(dw), L.dptr(db), rows, cin, cout, wsp, wsn,
+           L.stream())
+    return dw, db
+
+
+class _DenseTrainable(torch.autograd.Function):
+    """ops.dense forward; odet_dense_wgrad_f32 (and, only when the input needs a gradient, odet_dense_dgrad_f32) backward"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        y = dense(x, weight, bias, relu)
+        ctx.relu = bool(relu)
+        ctx.save_for_backward(x, weight, y if relu else None)
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight, y = ctx.saved_tensors
+        dy = dy if dy.is_contiguous() else dy.contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+            dw, db = dense_wgrad(dy, x, y, with_bias=ctx.has_bias and ctx.needs_input_grad[2])
+            dw = dw if ctx.needs_input_grad[1] else None
+        if ctx.needs_input_grad[0]:
+            dx = dense_dgrad(dy, weight, y)
+        return dx, dw, db, None
+
+
+def dense_trainable(x, weight, bias, relu=False):
+    """ops.dense with a backward pass (float32, f32_form 'exact'): the forward is `dense`, bit for bit; `.backward()` leaves
+    weight.grad [cout, cin] and bias.grad [cout] contiguous in the variables' shapes (what training.train_step takes), and
+    computes the input gradient only when x requires one."""
+    if x.dim() != 2 or x.dtype != torch.float32 or weight.dtype != torch.float32 or weight.dim() != 2 or not weight.is_contiguous():
+        raise ValueError('dense_trainable: x [rows, cin] and weight [cout, cin] must be float32, weight contiguous')
+    if current_f32_form() != 'exact':
+        raise ValueError("dense_trainable: the Dense backward runs only under f32_form 'exact', not %r" % current_f32_form())
+    return _DenseTrainable.apply(x if x.is_contiguous() else x.contiguous(), weight, bias, bool(relu))
+
+
 def lateral_merge(x, weight, bias, top, out=None):
     """The FPN neck's lateral 1x1 convolution with the top-down merge in its epilogue (odet_lateral_merge_f16 / _f32;
     resnet_fpn.py:385-398): 0.5 * resize_bilinear(top) + 0.5 * (x . w^T + bias); ``x`` [B,H,W,cin], ``top`` [B,h,w,cout]
