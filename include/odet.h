@@ -999,7 +999,12 @@ int odet_proposal_target(const float* rois, const int32_t* roi_counts, int max_r
  * label-1 rows and their 4 coordinates of l), with inside = 1 and outside = float32(1) / float32(n) (dim=[0,1]: a sum).
  * row_grad_scores [batch,S,2] = (p_j - [j == label]) / float32(n) and row_grad_deltas [batch,S,4] = the smooth-L1 gradient
  * (0 on label-0 rows): d loss / d (row of the head outputs) at upstream gradient 1.  Rows >= n are 0.  An image whose counts
- * row is -1 or whose n is 0 has losses 0 and gradients 0.  All pointers are required. */
+ * row is -1 or whose n is 0 has losses 0 and gradients 0.  All pointers are required.
+ * Counts and indices that odet_anchor_target never writes are clamped, not trusted: a negative counts[3] or counts[4] empties
+ * the image; then counts[3] = min(counts[3], S) and n = min(counts[3] + counts[4], S).  A row r < n whose sample_idx lies
+ * outside 0..N-1 adds nothing to either loss and has zero row gradients, but still counts in n (the divisor and outside);
+ * odet_rpn_loss_backward skips every such index among all S entries and writes every other one (a row >= n with
+ * upstream * 0, a zero that carries the upstream's sign). */
 int odet_rpn_loss(const float* scores, const float* deltas, int num_anchors, int batch, int layout,
                   int anchors_per_location, const int32_t* sample_idx, const float* sample_targets, const int32_t* counts,
                   int total_num_samples, float sigma, float* losses, float* row_grad_scores, float* row_grad_deltas,
@@ -1019,7 +1024,10 @@ int odet_rpn_loss_backward(const int32_t* sample_idx, const float* row_grad_scor
  * losses [batch,2] = (float32(sum over head rows of CE) / float32(max(rows,1)), float32(sum over head rows of the row's
  * smooth-L1 sum) / float32(max(rows,1))).  grad_scores [batch,R,C] = u_cls * ((p_j - [j == label]) / float32(rows)),
  * grad_deltas [batch,R,4C] = u_reg * (smooth-L1 gradient / float32(rows)), (u_cls, u_reg) = upstream[b] (device float32
- * [batch,2]) or (1, 1) when upstream is null.  losses, grad_scores and grad_deltas are each nullable. */
+ * [batch,2]) or (1, 1) when upstream is null.  losses, grad_scores and grad_deltas are each nullable.
+ * rows is clamped to 0..S (a counts row of -1: nothing takes part).  A head row whose label is outside 0..C-1 (a stray -1 or
+ * C) gets gradient 0 like a row without a target, and its target row still counts in rows.  With num_rows == 0 scores and
+ * deltas may be NULL and the losses are 0. */
 int odet_roi_loss(const float* scores, const float* deltas, int num_rows, int num_classes, int batch,
                   const int32_t* final_labels, const float* targets, const float* inside, const float* outside,
                   const int32_t* counts, int total_num_samples, const int32_t* row_map, float sigma,

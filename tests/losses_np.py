@@ -44,17 +44,26 @@ def smooth_l1(pred, tgt, inside, outside, sigma):
     return outside * in_loss, outside * inside * slope, sign
 
 
-def softmax_rows(x, label):
+def softmax_rows(x, label, class_sum=ordered_sum):
     """x float32 [n,C], label int [n] -> (CE [n], p [n,C], z_label [n]) with s summed over the classes in ascending order"""
     x = np.asarray(x, F32)
     n = x.shape[0]
     if n == 0:
         return np.zeros(0, F32), np.zeros(x.shape, F32), np.zeros(0, F32)
-    z = x - x.max(axis=1, keepdims=True)
+    with np.errstate(over='ignore'):                                 # (logits of +-3e38: the gap is -inf, e is 0)
+        z = x - x.max(axis=1, keepdims=True)
     e = exp32(z)
-    sf = ordered_sum(e, axis=1).astype(F32)
+    sf = np.asarray(class_sum(e, axis=1)).astype(F32)
     zl = z[np.arange(n), label]
     return log32(sf) - zl, e / sf[:, None], zl
+
+
+# the sums of a loss by role, in the header's orders.  tests/order_data.py swaps one for a wrong order to prove that its data
+# tells the two apart; nothing else passes `sums`.
+def _header_sums(sums):
+    out = dict(classes=ordered_sum, coords=ordered_sum, columns=roi_row_sum, rows_ce=ordered_sum, rows_reg=ordered_sum)
+    out.update(sums or {})
+    return out
 
 
 def fpn_view(scores, layout, A):
@@ -72,43 +81,57 @@ def from_fpn_view(rows, layout, A):
     return rows.reshape(-1, A, 2).transpose(0, 2, 1).reshape(-1)
 
 
-def rpn_loss(scores, deltas, sample_idx, sample_targets, counts, sigma, layout=LAYOUT_FPN, A=1):
-    """one image of odet_rpn_loss -> dict(losses [2], row_grad_scores [S,2], row_grad_deltas [S,4], z_label, sign)"""
+def rpn_loss(scores, deltas, sample_idx, sample_targets, counts, sigma, layout=LAYOUT_FPN, A=1, sums=None):
+    """one image of odet_rpn_loss -> dict(losses [2], row_grad_scores [S,2], row_grad_deltas [S,4], z_label, sign, and the
+    terms of the sums: ce_rows [n] float32, reg_terms [n,4] float32).  The header's clamps: a negative count empties the
+    image, kfg = min(kfg, S), n = min(kfg + kbg, S); a row r < n whose index lies outside 0..N-1 adds nothing and has zero row
+    gradients, but counts in n."""
+    sm = _header_sums(sums)
     x = fpn_view(np.asarray(scores, F32), layout, A)
     deltas = np.asarray(deltas, F32).reshape(-1, 4)
-    S = len(sample_idx)
+    N, S = deltas.shape[0], len(sample_idx)
     kfg, kbg = int(counts[3]), int(counts[4])
     if kfg < 0 or kbg < 0:
         kfg = kbg = 0
-    n = kfg + kbg
+    kfg = min(kfg, S)
+    n = min(kfg + kbg, S)
     nf = F32(max(n, 1))
     row_gs, row_gd = np.zeros((S, 2), F32), np.zeros((S, 4), F32)
     idx = np.asarray(sample_idx[:n], np.int64)
-    label = (np.arange(n) < kfg).astype(np.int64)
-    ce, p, zl = softmax_rows(x[idx], label)
-    onehot = np.zeros((n, 2), F32)
-    onehot[np.arange(n), label] = 1
-    row_gs[:n] = (p - onehot) / nf
+    v = np.nonzero((idx >= 0) & (idx < N))[0]                        # the rows that take part
+    label = (v < kfg).astype(np.int64)
+    ce, p, zl = softmax_rows(x[idx[v]], label, sm['classes'])
+    onehot = np.zeros((len(v), 2), F32)
+    onehot[np.arange(len(v)), label] = 1
+    row_gs[v] = (p - onehot) / nf
     outside = F32(1) / nf
-    terms, grad, sign = smooth_l1(deltas[idx[:kfg]], np.asarray(sample_targets, F32)[:kfg], F32(1), outside, sigma)
-    row_gd[:kfg] = grad
-    cls = F32(ordered_sum(ce)) / nf
-    reg = F32(ordered_sum(ordered_sum(terms, axis=1)))           # the 4 coordinates of a row, then the rows
-    return dict(losses=np.array([cls, reg], F32), row_grad_scores=row_gs, row_grad_deltas=row_gd, z_label=zl, sign=sign)
+    f = v[v < kfg]
+    terms, grad, sign = smooth_l1(deltas[idx[f]], np.asarray(sample_targets, F32).reshape(-1, 4)[f], F32(1), outside, sigma)
+    row_gd[f] = grad
+    ce_rows, reg_terms = np.zeros(n, F32), np.zeros((n, 4), F32)
+    ce_rows[v] = ce
+    reg_terms[f] = terms
+    cls = F32(sm['rows_ce'](ce_rows)) / nf
+    reg = F32(sm['rows_reg'](sm['coords'](reg_terms, axis=1)))       # the 4 coordinates of a row, then the rows
+    return dict(losses=np.array([cls, reg], F32), row_grad_scores=row_gs, row_grad_deltas=row_gd, z_label=zl, sign=sign,
+                ce_rows=ce_rows, reg_terms=reg_terms, n=n)
 
 
 def rpn_loss_backward(sample_idx, row_grad_scores, row_grad_deltas, upstream, N, layout=LAYOUT_FPN, A=1):
-    """one image of odet_rpn_loss_backward -> (grad_scores flat [2N] in `layout`, grad_deltas [N,4])"""
+    """one image of odet_rpn_loss_backward -> (grad_scores flat [2N] in `layout`, grad_deltas [N,4]): every one of the S rows
+    whose index lies in 0..N-1 is written (a row >= n with upstream * 0, which is -0 under a negative upstream), an index
+    outside is skipped"""
     rows, gd = np.zeros((N, 2), F32), np.zeros((N, 4), F32)
-    k = np.asarray(sample_idx) >= 0
+    k = (np.asarray(sample_idx) >= 0) & (np.asarray(sample_idx) < N)
     idx = np.asarray(sample_idx)[k]
     rows[idx] = F32(upstream[0]) * np.asarray(row_grad_scores, F32)[k]
     gd[idx] = F32(upstream[1]) * np.asarray(row_grad_deltas, F32)[k]
     return from_fpn_view(rows, layout, A), gd
 
 
-def roi_row_sum(terms):
+def roi_row_sum(terms, axis=1):
     """the 4C columns of every row as 64 partial sums (partial l: columns l, l + 64, ... ascending), added in ascending l"""
+    assert axis == 1
     r, w = terms.shape
     pad = np.zeros((r, -(-w // 64) * 64), F64)
     pad[:, :w] = terms
@@ -124,8 +147,10 @@ def _roi_rows(R, labels, counts, row_map, C):
     return rows, m, ok, lab
 
 
-def roi_loss(scores, deltas, labels, targets, inside, outside, counts, sigma, row_map=None, upstream=None):
-    """one image of odet_roi_loss -> dict(losses [2], grad_scores [R,C], grad_deltas [R,4C], z_label, sign)"""
+def roi_loss(scores, deltas, labels, targets, inside, outside, counts, sigma, row_map=None, upstream=None, sums=None):
+    """one image of odet_roi_loss -> dict(losses [2], grad_scores [R,C], grad_deltas [R,4C], z_label, sign, and the terms of
+    the row sums: ce_rows [R] float32, reg_rows [R] float64, target_row [R]).  rows = min(max(counts[3], 0), S)."""
+    sm = _header_sums(sums)
     scores, deltas = np.asarray(scores, F32), np.asarray(deltas, F32)
     R, C = scores.shape
     rows, m, ok, lab = _roi_rows(R, labels, counts, row_map, C)
@@ -134,7 +159,7 @@ def roi_loss(scores, deltas, labels, targets, inside, outside, counts, sigma, ro
     v = np.nonzero(ok)[0]
     ce_all, reg_all = np.zeros(R, F32), np.zeros(R, F64)
     gs, gd = np.zeros((R, C), F32), np.zeros((R, 4 * C), F32)
-    ce, p, zl = softmax_rows(scores[v], lab[v])
+    ce, p, zl = softmax_rows(scores[v], lab[v], sm['classes'])
     onehot = np.zeros((len(v), C), F32)
     onehot[np.arange(len(v)), lab[v]] = 1
     gs[v] = up[0] * ((p - onehot) / nf)
@@ -144,11 +169,12 @@ def roi_loss(scores, deltas, labels, targets, inside, outside, counts, sigma, ro
     gd[v] = up[1] * (grad / nf)
     ce_all[v] = ce
     if len(v):
-        reg_all[v] = roi_row_sum(terms)
-    cls = F32(ordered_sum(ce_all)) / nf
-    reg = F32(ordered_sum(reg_all)) / nf
+        reg_all[v] = sm['columns'](terms, axis=1)
+    cls = F32(sm['rows_ce'](ce_all)) / nf
+    reg = F32(sm['rows_reg'](reg_all)) / nf
     return dict(losses=np.array([cls, reg], F32), grad_scores=gs, grad_deltas=gd, z_label=zl, sign=sign,
-                active=np.asarray(inside, F32)[mv] != 0)
+                active=np.asarray(inside, F32)[mv] != 0, ce_rows=ce_all, reg_rows=reg_all, target_row=np.where(ok, m, -1),
+                rows=rows)
 
 
 # ---- the same formulas in float64 ----------------------------------------------------------------------------------------

@@ -320,7 +320,8 @@ extern "C" int odet_roi_loss(const float* scores, const float* deltas, int num_r
   if (total_num_samples < 1 || total_num_samples > LS_MAX_SAMPLES)
     return odet_set_error(ODET_E_LIMIT, "odet_roi_loss: total_num_samples %d outside 1..%d", total_num_samples, LS_MAX_SAMPLES);
   if (batch == 0) return ODET_OK;
-  ODET_REQUIRE(scores && deltas && final_labels && targets && inside && outside && counts, "odet_roi_loss: null pointer");
+  ODET_REQUIRE((num_rows == 0 || (scores && deltas)) && final_labels && targets && inside && outside && counts,
+               "odet_roi_loss: null pointer");             // (no head row: the losses are 0, nothing of the head is read)
   ODET_REQUIRE(sigma > 0.0f, "odet_roi_loss: sigma must be positive");
   if (!losses && !grad_scores && !grad_deltas) return ODET_OK;
   RoiLossArgs a;
