@@ -40,7 +40,8 @@ extern "C" {
  * (odet_anchor_target, odet_proposal_target) and the fused training losses with their gradients (odet_rpn_loss,
  * odet_rpn_loss_backward, odet_roi_loss) and odet_preprocess_train (the training input stage) and the training step
  * (odet_opt_step, odet_l2_loss, odet_opt_partials_bytes with the odet_opt_*_t records) and the float32 Dense backward
- * (odet_dense_dgrad_f32, odet_dense_wgrad_f32, odet_dense_grad_workspace_bytes); no existing entry point or struct changed. */
+ * (odet_dense_dgrad_f32, odet_dense_wgrad_f32, odet_dense_grad_workspace_bytes) and the RoI pooling backward
+ * (odet_roi_pool_argmax, odet_roi_pool_backward); no existing entry point or struct changed. */
 #define ODET_VERSION 103
 
 #define ODET_OK 0
@@ -1155,6 +1156,33 @@ int odet_dense_dgrad_f32(const float* dy, const float* w, const float* y_relu, c
                          int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream);
 int odet_dense_wgrad_f32(const float* dy, const float* x, const float* y_relu, float* dw, float* db, int rows, int cin, int cout,
                          void* workspace, size_t workspace_bytes, odet_stream_t stream);
+
+/* ---- RoI pooling backward, float32 (added within 103) --------------------------------------------------------------
+ * The gradient of odet_roi_pool with respect to the float32 feature maps (TF r1.13 CropAndResizeGradImage and the max-pool
+ * gradient), one image per call, any norm_mode x pool_mode the forward accepts; the boxes get no gradient.  crop = P
+ * (POOL_NONE) or 2P; ty(r,i), tx(r,j) are the forward's own sample rows / columns (same normalisation, level clamp, count_dev
+ * clamped to n, pad remap; an extrapolated sample never becomes an address).
+ *   odet_roi_pool_argmax (POOL_MAX2): sel [n,P,P,C] uint8 -- which sample of each bin and channel the forward's max took: the
+ *     first in the order (0,0),(0,1),(1,0),(1,1) that compares equal to the pooled value (the first-maximum rule of TF's and
+ *     torch's max-pool gradients); 0..3 = 2*di+dj, 4 = none (an all-NaN bin; rows at or beyond the count).  levels = the maps.
+ *   odet_roi_pool_backward: levels[i].data = dx of level i ([H,W,C] float32, written); dy [n,P,P,C]; sel required for
+ *     POOL_MAX2, NULL otherwise.  Upstream per sample g = dy (NONE), dy * 0.25f (AVG2), dy for the selected sample only (MAX2).
+ *     A sample inside the map adds wx * (wy * g) -- two float32 multiplies, a separate add, no FMA -- to up to four cells
+ *     (wy = 1 - ty.lerp on ty.lo, ty.lerp on ty.hi; likewise wx); when lo == hi both are added.
+ * Order of sums: dx[l][y][x][c] starts at +0.0f and receives its contributions in ascending (RoI r; sample row i; top before
+ * bottom; sample column j; left before right), RoIs with r < count on level l only -- a function of the data's indices, no
+ * atomics; bit-reproducible and restated on the CPU (tests/roi_grad_np.py).  Every element of every dx is written exactly once
+ * (cells nothing taps: +0.0f); nothing is read from dx, no memset, no workspace.  dy rows at or beyond the count are ignored.
+ * Errors, all before any HIP call: ODET_E_INVALID (null pointer, num_levels outside 1..ODET_MAX_LEVELS, C no multiple of 4,
+ * unknown mode, sel against pool_mode, misaligned pointer: maps / dx / dy / rois 16 bytes, sel 4), ODET_E_LIMIT (n > 8192,
+ * pool_size > 16, a level of 2 GiB or more).  n == 0: argmax is a no-op, backward writes zeros.  No allocation, no host read
+ * (graph-capturable). */
+int odet_roi_pool_argmax(const odet_level_t* levels, int num_levels, int C, const float* rois, const int32_t* roi_level, int n,
+                         const int32_t* count_dev, int norm_mode, int image_h, int image_w, int pool_size, uint8_t* sel,
+                         odet_stream_t stream);
+int odet_roi_pool_backward(const odet_level_t* levels, int num_levels, int C, const float* rois, const int32_t* roi_level, int n,
+                           const int32_t* count_dev, int norm_mode, int image_h, int image_w, int pool_size, int pool_mode,
+                           const float* dy, const uint8_t* sel, odet_stream_t stream);
 
 #ifdef __cplusplus
 }

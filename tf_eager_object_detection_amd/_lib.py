@@ -225,6 +225,8 @@ SIGNATURES = {
     'odet_dense_grad_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'odet_dense_dgrad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     'odet_dense_wgrad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    'odet_roi_pool_argmax': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'odet_roi_pool_backward': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
 }
 
 

@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "conv_diag.h"   // (odet_internal.h; in the diagnostic build the plan-only switch)
+#include "roi_taps.h"    // Axis, Tap, make_axis, make_tap, roi_norm_box, lerp_tap: shared with the backward (roi_grad.hip)
 
 struct RoiParams {
   const void* data[ODET_MAX_BATCH][ODET_MAX_LEVELS];    // [image of the batch][pyramid level]; float32 or float16
@@ -65,58 +66,6 @@ struct RoiParams {
   int roi_groups;     // > 0 (slices > 1 and the image's XCDs are a multiple of the slices): an XCD serves ONE slice for one of
                       // roi_groups contiguous parts of the processing order (rois_per_xcd RoIs each)
 };
-
-struct Axis {
-  float start;   // in_(0)
-  float scale;   // per-sample step
-  float limit;   // dim - 1 (in sampled-map coordinates)
-  float single;  // crop == 1: the one sample coordinate
-};
-
-// TF crop_and_resize_op.cc: in = lo_n * (dim-1) + i * scale, scale = (hi_n - lo_n)*(dim-1)/(crop-1)
-__device__ __forceinline__ Axis make_axis(float lo_n, float hi_n, int dim, int crop) {
-  Axis a;
-  a.limit = (float)(dim - 1);
-  a.scale = (crop > 1) ? (hi_n - lo_n) * a.limit / (float)(crop - 1) : 0.0f;
-  a.start = lo_n * a.limit;
-  a.single = 0.5f * (lo_n + hi_n) * a.limit;   // crop == 1 path
-  return a;
-}
-
-struct Tap {      // one sample along one axis
-  bool ok;        // TF: not extrapolated (0 <= in <= dim-1; NaN fails)
-  int lo, hi;     // floor / ceil cell (after the SYMMETRIC-pad remap for the padded tensorpack mode)
-  float lerp;
-};
-
-template <bool PAD>
-__device__ __forceinline__ Tap make_tap(const Axis& a, int i, int crop, int dim) {
-  Tap t;
-  const float in = (crop > 1) ? a.start + (float)i * a.scale : a.single;
-  // TF: extrapolate when (in < 0 || in > dim-1).  Written as the positive test so that a NaN
-  // coordinate can never turn into a tap index.
-  t.ok = (in >= 0.0f && in <= a.limit);
-  const float f = floorf(in);
-  t.lerp = in - f;
-  int lo = (int)f, hi = (int)ceilf(in);
-  if (PAD) {   // SYMMETRIC 1-px pad == edge replicate: padded[i] = src[clamp(i-1)]
-    lo = min(max(lo - 1, 0), dim - 1);
-    hi = min(max(hi - 1, 0), dim - 1);
-  }
-  if (!t.ok) { lo = 0; hi = 0; }     // never an address
-  t.lo = lo; t.hi = hi;
-  return t;
-}
-
-__device__ __forceinline__ float4 lerp_tap(float4 tl, float4 tr, float4 bl, float4 br, float xw, float yw) {
-  float4 r;
-  float t, b;
-  t = tl.x + (tr.x - tl.x) * xw; b = bl.x + (br.x - bl.x) * xw; r.x = t + (b - t) * yw;
-  t = tl.y + (tr.y - tl.y) * xw; b = bl.y + (br.y - bl.y) * xw; r.y = t + (b - t) * yw;
-  t = tl.z + (tr.z - tl.z) * xw; b = bl.z + (br.z - bl.z) * xw; r.z = t + (b - t) * yw;
-  t = tl.w + (tr.w - tl.w) * xw; b = bl.w + (br.w - bl.w) * xw; r.w = t + (b - t) * yw;
-  return r;
-}
 
 template <int POOL>
 __device__ __forceinline__ float4 pool4(const float4 (&v)[2][2]) {
@@ -551,33 +500,10 @@ __global__ void __launch_bounds__(1024) k_roi_pool(RoiParams p) {
   const int H = p.H[lvl], W = p.W[lvl];
   const int crop = P * S;
 
-  // normalised box (y1,x1,y2,x2) exactly as the reference builds it
-  float y1n, x1n, y2n, x2n;
-  int Hs = H, Ws = W;     // dims of the map crop_and_resize samples (padded for TP_ALIGN)
-  if (NORM == ODET_ROI_NORM_IMAGE) {
-    y1n = roi.y / p.image_h; x1n = roi.x / p.image_w;            // roi_pooling.py:30-35
-    y2n = roi.w / p.image_h; x2n = roi.z / p.image_w;
-  } else if (NORM == ODET_ROI_NORM_STRIDE) {
-    const float st = p.stride[lvl];
-    const float hm = (float)(H - 1), wm = (float)(W - 1);
-    y1n = (roi.y / st) / hm; x1n = (roi.x / st) / wm;            // roi_pooling.py:64,69-74
-    y2n = (roi.w / st) / hm; x2n = (roi.z / st) / wm;
-  } else {
-    const float st = p.stride[lvl];
-    const float off = PAD ? 1.0f : 0.0f;
-    if (PAD) { Hs = H + 2; Ws = W + 2; }                         // roi_pooling.py:100
-    float x0 = roi.x / st, y0 = roi.y / st;                      // :175
-    float x1 = roi.z / st, y1 = roi.w / st;
-    if (PAD) { x0 = x0 + off; y0 = y0 + off; x1 = x1 + off; y1 = y1 + off; }   // :101
-    const float cs = (float)crop;
-    const float sw = (x1 - x0) / cs, sh = (y1 - y0) / cs;        // :120-121
-    const float imh = (float)(Hs - 1), imw = (float)(Ws - 1);
-    x1n = (x0 + sw / 2.0f - 0.5f) / imw;                         // :124
-    y1n = (y0 + sh / 2.0f - 0.5f) / imh;                         // :125
-    const float nw = sw * (float)(crop - 1) / imw;               // :127
-    const float nh = sh * (float)(crop - 1) / imh;               // :128
-    y2n = y1n + nh; x2n = x1n + nw;                              // :130
-  }
+  // normalised box (y1,x1,y2,x2) exactly as the reference builds it (roi_taps.h)
+  const RoiBox nb = roi_norm_box<NORM>(roi, H, W, NORM == ODET_ROI_NORM_IMAGE ? 0.0f : p.stride[lvl], p.image_h, p.image_w, crop);
+  const int Hs = nb.Hs, Ws = nb.Ws;     // dims of the map crop_and_resize samples (padded for TP_ALIGN)
+  const float y1n = nb.y1n, x1n = nb.x1n, y2n = nb.y2n, x2n = nb.x2n;
   const Axis ay = make_axis(y1n, y2n, Hs, crop);
   const Axis ax = make_axis(x1n, x2n, Ws, crop);
   const int Hdim = PAD ? H : Hs, Wdim = PAD ? W : Ws;

@@ -12,7 +12,8 @@ Every tensor op between the layers that the reference delegates to TF (softmax, 
 the GPU; every detection op is a HIP kernel behind the C ABI.  Training (`training=True`) returns the four losses of the
 forward pass (:232-264) on the target layers of this package; the dense kernels are inference kernels (no backward), except
 the FPN RoI head with `train_roi_head=True` (float32, exact form): its four Dense layers then run ops.dense_trainable and the two
-RoI losses carry a graph into fc1, fc2, score and bbox."""
+RoI losses carry a graph into fc1, fc2, score and bbox -- and, when the maps handed to the pooling require a gradient, through
+ops.roi_pool_trainable into those maps (the models' own maps never do: the neck and the extractor have no backward yet)."""
 import torch
 
 from .. import ops
@@ -118,7 +119,7 @@ class BaseFPN(torch.nn.Module):
             num_post_nms_train=rpn_proposal_num_post_nms_train, num_pre_nms_test=rpn_proposal_num_pre_nms_test,
             num_post_nms_test=rpn_proposal_num_post_nms_test, nms_iou_threshold=rpn_proposal_nms_iou_threshold,
             target_means=rpn_proposal_means, target_stds=rpn_proposal_stds)
-        self._roi_pooling = RoiPoolingCropAndResize2(pool_size=roi_pool_size)
+        self._roi_pooling = RoiPoolingCropAndResize2(pool_size=roi_pool_size, trainable=self._train_roi_head)
         self._roi_head = self._get_roi_head()
         # training_targets: 'torch' = AnchorTarget / ProposalTarget (generator-driven sampling), 'hip' = the fused stage
         self._anchor_target, self._proposal_target = training_target_layers(
@@ -248,8 +249,13 @@ class BaseFPN(torch.nn.Module):
         return rpn_cls_loss[0], rpn_reg_loss[0], roi_cls_loss[0], roi_reg_loss[0]
 
     def _training_roi_head(self, rois_list, p_list, image_shape, training):
-        """pooling + RoI head of both training branches: under no_grad, unless train_roi_head -- then the pooling stays under
-        no_grad (it has no backward) and the head runs its trainable form outside it, so the two RoI losses carry a graph"""
+        """pooling + RoI head of both training branches: under no_grad, unless train_roi_head -- then the head runs its trainable
+        form outside it, so the two RoI losses carry a graph.  The pooling stays under no_grad as long as no map of p_list requires
+        a gradient (the models' own maps never do); when one does, the pooling layer takes its trainable form, the head's first
+        layer receives an input that requires a gradient and computes fc1's input gradient, and odet_roi_pool_backward carries
+        it into the maps."""
+        if self._train_roi_head and any(isinstance(p, torch.Tensor) and p.requires_grad for p in p_list):
+            return self._get_trainable_roi_head()(self._get_roi_features(rois_list, p_list, image_shape))
         with torch.no_grad():
             roi_features = self._get_roi_features(rois_list, p_list, image_shape)
             if not self._train_roi_head:

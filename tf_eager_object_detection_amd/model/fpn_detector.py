@@ -717,8 +717,10 @@ class ResNetFpnDetector(_NmsCompleteness, _FinalLayer, nn.Module):
     @_in_f32_form
     def roi_head_trainable(self, roi_features):
         """roi_head with a backward pass into fc1, fc2, score and bbox (float32, f32_form 'exact'): the same four layers through
-        ops.dense_trainable, outputs bit-equal to roi_head's.  The features get no gradient (RoI pooling has no backward), so
-        fc1's input gradient -- a read of its 51 MB of weights -- is never computed."""
+        ops.dense_trainable, outputs bit-equal to roi_head's.  Features that require no gradient (the pooling of the models' own
+        maps) cost nothing more: fc1's input gradient -- a read of its 51 MB of weights -- is then never computed.  Features from
+        ops.roi_pool_trainable require one: fc1's dense_dgrad produces the [n,P,P,C] gradient that odet_roi_pool_backward
+        carries into the feature maps."""
         if self.dtype != torch.float32 or self.f32_form != 'exact':
             raise ValueError("roi_head_trainable needs dtype=torch.float32 and f32_form='exact' (got %s, %r)"
                              % (self.dtype, self.f32_form))

@@ -1,7 +1,11 @@
 """RoI feature extraction -- counterpart of the reference's object_detection/model/roi_pooling.py.
 
 All three reference layers map onto ONE fused HIP kernel (odet_roi_pool): TF crop_and_resize
-sampling + the 2x2 max / avg pool, without materialising the [R,14,14,C] crops."""
+sampling + the 2x2 max / avg pool, without materialising the [R,14,14,C] crops.
+
+`trainable=True` (a constructor argument of the layers, a keyword of the functions; default False = the plain path): when the
+feature map requires a gradient the call goes through ops.roi_pool_trainable -- the same forward bits, and a graph whose
+backward is odet_roi_pool_backward into the map (float32 only; the RoIs get none, as the reference stops it: roi_pooling.py:78)."""
 import torch
 
 from .. import ops
@@ -22,17 +26,31 @@ def _spatial_order(feature_map, rois, stride):
     return ops.roi_order(rois, None, (max(1, int(round(h * float(stride)))), max(1, int(round(w * float(stride))))))
 
 
+def _wants_grad(trainable, maps):
+    return bool(trainable) and any(isinstance(m, torch.Tensor) and m.requires_grad for m in maps)
+
+
+def _pool_trainable(maps, rois, roi_level, norm_mode, pool_size, pool_mode, **kw):
+    """the trainable form records a graph whatever the caller's grad mode (the layers' forward is decorated no_grad)"""
+    with torch.enable_grad():
+        return ops.roi_pool_trainable(list(maps), rois, roi_level, norm_mode, pool_size, pool_mode, **kw)
+
+
 class RoiPoolingCropAndResize2(torch.nn.Module):
     """reference model/roi_pooling.py:8-42 (FPN variant: boxes normalised by the IMAGE size,
     always crop 2P + 2x2 max-pool)."""
 
-    def __init__(self, pool_size):
+    def __init__(self, pool_size, trainable=False):
         super().__init__()
         self._pool_size = pool_size
+        self._trainable = bool(trainable)
 
     @torch.no_grad()
     def forward(self, inputs, training=None, mask=None):
         shared_layers, rois, image_shape = inputs
+        if _wants_grad(self._trainable, [shared_layers]):
+            return _pool_trainable([shared_layers], rois, None, ops.ROI_NORM_IMAGE, self._pool_size, ops.ROI_POOL_MAX2,
+                                   image_shape=image_shape)
         return ops.roi_pool([shared_layers], rois, None, ops.ROI_NORM_IMAGE, self._pool_size, ops.ROI_POOL_MAX2,
                             image_shape=image_shape)
 
@@ -43,33 +61,41 @@ class RoiPoolingCropAndResize(torch.nn.Module):
     """reference model/roi_pooling.py:45-90 (boxes / stride / (dim-1); crop 2P + max-pool when
     ``max_pooling_flag`` else crop P)."""
 
-    def __init__(self, pool_size, max_pooling_flag=True):
+    def __init__(self, pool_size, max_pooling_flag=True, trainable=False):
         super().__init__()
         self._pool_size = pool_size
         self._max_pooling_flag = max_pooling_flag
+        self._trainable = bool(trainable)
 
     @torch.no_grad()
     def forward(self, inputs, training=None, mask=None):
         shared_layers, rois, extractor_stride = inputs
         mode = ops.ROI_POOL_MAX2 if self._max_pooling_flag else ops.ROI_POOL_NONE
+        if _wants_grad(self._trainable, [shared_layers]):
+            return _pool_trainable([shared_layers], rois, None, ops.ROI_NORM_STRIDE, self._pool_size, mode,
+                                   strides=[float(extractor_stride)])
         return ops.roi_pool([shared_layers], rois, None, ops.ROI_NORM_STRIDE, self._pool_size, mode,
                             strides=[float(extractor_stride)], order=_spatial_order(shared_layers, rois, extractor_stride))
 
     call = forward
 
 
-def crop_and_resize(image, boxes, box_ind, crop_size, pad_border=True):
+def crop_and_resize(image, boxes, box_ind, crop_size, pad_border=True, trainable=False):
     """reference model/roi_pooling.py:93-137 (tensorpack-style aligned crop).  ``boxes`` are in
     feature-map coordinates; ``box_ind`` must be all zeros (batch = 1, as everywhere in the
     reference: roi_pooling.py:28,66,152)."""
     assert isinstance(crop_size, int), crop_size
     mode = ops.ROI_NORM_TP_ALIGN if pad_border else 3
+    if _wants_grad(trainable, [image]):
+        return _pool_trainable([image], boxes, None, mode, crop_size, ops.ROI_POOL_NONE, strides=[1.0])
     return ops.roi_pool([image], boxes, None, mode, crop_size, ops.ROI_POOL_NONE, strides=[1.0],
                         order=_spatial_order(image, boxes, 1.0))
 
 
-def roi_align(featuremap, boxes, resolution):
+def roi_align(featuremap, boxes, resolution, trainable=False):
     """reference model/roi_pooling.py:140-155: 4 samples per bin (crop 2*resolution) + 2x2 avg."""
+    if _wants_grad(trainable, [featuremap]):
+        return _pool_trainable([featuremap], boxes, None, ops.ROI_NORM_TP_ALIGN, resolution, ops.ROI_POOL_AVG2, strides=[1.0])
     return ops.roi_pool([featuremap], boxes, None, ops.ROI_NORM_TP_ALIGN, resolution, ops.ROI_POOL_AVG2,
                         strides=[1.0], order=_spatial_order(featuremap, boxes, 1.0))
 
@@ -77,13 +103,17 @@ def roi_align(featuremap, boxes, resolution):
 class RoiPoolingRoiAlign(torch.nn.Module):
     """reference model/roi_pooling.py:158-177."""
 
-    def __init__(self, pool_size):
+    def __init__(self, pool_size, trainable=False):
         super().__init__()
         self._pool_size = pool_size
+        self._trainable = bool(trainable)
 
     @torch.no_grad()
     def forward(self, inputs, training=None, mask=None):
         shared_layers, rois, extractor_stride = inputs
+        if _wants_grad(self._trainable, [shared_layers]):
+            return _pool_trainable([shared_layers], rois, None, ops.ROI_NORM_TP_ALIGN, self._pool_size, ops.ROI_POOL_AVG2,
+                                   strides=[float(extractor_stride)])
         return ops.roi_pool([shared_layers], rois, None, ops.ROI_NORM_TP_ALIGN, self._pool_size,
                             ops.ROI_POOL_AVG2, strides=[float(extractor_stride)],
                             order=_spatial_order(shared_layers, rois, extractor_stride))
@@ -91,9 +121,14 @@ class RoiPoolingRoiAlign(torch.nn.Module):
     call = forward
 
 
-def roi_pooling_fpn_levels(p_list, rois_sorted, roi_level, image_shape, pool_size, count_dev=None, out=None):
+def roi_pooling_fpn_levels(p_list, rois_sorted, roi_level, image_shape, pool_size, count_dev=None, out=None, trainable=False):
     """Native addition: what reference model/fpn/base_fpn_model.py:152-161 (_get_roi_features)
     does with one RoiPoolingCropAndResize2 call per non-empty level + concat, as ONE launch over
     the level-sorted RoIs (``roi_level`` = 0-based level of each row)."""
+    if _wants_grad(trainable, p_list):
+        if out is not None:
+            raise ValueError('roi_pooling_fpn_levels: the trainable form allocates its output (out must be None)')
+        return _pool_trainable(p_list, rois_sorted, roi_level, ops.ROI_NORM_IMAGE, pool_size, ops.ROI_POOL_MAX2,
+                               image_shape=image_shape, count_dev=count_dev)
     return ops.roi_pool(list(p_list), rois_sorted, roi_level, ops.ROI_NORM_IMAGE, pool_size, ops.ROI_POOL_MAX2,
                         image_shape=image_shape, count_dev=count_dev, out=out)

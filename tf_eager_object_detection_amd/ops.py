@@ -1219,6 +1219,144 @@ def roi_pool(feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, str
     return out
 
 
+ROI_GRAD_MAX_ROIS = 8192       # odet_roi_pool_argmax / odet_roi_pool_backward: ODET_E_LIMIT above
+ROI_GRAD_MAX_POOL = 16
+
+
+def _roi_grad_levels(who, maps_or_shapes, strides, device, alloc):
+    """the level table of the RoI backward: `maps_or_shapes` = float32 NHWC GPU tensors [1,H,W,C] (the maps, or dx buffers to
+    write) or shapes (1,H,W,C) (alloc: buffers are made) -> (levels, tensors, C)"""
+    nl = len(maps_or_shapes)
+    if nl < 1 or nl > MAX_LEVELS:
+        raise ValueError('%s: between 1 and %d feature maps expected' % (who, MAX_LEVELS))
+    levels = (L.OdetLevel * nl)()
+    keep, Cc = [], None
+    for i, fm in enumerate(maps_or_shapes):
+        if not isinstance(fm, torch.Tensor):
+            if not alloc:
+                raise TypeError('%s: feature maps must be tensors' % who)
+            fm = torch.empty(tuple(int(v) for v in fm), dtype=torch.float32, device=device)
+        if fm.dtype != torch.float32:
+            raise ValueError('%s: feature maps must be float32 (the RoI backward has no float16 form), got %s' % (who, fm.dtype))
+        if fm.dim() != 4 or fm.shape[0] != 1:
+            raise ValueError('%s: feature map must be NHWC with batch 1, got %s' % (who, tuple(fm.shape)))
+        if not fm.is_cuda:
+            raise L.OdetError('%s: shared_layers must live on the GPU: tf_eager_object_detection_amd has no CPU path' % who)
+        if not fm.is_contiguous():
+            raise ValueError('%s: feature maps must be contiguous' % who)
+        if Cc is None:
+            Cc = int(fm.shape[3])
+        elif int(fm.shape[3]) != Cc:
+            raise ValueError('%s: all levels must share the channel count' % who)
+        keep.append(fm)
+        levels[i].data = fm.data_ptr()
+        levels[i].H = fm.shape[1]
+        levels[i].W = fm.shape[2]
+        levels[i].stride = float(strides[i]) if strides is not None else 0.0
+    return levels, keep, Cc
+
+
+def _roi_grad_f32(who, maps):
+    for fm in maps:
+        if isinstance(fm, torch.Tensor) and fm.dtype != torch.float32:
+            raise ValueError('%s: feature maps must be float32 (the RoI backward has no float16 form), got %s' % (who, fm.dtype))
+
+
+def _roi_grad_rois(who, rois, roi_level, pool_size):
+    rois = _boxes(rois, 'rois')
+    if roi_level is not None and roi_level.dtype != torch.int32:
+        roi_level = roi_level.to(torch.int32)
+    return rois, roi_level, int(rois.shape[0]), int(pool_size)
+
+
+def roi_pool_argmax(feature_maps, rois, roi_level, norm_mode, pool_size, strides=None, image_shape=None, count_dev=None,
+                    out=None):
+    """Which sample of each 2x2 bin roi_pool(..., ROI_POOL_MAX2) took (odet_roi_pool_argmax): uint8 [n,P,P,C], 0..3 = 2*di+dj
+    (the first sample equal to the pooled value), 4 = none.  float32 maps only."""
+    _roi_grad_f32('roi_pool_argmax', feature_maps)
+    rois, roi_level, n, P = _roi_grad_rois('roi_pool_argmax', rois, roi_level, pool_size)
+    levels, keep, Cc = _roi_grad_levels('roi_pool_argmax', list(feature_maps), strides, rois.device, alloc=False)
+    out = _out(out, (n, P, P, Cc), torch.uint8, rois.device)
+    ih, iw = (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
+    L.call('odet_roi_pool_argmax', levels, len(keep), Cc, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev), int(norm_mode),
+           ih, iw, P, L.dptr(out), L.stream())
+    return out
+
+
+def roi_pool_backward(dy, feature_shapes_or_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None,
+                      image_shape=None, count_dev=None, outs=None, sel=None):
+    """The gradient of roi_pool with respect to its float32 maps (odet_roi_pool_backward): dy [n,P,P,C] -> list of dx, one
+    [1,H,W,C] float32 per level, every element written once in an order fixed by the data's indices (bit-reproducible).
+    `feature_shapes_or_maps`: the maps (only their shapes are used) or their shapes; `sel`: roi_pool_argmax's output, required
+    for ROI_POOL_MAX2 and refused otherwise; `outs`: buffers to write instead of new ones."""
+    who = 'roi_pool_backward'
+    if not isinstance(dy, torch.Tensor) or dy.dtype != torch.float32:
+        raise ValueError('%s: dy must be a float32 tensor (the RoI backward has no float16 form)' % who)
+    _roi_grad_f32(who, feature_shapes_or_maps if outs is None else outs)
+    if (int(pool_mode) == ROI_POOL_MAX2) != (sel is not None):
+        raise ValueError('%s: sel (roi_pool_argmax) is required for ROI_POOL_MAX2 and goes with no other pool_mode' % who)
+    rois, roi_level, n, P = _roi_grad_rois(who, rois, roi_level, pool_size)
+    if outs is None:
+        outs = [tuple(fm.shape) if isinstance(fm, torch.Tensor) else tuple(fm) for fm in feature_shapes_or_maps]
+    levels, dxs, Cc = _roi_grad_levels(who, list(outs), strides, rois.device, alloc=True)
+    if tuple(dy.shape) != (n, P, P, Cc) or not dy.is_contiguous():
+        raise ValueError('%s: dy must be contiguous [n,P,P,C] = %s, got %s' % (who, (n, P, P, Cc), tuple(dy.shape)))
+    if sel is not None and (sel.dtype != torch.uint8 or tuple(sel.shape) != (n, P, P, Cc) or not sel.is_contiguous()):
+        raise ValueError('%s: sel must be contiguous uint8 [n,P,P,C]' % who)
+    ih, iw = (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
+    L.call('odet_roi_pool_backward', levels, len(dxs), Cc, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev), int(norm_mode),
+           ih, iw, P, int(pool_mode), L.dptr(dy), L.dptr(sel), L.stream())
+    return dxs
+
+
+class _RoiPoolTrainable(torch.autograd.Function):
+    """ops.roi_pool forward (and, for ROI_POOL_MAX2, the select launch while the maps are warm); one roi_pool_backward backward"""
+
+    @staticmethod
+    def forward(ctx, rois, roi_level, count_dev, cfg, *maps):
+        norm_mode, pool_size, pool_mode, strides, image_shape = cfg
+        out = roi_pool(list(maps), rois, roi_level, norm_mode, pool_size, pool_mode, strides=strides, image_shape=image_shape,
+                       count_dev=count_dev)
+        sel = None
+        if pool_mode == ROI_POOL_MAX2:
+            sel = roi_pool_argmax(maps, rois, roi_level, norm_mode, pool_size, strides=strides, image_shape=image_shape,
+                                  count_dev=count_dev)
+        ctx.cfg = cfg
+        ctx.shapes = [tuple(m.shape) for m in maps]
+        ctx.save_for_backward(rois, roi_level, count_dev, sel)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        rois, roi_level, count_dev, sel = ctx.saved_tensors
+        norm_mode, pool_size, pool_mode, strides, image_shape = ctx.cfg
+        dxs = roi_pool_backward(dy if dy.is_contiguous() else dy.contiguous(), ctx.shapes, rois, roi_level, norm_mode, pool_size,
+                                pool_mode, strides=strides, image_shape=image_shape, count_dev=count_dev, sel=sel)
+        return (None, None, None, None) + tuple(dx if need else None for dx, need in zip(dxs, ctx.needs_input_grad[4:]))
+
+
+def roi_pool_trainable(feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None, image_shape=None,
+                       count_dev=None):
+    """ops.roi_pool with a backward pass into the float32 maps: the forward is `roi_pool`, bit for bit; `.backward()` is one
+    roi_pool_backward and leaves a gradient on every map that requires one (None for the others).  The RoIs get no gradient
+    (the reference stops it: roi_pooling.py:78)."""
+    maps = []
+    for fm in feature_maps:
+        if not isinstance(fm, torch.Tensor) or fm.dtype != torch.float32:
+            raise ValueError('roi_pool_trainable: feature maps must be float32 tensors (the RoI backward has no float16 form), got %s'
+                             % getattr(fm, 'dtype', type(fm).__name__))
+        maps.append(fm if fm.is_contiguous() else fm.contiguous())
+    if int(rois.shape[0]) > ROI_GRAD_MAX_ROIS or int(pool_size) > ROI_GRAD_MAX_POOL:
+        raise ValueError('roi_pool_trainable: at most %d RoIs and pool_size %d' % (ROI_GRAD_MAX_ROIS, ROI_GRAD_MAX_POOL))
+    rois = _boxes(rois.detach(), 'rois')
+    if roi_level is not None and roi_level.dtype != torch.int32:
+        roi_level = roi_level.to(torch.int32)
+    cfg = (int(norm_mode), int(pool_size), int(pool_mode), None if strides is None else tuple(float(s) for s in strides),
+           None if image_shape is None else (int(image_shape[0]), int(image_shape[1])))
+    return _RoiPoolTrainable.apply(rois, roi_level, count_dev, cfg, *maps)
+
+
 def post_ops(scores, deltas, rois, image_shape, means, stds, max_per_class, max_per_image, nms_iou_threshold,
              score_threshold, min_edge, num_classes, count_dev=None, out=None, workspace=None, record=None):
     """-> (boxes [M,4], labels int32 [M], scores [M]) padded to max_per_image, count int32[1].
