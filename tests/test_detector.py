@@ -189,15 +189,9 @@ def test_detector_hot_path_state_matches_oracle():
     assert int(count.item()) > 0
 
 
-@pytest.mark.gpu
-def test_detector_hip_graph_replay_matches_eager():
-    """ResNetFpnDetector.capture: the whole forward pass replayed as one HIP graph gives the eager outputs,
-    and follows its input (a second image through the same graph)."""
-    from tf_eager_object_detection_amd.model.fpn_detector import ResNetFpnDetector
-    torch.manual_seed(3)
-    shape = (256, 352)
-    m = ResNetFpnDetector(50, 21, shape, 300, dtype=torch.float32, blind_chunks=3).prepare()
-    rng = np.random.default_rng(7)
+def _graph_replay_matches_eager(m, shape, rng):
+    """capture(): the whole forward pass replayed as one HIP graph gives the eager outputs, and follows its input (a second
+    image through the same graph)"""
     imgs = [torch.from_numpy((rng.uniform(0, 255, (1,) + shape + (3,)) - 110).astype(np.float32)).cuda() for _ in range(2)]
     eager = []
     for im in imgs:
@@ -213,6 +207,37 @@ def test_detector_hip_graph_replay_matches_eager():
         torch.testing.assert_close(b[:ec], eb[:ec], rtol=1e-3, atol=1e-2)
         torch.testing.assert_close(s[:ec], es[:ec], rtol=1e-3, atol=1e-4)
     assert int(m._hot[0].nms_done.item()) == 1
+
+
+@pytest.mark.gpu
+def test_detector_hip_graph_replay_matches_eager():
+    """ResNetFpnDetector.capture: the whole forward pass replayed as one HIP graph gives the eager outputs,
+    and follows its input (a second image through the same graph)."""
+    from tf_eager_object_detection_amd.model.fpn_detector import ResNetFpnDetector
+    torch.manual_seed(3)
+    shape = (256, 352)
+    m = ResNetFpnDetector(50, 21, shape, 300, dtype=torch.float32, blind_chunks=3).prepare()
+    _graph_replay_matches_eager(m, shape, np.random.default_rng(7))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('family', ['c4', 'vgg16'])
+def test_detector_hip_graph_replay_matches_eager_single_level(family):
+    """the same capture() (detector_base.Detector's: one for the three detectors) on the single-level families -- the
+    benchmark replays VGG16 as a graph; detectors, seeds and shapes of test_c4_detector_hot_path_state_matches_oracle and
+    test_vgg16_detector_runs_and_pools_like_oracle"""
+    from tf_eager_object_detection_amd.model.frcnn_detector import ResNetC4Detector, Vgg16Detector
+    if family == 'c4':
+        torch.manual_seed(4)
+        shape = (256, 352)
+        m = ResNetC4Detector(50, 21, shape, 100, dtype=torch.float32, blind_chunks=4).prepare()
+        rng = np.random.default_rng(4)
+    else:
+        torch.manual_seed(6)
+        shape = (240, 320)
+        m = Vgg16Detector(21, shape, 100, dtype=torch.float32, blind_chunks=4).prepare()
+        rng = np.random.default_rng(6)
+    _graph_replay_matches_eager(m, shape, rng)
 
 
 def test_c4_feature_map_size_matches_anchor_grid_cpu():
@@ -666,6 +691,70 @@ def test_detector_recovers_incomplete_nms_in_exact_mode(batched):
     # im_detect takes the same route (base_fpn_model.py:364-390): no exception, every proposal of the exact NMS
     det = m.im_detect(img, 1.0)
     assert m.nms_reruns == 4 and all(d[0].shape[0] == int(m._hot[b].roi_count.item()) > 0 for b, d in enumerate(det))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('batched', [True, False])
+def test_c4_detector_recovers_incomplete_nms_in_exact_mode(batched):
+    """the recovery of test_detector_recovers_incomplete_nms_in_exact_mode through the shared pass on a single-level family, in
+    both arrangements: an all-tied RPN score map (zero score weights) does not complete inside blind_chunks = 1; forward() does
+    not raise, both images are re-run in the exact mode and end with as many proposals as the oracle's region_proposal keeps on
+    the recorded RPN outputs; im_detect takes the same route and returns that many rows."""
+    from tf_eager_object_detection_amd.model.frcnn_detector import ResNetC4Detector
+    torch.manual_seed(21)
+    shape, K = (256, 352), 300
+    m = ResNetC4Detector(50, 21, shape, K, dtype=torch.float32, max_batch=2, blind_chunks=1, batched=batched).prepare()
+    assert (m._steps is not None) == batched
+    with torch.no_grad():
+        m.rpn_score.weight.zero_()
+        m.rpn_score.bias.zero_()
+    rng = np.random.default_rng(5)
+    img = torch.from_numpy((rng.uniform(0, 255, (2,) + shape + (3,)) - 110).astype(np.float32)).cuda()
+    anchors = co.anchors_shift(m._hot[0].anchor_base, 16, m._hot[0].fh, m._hot[0].fw)
+
+    def oracle_counts():
+        sc, dl = m._last_pass[0], m._last_pass[1]
+        return [len(co.region_proposal(dl[b].cpu().numpy(), anchors, co.rpn_fg_frcnn(sc[b].cpu().numpy(), 9), shape, K, 0.7)[1])
+                for b in range(2)]
+    outs = m(img)                                         # no exception
+    torch.cuda.synchronize()
+    assert len(outs) == 2
+    assert m.nms_reruns == 2 and m.incomplete(2) == []
+    want = oracle_counts()
+    for b in range(2):
+        k = int(m._hot[b].roi_count.item())
+        print('image %d: roi_count %d, oracle %d' % (b, k, want[b]))
+        assert k > 0 and k == want[b]
+    det = m.im_detect(img, 1.0)
+    want = oracle_counts()
+    assert m.nms_reruns == 4
+    for b, d in enumerate(det):
+        assert d[0].shape[0] == d[1].shape[0] == d[2].shape[0] == int(m._hot[b].roi_count.item()) == want[b] > 0
+
+
+@pytest.mark.gpu
+def test_detector_stays_per_image_over_repeated_prepare():
+    """a detector built with batched=False keeps the per-image arrangement however often it is prepared (prepare() reads the
+    hot-path keywords from a copy), and gives the same detections after the second prepare().  Two passes of the same network on
+    the same images differ at most in float32 summation order: the tolerances of the eager / graph-replay comparison above."""
+    from tf_eager_object_detection_amd.model.fpn_detector import ResNetFpnDetector
+    torch.manual_seed(8)                                  # (network and images of test_detector_batched_hot_path_matches_per_image_path)
+    shape = (256, 352)
+    m = ResNetFpnDetector(50, 21, shape, 300, max_batch=2, batched=False)
+    rng = np.random.default_rng(8)
+    img = torch.from_numpy((rng.uniform(0, 255, (2,) + shape + (3,)) - 110).astype(np.float32)).cuda()
+    seen = []
+    for _ in range(2):
+        m.prepare()
+        assert m._steps is None and len(m._hot) == 2
+        outs = m(img)
+        torch.cuda.synchronize()
+        seen.append([(b.clone(), l.clone(), s.clone(), int(c.item())) for b, l, s, c in outs])
+    for (b0, l0, s0, c0), (b1, l1, s1, c1) in zip(*seen):
+        assert c0 == c1 and c0 > 0
+        assert torch.equal(l0[:c0], l1[:c0])
+        torch.testing.assert_close(b0[:c0], b1[:c0], rtol=1e-3, atol=1e-2)
+        torch.testing.assert_close(s0[:c0], s1[:c0], rtol=1e-3, atol=1e-4)
 
 
 @pytest.mark.gpu

@@ -277,6 +277,38 @@ def test_hot_path_defaults_pinned_by_reference_configs():
     assert Vgg16Detector(21, (64, 64), 10)._hot_kwargs['max_pooling_flag'] == fr['vgg16_roi_pooling_max_pooling_flag']
 
 
+def test_detectors_share_one_pass():
+    """model/detector_base.py owns a detector's pass: the three detectors resolve prepare / forward / im_detect / capture /
+    _run_to_head / _detect to the base class's own functions, frcnn_detector.py borrows nothing from the FPN detector's class,
+    the two-limb -> three-limb switch is written once, and the four files together are smaller than before the merge."""
+    import inspect
+    from tf_eager_object_detection_amd.model import detector_base, fpn_detector, frcnn_detector
+    base = detector_base.Detector
+    for cls in (fpn_detector.ResNetFpnDetector, frcnn_detector.ResNetC4Detector, frcnn_detector.Vgg16Detector):
+        assert issubclass(cls, base)
+        for name in ('prepare', 'forward', 'im_detect', 'capture', '_run_to_head', '_detect'):
+            assert getattr(cls, name) is base.__dict__[name], (cls.__name__, name)
+    src = inspect.getsource(detector_base)
+    assert 'fpn_detector import' not in src and 'frcnn_detector import' not in src and 'import fpn_detector' not in src
+    src = inspect.getsource(frcnn_detector)
+    assert 'ResNetFpnDetector' not in src and '_NmsCompleteness' not in src
+    # (every name that moved is still importable from fpn_detector: the caller objects and the tests take them from there)
+    for name in ('DEFAULT_BLIND_CHUNKS', '_NmsCompleteness', '_FinalLayer', '_FinalTrainable', '_in_f32_form', '_x3_workspace_of',
+                 'caller_range_checked', 'check_caller_f32_form'):
+        assert getattr(fpn_detector, name) is getattr(detector_base, name), name
+    assign = re.compile(r'f32_form\s*=(?!=)')
+    nc = detector_base._NmsCompleteness
+    assert not assign.search(inspect.getsource(nc.run_range_checked)) and not assign.search(inspect.getsource(nc._forward_checked))
+    assert len(assign.findall(inspect.getsource(nc._on_three_limbs))) == 2          # 'x3' and back to 'x2': in the one helper
+    assert len(re.findall(r'self\.f32_form\s*=(?!=)', inspect.getsource(detector_base))) == 2
+    # non-blank, non-comment lines of the four files: 1529 on the commit before the merge (699 + 268 + 0 + 562)
+    total = 0
+    for rel in ('model/fpn_detector.py', 'model/frcnn_detector.py', 'model/detector_base.py', 'pipeline.py'):
+        lines = open(os.path.join(ROOT, 'tf_eager_object_detection_amd', rel)).read().splitlines()
+        total += sum(1 for ln in lines if ln.strip() and not ln.strip().startswith('#'))
+    assert total < 1529, total
+
+
 def test_bench_self_launch_starts_torchrun_children(monkeypatch):
     """`python bench.py --gpus N` without a launcher's environment starts `python -m torch.distributed.run --nnodes=1
     --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>` as a child process (never an exec) and returns

@@ -7,7 +7,9 @@ Same arrangement as model/fpn_detector.py: the convolutions are genuine dense co
 through this repository's kernels (NHWC, float32 = parity mode / float16 = throughput mode; no library convolution or GEMM
 route, no CPU path); everything between them is FrcnnHotPath (anchors in registers -> [A bg | A fg] softmax -> decode /
 clip -> exact NMS over all anchors -> 7x7 crop (ResNet) / 14x14 crop + 2x2 max (VGG16) on the stride-16 map ->
-post_ops_prediction).  Weights are randomly initialised with the reference's initialisers (no checkpoints offline), frozen
+post_ops_prediction).  The pass that strings them together -- prepare, forward, im_detect, the after-pass checks, the
+HIP-graph capture -- is detector_base.Detector's, shared with the FPN detector; this file holds the two networks and the
+per-image (`batched=False`) arrangement of the single-level families.  Weights are randomly initialised with the reference's initialisers (no checkpoints offline), frozen
 batch-norm folded.  The plain-torch formulation of the same networks lives with the tests (tests/torch_reference.py)."""
 import torch
 import torch.nn as nn
@@ -15,23 +17,26 @@ import torch.nn as nn
 from .. import ops
 from ..derived import derived
 from ..pipeline import FrcnnHotPath, FrcnnStepBatch
-from . import fpn_detector as fpn
-from .fpn_detector import _BLOCKS, DEFAULT_BLIND_CHUNKS, ResNetFpnDetector, _NmsCompleteness, _FinalLayer, _conv, _conv_epi, _stem, \
-    _conv_relu_pool, _fold_frozen_bn, _in_f32_form, _nhwc, _no_kernel, _stack, rpn_pair_weights
+from .detector_base import Detector, _in_f32_form
+from .fpn_detector import _BLOCKS, _conv, _conv_epi, _conv_relu_pool, _fold_frozen_bn, _nhwc, _no_kernel, _patch_gemm, \
+    _patch_weight, _stack, _stem, rpn_pair_padded, rpn_pair_weights
 
 __all__ = ['ResNetC4Detector', 'Vgg16Detector']
 
 
-class ResNetC4Detector(_NmsCompleteness, _FinalLayer, nn.Module):
-    """Inference-only ResNet-{50,101,152} C4 Faster R-CNN.  `forward(images)` takes NHWC float images [B,H,W,3]
-    (mean-subtracted) and returns, per image, the padded detections of post_ops_prediction + their count."""
+class ResNetC4Detector(Detector):
+    """Inference-only ResNet-{50,101,152} C4 Faster R-CNN (the pass itself: detector_base.Detector).  Batched arrangement:
+    FrcnnStepBatch (odet_fpn_step_t.single_level); per image (`batched=False`): one FrcnnHotPath per image on a stream of its
+    own, then ONE RoI-head call for the whole batch."""
+
+    _step_batch_class, _hot_path_class = FrcnnStepBatch, FrcnnHotPath
 
     def __init__(self, depth=50, num_classes=21, image_shape=(800, 1333), num_proposals=300, dtype=torch.float32,
                  max_batch=1, roi_chunk=0, f32_form='exact', **hot_kwargs):
         super().__init__()
         b = _BLOCKS[depth]
         self.dtype = dtype
-        self.f32_form = f32_form             # float32 mode: 'exact' | 'x3' | 'x2' (model/fpn_detector.py)
+        self.f32_form = f32_form             # float32 mode: 'exact' | 'x3' | 'x2' (model/detector_base.py)
         self.image_shape = (int(image_shape[0]), int(image_shape[1]))
         self.num_classes = num_classes
         # extractor (resnet_faster_rcnn.py:104-153): conv1 .. conv4, stride 16
@@ -51,46 +56,21 @@ class ResNetC4Detector(_NmsCompleteness, _FinalLayer, nn.Module):
         for m, std in ((self.score, 0.01), (self.bbox, 0.001)):
             nn.init.normal_(m.weight, 0.0, std)
             nn.init.zeros_(m.bias)
-        self._hot_args = (self.image_shape, num_classes, num_proposals, 1024)
         # config/faster_rcnn_config.py: 'resnet_roi_pooling_max_pooling_flag': False (7x7 crop, no pool) -- what
         # model_factory.py:117 passes, overriding the class default
-        self._hot_kwargs = dict(pool_size=7, max_pooling_flag=False, blind_chunks=DEFAULT_BLIND_CHUNKS)
-        self._hot_kwargs.update(hot_kwargs)
-        self._hot = []
-        self._max_batch = max_batch
+        self._declare_hot_path(1024, num_proposals, max_batch, hot_kwargs, pool_size=7, max_pooling_flag=False)
         self._roi_chunk = int(roi_chunk)
 
-    def prepare(self, device='cuda'):
-        """Moves the model to the GPU and allocates the hot path.  Up to 8 images go through the hot path in the SAME
-        kernel launches (FrcnnStepBatch: odet_fpn_step_t.single_level) and through the RoI head as one batch;
-        `batched=False` in the hot-path keywords selects one FrcnnHotPath per image on a stream of its own."""
-        self.to(device=device, dtype=self.dtype, memory_format=torch.channels_last).eval()
-        ops.invalidate_planes(self)                   # (every derived tensor: the weights may have been rewritten through .data)
-        # float16 maps go straight into the RoI kernel (pooled 14x14 + max and un-pooled 7x7 crop alike)
-        feat_dtype = torch.float16 if self.dtype == torch.float16 else torch.float32
-        self._feature_dtype = feat_dtype
-        kw = dict(self._hot_kwargs)
-        self._steps = None
-        if self._max_batch <= 64 and kw.pop('batched', True):
-            self._steps = FrcnnStepBatch(self._max_batch, *self._hot_args, feature_dtype=feat_dtype, **kw)
-            self._hot = self._steps.slots
-            self._roi_feat_all = self._steps.roi_features
-            K = self._hot_args[2]
-            dev = self._hot[0].device
-            self._cls = torch.zeros((self._max_batch, K, self.num_classes), dtype=torch.float32, device=dev)
-            self._dlt = torch.zeros((self._max_batch, K, 4 * self.num_classes), dtype=torch.float32, device=dev)
-            self._bound = False
-            return self
-        self._hot = [FrcnnHotPath(*self._hot_args, feature_dtype=feat_dtype, **kw) for _ in range(self._max_batch)]
+    def _prepare_per_image(self):
         # the images' RoI features are consecutive blocks of one buffer: the RoI head takes the whole batch at once
         h0 = self._hot[0]
-        self._roi_feat_all = torch.zeros((self._max_batch,) + tuple(h0.roi_features.shape), dtype=feat_dtype, device=h0.device)
+        self._roi_feat_all = torch.zeros((self._max_batch,) + tuple(h0.roi_features.shape), dtype=self._feature_dtype,
+                                         device=h0.device)
         for b, h in enumerate(self._hot):
             h.roi_features = self._roi_feat_all[b]
         # one stream per image: the hot path of an image is a chain of small launches (~130 us), the images'
         # chains run beside each other
         self._streams = [torch.cuda.Stream(device=h0.device) for _ in range(self._max_batch)]
-        return self
 
     def _per_image(self, B, fn):
         """fn(b) for every image on its own stream; the current stream forks before and joins after (events, no host
@@ -130,7 +110,7 @@ class ResNetC4Detector(_NmsCompleteness, _FinalLayer, nn.Module):
         # the two 1x1 convolutions as ONE contraction on the pointwise GEMM kernel (weight rows zero-padded to 64), then ONE
         # pass: + bias, float32, split (ops.rpn_pack_pair; [fh*fw, 2A] and [fh*fw*A, 2] are the same memory)
         w, b = rpn_pair_weights(self)
-        sd = ops.pointwise(_nhwc(x), fpn.rpn_pair_padded(self, w), None)[..., :6 * self.A]
+        sd = ops.pointwise(_nhwc(x), rpn_pair_padded(self, w), None)[..., :6 * self.A]
         n = int(sd.shape[1]) * int(sd.shape[2]) * self.A
         scores = torch.empty((B, n, 2), dtype=torch.float32, device=x.device)
         deltas = torch.empty((B, n, 4), dtype=torch.float32, device=x.device)
@@ -152,85 +132,34 @@ class ResNetC4Detector(_NmsCompleteness, _FinalLayer, nn.Module):
         """-> (score logits [R,C], box deltas [R,4C]), float32"""
         return self._final_outputs(self.head_activation(roi_features))
 
-    capture = ResNetFpnDetector.capture          # whole forward pass as one HIP graph (generic over self.forward)
-
-    # ---- the model ----------------------------------------------------------------------------------
-    def _run_to_head(self, images_nhwc):
-        """extractor -> RPN head -> proposals -> RoI features -> RoI head (base_faster_rcnn_model.py:132-187 /
-        :279-304): per image (class softmax [K,Ccls], raw deltas [K,4*Ccls]); rows >= the proposal count are padding."""
-        B = images_nhwc.shape[0]
-        if B > len(self._hot):
-            raise ValueError('batch %d exceeds max_batch %d' % (B, len(self._hot)))
+    # ---- the model (the pass: detector_base.Detector) -----------------------------------------------
+    def _dense(self, images_nhwc):
+        """extractor -> RPN head (base_faster_rcnn_model.py:132-153): (rpn scores [B,fh*fw,2A], rpn deltas [B,N,4], the
+        contiguous NHWC stride-16 map in the hot path's feature dtype)"""
         c4 = self.features(images_nhwc)
         rpn_scores, rpn_deltas = self.rpn(c4)
         rpn_scores, rpn_deltas = rpn_scores.float().contiguous(), rpn_deltas.float().contiguous()
         maps = c4.permute(0, 2, 3, 1)                                            # NHWC view
         if maps.dtype != self._feature_dtype:
             maps = maps.to(self._feature_dtype)
-        maps = maps.contiguous()
-        K = self._roi_feat_all.shape[1]
-        if self._steps is not None:
-            # B images in the same hot-path launches, the RoI head on all B x K crops at once
-            sb = self._steps
-            bind = sb.rebind if self._bound else sb.bind
-            for b in range(B):
-                bind(b, rpn_scores[b], rpn_deltas[b], [maps[b:b + 1]], self._cls[b], self._dlt[b])
-            if B == self._max_batch:
-                self._bound = True
-            sb.enqueue(sb.STAGE_PROPOSALS | sb.STAGE_ROI, B)
-            feats = sb.roi_features[:B].reshape((B * K,) + tuple(sb.roi_features.shape[2:]))
-            logits, bbox = self.roi_head(feats)
-            torch.softmax(logits.float(), dim=-1, out=self._cls[:B].view(B * K, -1))
-            self._dlt[:B].view(B * K, -1).copy_(bbox)
-            heads = [(self._cls[b], self._dlt[b]) for b in range(B)]
-            self._last_pass = (rpn_scores, rpn_deltas, maps, heads)
-            return heads
-        def proposals_and_crops(b):
-            hot = self._hot[b]
-            hot.stage_proposals(rpn_scores[b], rpn_deltas[b])
-            hot.stage_roi(maps[b:b + 1])
-        self._per_image(B, proposals_and_crops)
-        feats = self._roi_feat_all[:B].reshape((B * K,) + tuple(self._roi_feat_all.shape[2:]))
-        logits, bbox = self.roi_head(feats)                                      # one head pass for the whole batch
-        cls = torch.softmax(logits.float(), dim=-1).reshape(B, K, -1).contiguous()
-        bbox = bbox.float().reshape(B, K, -1).contiguous()
-        heads = [(cls[b], bbox[b]) for b in range(B)]
-        self._last_pass = (rpn_scores, rpn_deltas, maps, heads)
-        return heads
+        return rpn_scores, rpn_deltas, maps.contiguous()
 
     @staticmethod
     def _maps_of(maps, b):
         return maps[b:b + 1]
 
-    @torch.no_grad()
-    def forward(self, images_nhwc, check=None):
-        def run(im):
-            heads = self._run_to_head(im)
-            B = len(heads)
-            if self._steps is not None:
-                sb = self._steps
-                sb.enqueue(sb.STAGE_DETECT, B)
-                return [(h.det_boxes, h.det_labels, h.det_scores, h.det_count) for h in sb.slots[:B]]
-            return self._per_image(B, lambda b: self._hot[b].stage_detect(heads[b][0], heads[b][1]))
-        return self._forward_checked(images_nhwc, check, run)
-
-    @torch.no_grad()
-    def im_detect(self, images_nhwc, img_scale):
-        """The evaluation entry of the reference models (base_faster_rcnn_model.py:279-306): per image
-        (softmax scores [R,Ccls], raw deltas [R,4*Ccls], rois / img_scale [R,4]) for the R proposals the image kept
-        (NMS order); consumed by evaluation.pascal_eval.detect_image with img_scale = 1.  Host-syncs once."""
-        heads = self.run_range_checked(lambda: self._run_to_head(images_nhwc))     # ('x2': out of range -> again on three limbs)
-        B = len(heads)
-        self._last_batch = B
-        self.recover(B)
-        out = []
-        for b, (cls, dlt) in enumerate(heads):
+    def _per_image_to_head(self, B, rpn_scores, rpn_deltas, maps):
+        def proposals_and_crops(b):
             hot = self._hot[b]
-            k = int(hot.roi_count.item())
-            sc = img_scale[b] if isinstance(img_scale, (list, tuple)) or (hasattr(img_scale, 'ndim') and img_scale.ndim > 0) else img_scale
-            div = torch.full((1,), float(sc), dtype=torch.float32, device=hot.rois.device)   # (true division: see the FPN detector)
-            out.append((cls[:k].clone(), dlt[:k].clone(), hot.rois[:k] / div))
-        return out
+            hot.stage_proposals(rpn_scores[b], rpn_deltas[b])
+            hot.stage_roi(maps[b:b + 1])
+        self._per_image(B, proposals_and_crops)
+        K = self._roi_feat_all.shape[1]
+        feats = self._roi_feat_all[:B].reshape((B * K,) + tuple(self._roi_feat_all.shape[2:]))
+        logits, bbox = self.roi_head(feats)                                      # one head pass for the whole batch
+        cls = torch.softmax(logits.float(), dim=-1).reshape(B, K, -1).contiguous()
+        bbox = bbox.float().reshape(B, K, -1).contiguous()
+        return [(cls[b], bbox[b]) for b in range(B)]
 
 
 class Vgg16Detector(ResNetC4Detector):
@@ -265,11 +194,7 @@ class Vgg16Detector(ResNetC4Detector):
         for m, std in ((self.fc1, 0.01), (self.fc2, 0.01), (self.score, 0.01), (self.bbox, 0.001)):
             nn.init.normal_(m.weight, 0.0, std)
             nn.init.zeros_(m.bias)
-        self._hot_args = (self.image_shape, num_classes, num_proposals, 512)
-        self._hot_kwargs = dict(pool_size=7, max_pooling_flag=True, blind_chunks=DEFAULT_BLIND_CHUNKS)
-        self._hot_kwargs.update(hot_kwargs)
-        self._hot = []
-        self._max_batch = max_batch
+        self._declare_hot_path(512, num_proposals, max_batch, hot_kwargs, pool_size=7, max_pooling_flag=True)
         self._roi_chunk = 0
 
     @_in_f32_form
@@ -284,9 +209,9 @@ class Vgg16Detector(ResNetC4Detector):
             x = ops.conv3x3_rgb(images_nhwc, packed, first.bias, relu=True).permute(0, 3, 1, 2)
         elif self.dtype == torch.float32 and images_nhwc.dtype == torch.float32:
             # float32 (parity mode): conv1_1 as the exact-float32 GEMM on its patch matrix (ops.rgb_patches3x3_f32)
-            w = derived(first, 'rgb_f32', (first.weight,), lambda weight: fpn._patch_weight(weight, 64))
+            w = derived(first, 'rgb_f32', (first.weight,), lambda weight: _patch_weight(weight, 64))
             Hn, Wn = int(images_nhwc.shape[1]), int(images_nhwc.shape[2])
-            x = fpn._patch_gemm(images_nhwc, Hn * Wn * 64 * 4, ops.rgb_patches3x3_f32, w, first.bias, True)
+            x = _patch_gemm(images_nhwc, Hn * Wn * 64 * 4, ops.rgb_patches3x3_f32, w, first.bias, True)
         else:
             raise _no_kernel('first convolution', first, images_nhwc)
         i = 0

@@ -255,19 +255,14 @@ class FrcnnHotPath:
         return feats, boxes, labels, scores, count
 
 
-def _fill_step(st, h, stream_handle, rpn_logits, rpn_deltas, p_list, cls_softmax, cls_deltas):
-    """Fills the odet_fpn_step_t `st` of FpnHotPath slot `h` for one image's inputs (float32 contiguous GPU
-    tensors; feature maps in the slot's feature dtype).  Returns the tensors the caller must keep alive."""
-    nl = h.max_level - h.min_level + 1
-    maps = list(p_list[:nl])
+def _fill_shared(st, h, who, min_edge, stream_handle, rpn_logits, rpn_deltas, cls_softmax, cls_deltas):
+    """What a multi-level and a single-level step fill alike in the odet_fpn_step_t `st` of hot-path slot `h`: the checks of the
+    four float32 tensors (`who`: the binding call's name in the error texts), image size, box coding, proposal, class and
+    post-ops fields (`min_edge`: the smallest box edge the post-ops keep), every input, output and workspace pointer, the
+    stream.  The level tables, the maps and what depends on the level sort stay with the two callers."""
     for t in (rpn_logits, rpn_deltas, cls_softmax, cls_deltas):
         if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise ValueError('FpnStreamPool.bind needs float32 contiguous GPU tensors')
-    fdt = h.roi_features.dtype                       # float16 slots (feature_dtype) take float16 maps
-    for t in maps:
-        if not (t.is_cuda and t.dtype == fdt and t.is_contiguous()):
-            raise ValueError('FpnStreamPool.bind needs %s contiguous GPU feature maps' % fdt)
-    tensors = [rpn_logits, rpn_deltas, cls_softmax, cls_deltas] + maps
+            raise ValueError('%s needs float32 contiguous GPU tensors' % who)
     if rpn_logits.numel() != h.N * 2 or rpn_deltas.numel() != h.N * 4:
         raise ValueError('%d anchors expected, got rpn scores %s / deltas %s'
                          % (h.N, tuple(rpn_logits.shape), tuple(rpn_deltas.shape)))
@@ -275,42 +270,54 @@ def _fill_step(st, h, stream_handle, rpn_logits, rpn_deltas, p_list, cls_softmax
         raise ValueError('class scores must be [%d, Ccls] and deltas [%d, Ccls, 4]' % (h.K, h.K))
     c = h.cfg
     st.image_h, st.image_w = h.image_shape
+    for k in range(4):
+        st.rpn_means[k], st.rpn_stds[k] = float(c['rpn_means'][k]), float(c['rpn_stds'][k])
+        st.roi_means[k], st.roi_stds[k] = float(c['roi_means'][k]), float(c['roi_stds'][k])
+    st.num_proposals, st.rpn_nms_iou, st.blind_chunks = h.K, float(c['rpn_nms_iou']), h.blind_chunks
+    st.channels, st.pool_size = h.C, h.P
+    st.maps_f16 = 1 if h.roi_features.dtype == torch.float16 else 0      # float16 slots (feature_dtype) take float16 maps
+    st.ccls, st.num_classes = cls_softmax.shape[1], h.num_classes
+    st.max_per_class, st.max_per_image = c['max_per_class'], c['max_per_image']
+    st.nms_iou, st.score_threshold, st.min_edge = float(c['nms_iou']), float(c['score_threshold']), float(min_edge)
+    st.rpn_logits, st.rpn_deltas = rpn_logits.data_ptr(), rpn_deltas.data_ptr()
+    st.cls_scores, st.cls_deltas = cls_softmax.data_ptr(), cls_deltas.data_ptr()
+    st.rois, st.roi_idx, st.roi_count = h.rois.data_ptr(), h.roi_idx.data_ptr(), h.roi_count.data_ptr()
+    st.nms_done, st.roi_features = h.nms_done.data_ptr(), h.roi_features.data_ptr()
+    st.roi_order = h.roi_order.data_ptr() if h.roi_order is not None else None
+    st.det_boxes, st.det_labels = h.det_boxes.data_ptr(), h.det_labels.data_ptr()
+    st.det_scores, st.det_count, st.record = h.det_scores.data_ptr(), h.det_count.data_ptr(), h.record.data_ptr()
+    st.ws_rpn, st.ws_rpn_bytes = h.ws_rpn.data_ptr(), h.ws_rpn.numel()
+    st.ws_rpn_clean = 1                              # (the slot zero-filled it at allocation and never exposes it)
+    st.ws_post_clean = 1
+    st.ws_post, st.ws_post_bytes = h.ws_post.data_ptr(), h.ws_post.numel()
+    st.stream = stream_handle
+
+
+def _fill_step(st, h, stream_handle, rpn_logits, rpn_deltas, p_list, cls_softmax, cls_deltas):
+    """Fills the odet_fpn_step_t `st` of FpnHotPath slot `h` for one image's inputs (float32 contiguous GPU
+    tensors; feature maps in the slot's feature dtype).  Returns the tensors the caller must keep alive."""
+    nl = h.max_level - h.min_level + 1
+    maps = list(p_list[:nl])
+    fdt = h.roi_features.dtype
+    for fm in maps:
+        if not (fm.is_cuda and fm.dtype == fdt and fm.is_contiguous()):
+            raise ValueError('FpnStreamPool.bind needs %s contiguous GPU feature maps' % fdt)
+        if fm.dim() != 4 or fm.shape[0] != 1 or fm.shape[3] != h.C:
+            raise ValueError('feature maps must be NHWC [1,H,W,%d]' % h.C)
+    _fill_shared(st, h, 'FpnStreamPool.bind', 16.0, stream_handle, rpn_logits, rpn_deltas, cls_softmax, cls_deltas)
     st.num_levels, st.A = len(h.fh), h.wh.shape[1]
     for l in range(len(h.fh)):
         st.fh[l], st.fw[l], st.stride[l] = h.fh[l], h.fw[l], int(h.strides[l])
     flat = h.wh.reshape(-1)
     for i in range(flat.shape[0]):
         st.wh[i] = float(flat[i])
-    for k in range(4):
-        st.rpn_means[k], st.rpn_stds[k] = float(c['rpn_means'][k]), float(c['rpn_stds'][k])
-        st.roi_means[k], st.roi_stds[k] = float(c['roi_means'][k]), float(c['roi_stds'][k])
-    st.num_proposals, st.rpn_nms_iou = h.K, float(c['rpn_nms_iou'])
-    st.min_level, st.max_level, st.blind_chunks = h.min_level, h.max_level, h.blind_chunks
-    st.nms_first_chunk = getattr(h, 'nms_first_chunk', 0)
-    st.num_maps, st.channels, st.pool_size = nl, h.C, h.P
-    st.maps_f16 = 1 if fdt == torch.float16 else 0
+    st.min_level, st.max_level, st.nms_first_chunk = h.min_level, h.max_level, getattr(h, 'nms_first_chunk', 0)
+    st.num_maps = nl
     for l, fm in enumerate(maps):
-        if fm.dim() != 4 or fm.shape[0] != 1 or fm.shape[3] != h.C:
-            raise ValueError('feature maps must be NHWC [1,H,W,%d]' % h.C)
         st.maps[l].data, st.maps[l].H, st.maps[l].W, st.maps[l].stride = fm.data_ptr(), fm.shape[1], fm.shape[2], 0.0
-    st.ccls, st.num_classes = cls_softmax.shape[1], h.num_classes
-    st.max_per_class, st.max_per_image = c['max_per_class'], c['max_per_image']
-    st.nms_iou, st.score_threshold, st.min_edge = float(c['nms_iou']), float(c['score_threshold']), 16.0
-    st.rpn_logits, st.rpn_deltas = rpn_logits.data_ptr(), rpn_deltas.data_ptr()
-    st.cls_scores, st.cls_deltas = cls_softmax.data_ptr(), cls_deltas.data_ptr()
-    st.rois, st.roi_idx, st.roi_count = h.rois.data_ptr(), h.roi_idx.data_ptr(), h.roi_count.data_ptr()
-    st.nms_done, st.sorted_rois = h.nms_done.data_ptr(), h.sorted_rois.data_ptr()
-    st.roi_level, st.roi_perm = h.roi_level.data_ptr(), h.roi_perm.data_ptr()
-    st.level_counts, st.roi_features = h.level_counts.data_ptr(), h.roi_features.data_ptr()
-    st.roi_order = h.roi_order.data_ptr() if h.roi_order is not None else None
-    st.det_boxes, st.det_labels = h.det_boxes.data_ptr(), h.det_labels.data_ptr()
-    st.det_scores, st.det_count, st.record = h.det_scores.data_ptr(), h.det_count.data_ptr(), h.record.data_ptr()
-    st.ws_rpn, st.ws_rpn_bytes = h.ws_rpn.data_ptr(), h.ws_rpn.numel()
-    st.ws_rpn_clean = 1                              # (FpnHotPath zero-filled it at allocation and never exposes it)
-    st.ws_post_clean = 1
-    st.ws_post, st.ws_post_bytes = h.ws_post.data_ptr(), h.ws_post.numel()
-    st.stream = stream_handle
-    return tensors
+    st.sorted_rois, st.roi_level = h.sorted_rois.data_ptr(), h.roi_level.data_ptr()
+    st.roi_perm, st.level_counts = h.roi_perm.data_ptr(), h.level_counts.data_ptr()
+    return [rpn_logits, rpn_deltas, cls_softmax, cls_deltas] + maps
 
 
 def _fill_frcnn_step(st, h, stream_handle, rpn_logits, rpn_deltas, feat, cls_softmax, cls_deltas):
@@ -319,54 +326,24 @@ def _fill_frcnn_step(st, h, stream_handle, rpn_logits, rpn_deltas, feat, cls_sof
     dtype.  Returns the tensors the caller must keep alive."""
     if isinstance(feat, (list, tuple)):
         feat = feat[0]
-    for t in (rpn_logits, rpn_deltas, cls_softmax, cls_deltas):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-            raise ValueError('FrcnnStepBatch.bind needs float32 contiguous GPU tensors')
     fdt = h.roi_features.dtype
     if not (feat.is_cuda and feat.dtype == fdt and feat.is_contiguous()):
         raise ValueError('FrcnnStepBatch.bind needs a %s contiguous GPU feature map' % fdt)
     if feat.dim() != 4 or feat.shape[0] != 1 or feat.shape[1] != h.fh or feat.shape[2] != h.fw or feat.shape[3] != h.C:
         raise ValueError('feature map must be NHWC [1,%d,%d,%d], got %s' % (h.fh, h.fw, h.C, tuple(feat.shape)))
-    if rpn_logits.numel() != h.N * 2 or rpn_deltas.numel() != h.N * 4:
-        raise ValueError('%d anchors expected, got rpn scores %s / deltas %s'
-                         % (h.N, tuple(rpn_logits.shape), tuple(rpn_deltas.shape)))
-    if cls_softmax.dim() != 2 or cls_softmax.shape[0] != h.K or cls_deltas.numel() != cls_softmax.numel() * 4:
-        raise ValueError('class scores must be [%d, Ccls] and deltas [%d, Ccls, 4]' % (h.K, h.K))
-    c = h.cfg
+    _fill_shared(st, h, 'FrcnnStepBatch.bind', h.stride, stream_handle, rpn_logits, rpn_deltas, cls_softmax, cls_deltas)
     st.single_level = 1
     st.roi_pool_mode = ops.ROI_POOL_MAX2 if h.max_pooling_flag else ops.ROI_POOL_NONE
-    st.image_h, st.image_w = h.image_shape
     st.num_levels, st.A = 1, h.A
     st.fh[0], st.fw[0], st.stride[0] = h.fh, h.fw, h.stride
     flat = h.anchor_base.reshape(-1)
     for i in range(flat.shape[0]):
         st.wh[i] = float(flat[i])
-    for k in range(4):
-        st.rpn_means[k], st.rpn_stds[k] = float(c['rpn_means'][k]), float(c['rpn_stds'][k])
-        st.roi_means[k], st.roi_stds[k] = float(c['roi_means'][k]), float(c['roi_stds'][k])
-    st.num_proposals, st.rpn_nms_iou = h.K, float(c['rpn_nms_iou'])
-    st.min_level, st.max_level, st.blind_chunks = 0, 0, h.blind_chunks
-    st.nms_first_chunk = 0
-    st.num_maps, st.channels, st.pool_size = 1, h.C, h.P
-    st.maps_f16 = 1 if fdt == torch.float16 else 0
+    st.min_level, st.max_level, st.nms_first_chunk = 0, 0, 0
+    st.num_maps = 1
     st.maps[0].data, st.maps[0].H, st.maps[0].W, st.maps[0].stride = feat.data_ptr(), h.fh, h.fw, float(h.stride)
-    st.ccls, st.num_classes = cls_softmax.shape[1], h.num_classes
-    st.max_per_class, st.max_per_image = c['max_per_class'], c['max_per_image']
-    st.nms_iou, st.score_threshold, st.min_edge = float(c['nms_iou']), float(c['score_threshold']), float(h.stride)
-    st.rpn_logits, st.rpn_deltas = rpn_logits.data_ptr(), rpn_deltas.data_ptr()
-    st.cls_scores, st.cls_deltas = cls_softmax.data_ptr(), cls_deltas.data_ptr()
-    st.rois, st.roi_idx, st.roi_count = h.rois.data_ptr(), h.roi_idx.data_ptr(), h.roi_count.data_ptr()
-    st.nms_done, st.sorted_rois = h.nms_done.data_ptr(), h.rois.data_ptr()       # (no level sort: the same list)
+    st.sorted_rois = h.rois.data_ptr()                                           # (no level sort: the same list)
     st.roi_level, st.roi_perm, st.level_counts = None, None, None
-    st.roi_features = h.roi_features.data_ptr()
-    st.roi_order = h.roi_order.data_ptr() if h.roi_order is not None else None
-    st.det_boxes, st.det_labels = h.det_boxes.data_ptr(), h.det_labels.data_ptr()
-    st.det_scores, st.det_count, st.record = h.det_scores.data_ptr(), h.det_count.data_ptr(), h.record.data_ptr()
-    st.ws_rpn, st.ws_rpn_bytes = h.ws_rpn.data_ptr(), h.ws_rpn.numel()
-    st.ws_rpn_clean = 1
-    st.ws_post_clean = 1
-    st.ws_post, st.ws_post_bytes = h.ws_post.data_ptr(), h.ws_post.numel()
-    st.stream = stream_handle
     return [rpn_logits, rpn_deltas, cls_softmax, cls_deltas, feat]
 
 
