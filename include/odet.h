@@ -261,10 +261,13 @@ int odet_prof_event_destroy(void* ev);
 int odet_prof_event_elapsed_ms(void* start, void* stop, float* ms);
 
 /* Spatial processing order for odet_roi_pool_ordered: out_order int32 [n] = the RoI rows sorted by
- * (level, y centre, x centre) (padded rows >= count last).  Native addition (no reference counterpart):
- * output row r still holds RoI r, only the order in which workgroups pick RoIs changes, so that the
- * chunk of RoIs one XCD processes taps one band of one pyramid level (fewer lines fetched into several
- * L2s, sliding working set).  n <= 8192. */
+ * (level, column strip of 1/8 of the image by the box centre's x, bin of 1/32 of the image by its y --
+ * counted downwards on even strips and upwards on odd ones, a serpentine --, then y centre, x centre, row)
+ * (padded rows >= count last).  Native addition (no reference counterpart): output row r still holds
+ * RoI r, only the order in which workgroups pick RoIs changes, so that the chunk of RoIs one XCD processes
+ * taps a window one strip wide of one pyramid level: a working set that slides through the XCD's L2 and
+ * still fits when two or three launches share it.  The fused order of odet_fpn_proposals visits the same
+ * (level, strip, bin) sequence, in arbitrary order inside a bin.  n <= 8192. */
 int odet_roi_order(const float* rois, const int32_t* roi_level, int n, const int32_t* count_dev,
                    int image_h, int image_w, int32_t* out_order, odet_stream_t stream);
 /* odet_roi_pool processing the RoIs in `order` (nullable = index order); start/stop events nullable

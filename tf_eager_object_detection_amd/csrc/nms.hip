@@ -762,7 +762,7 @@ struct ScanParams {          // pointer tables: one entry per image of the batch
   PerImg<int64_t*> as_perm;
   PerImg<int32_t*> as_counts;
   PerImg<int32_t*> as_order;                 // optional (K <= 1024): spatial processing order of the assigned RoIs
-  float ord_inv_h;
+  float ord_inv_h, ord_inv_w;
   int n, use_init, K, min_level, max_level;
   int fail_empty;      // last sync-free chunk of a job whose outputs feed further kernels through out_count (the fused
                        // proposal stages): an INCOMPLETE result is reported as zero proposals (+ *out_done = 0), so
@@ -775,6 +775,42 @@ __device__ __forceinline__ void scan_fail_empty(int32_t* out_count, int32_t* out
   if (out_done) *out_done = 0;
   if (level_counts)
     for (int L = 0; L < nl; ++L) level_counts[L] = 0;
+}
+
+// The order's bucket counts (tail of k_nms_scan) -> their exclusive prefix, in place: thread t takes the
+// ceil(nb / SCAN_THREADS) consecutive entries from t * that on (nb <= ODET_MAX_LEVELS * 256 = 4 per thread).  Barriers inside;
+// the caller syncs before (counts complete) and after (prefixes visible).
+__device__ __forceinline__ void scan_order_buckets(int* tbl, int nb, int* lds17) {
+  constexpr int PER_MAX = ODET_MAX_LEVELS * ROI_ORDER_BUCKETS_PER_LEVEL / SCAN_THREADS;
+  static_assert(PER_MAX * SCAN_THREADS == ODET_MAX_LEVELS * ROI_ORDER_BUCKETS_PER_LEVEL, "the scan covers the largest table");
+  const int per = (nb + SCAN_THREADS - 1) / SCAN_THREADS;
+  const int lo = (int)threadIdx.x * per;
+  int v[PER_MAX], sum = 0;
+#pragma unroll
+  for (int k = 0; k < PER_MAX; ++k) {
+    v[k] = (k < per && lo + k < nb) ? tbl[lo + k] : 0;
+    sum += v[k];
+  }
+  int total;
+  int ex = block_excl_scan(sum, lds17, &total);
+#pragma unroll
+  for (int k = 0; k < PER_MAX; ++k) {
+    if (k < per && lo + k < nb) { tbl[lo + k] = ex; ex += v[k]; }
+  }
+}
+
+// dynamic LDS the tail's order needs: 256 buckets per level the launch has.  k_nms_scan<true> keeps them in its staging area
+// (dead after the walk); k_nms_scan<false> has no staging area and is launched with exactly this much.
+static_assert(ODET_MAX_LEVELS * ROI_ORDER_BUCKETS_PER_LEVEL * sizeof(int) <= SCAN_DYN_LDS, "the bucket table fits the staging area");
+static size_t scan_order_lds(const ScanParams& sp) {
+  bool any = false, levels = false;
+  for (int i = 0; i < ODET_MAX_BATCH; ++i) {
+    any = any || sp.as_order.v[i] != nullptr;
+    levels = levels || sp.as_rois.v[i] != nullptr;
+  }
+  if (!any) return 0;
+  const int nl = levels ? sp.max_level - sp.min_level + 1 : 1;
+  return (size_t)nl * ROI_ORDER_BUCKETS_PER_LEVEL * sizeof(int);
 }
 
 template <bool LDSMAT>
@@ -805,7 +841,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_nms_scan(ScanParams sp) {
   __shared__ int keptpre[NMS_WORDS + 1];
   __shared__ int lvl_cnt[ODET_MAX_LEVELS][NMS_WORDS];
   __shared__ int lvl_tot[ODET_MAX_LEVELS];
-  extern __shared__ __align__(16) u64 mat[];  // packed strictly-lower matrix (LDSMAT)
+  extern __shared__ __align__(16) u64 mat[];  // packed strictly-lower matrix (LDSMAT); after the walk: the order's buckets
   if (st->done) return;                       // uniform: an earlier chunk finished the job
   // a later chunk that found nothing left in its order (the ranked selection is exhausted): the state stays
   // "not done" for whoever continues (the per-image fallback on the full order, or the caller's out_done check)
@@ -1058,10 +1094,10 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_nms_scan(ScanParams sp) {
                                         ao.counts, lds_al);
   }
   // Spatial processing order of the RoIs for the RoI kernel, in this launch instead of one of its own (odet_roi_order):
-  // the assigned RoIs were written by this workgroup just above.  A counting sort by (level, y band of 1/32 of the
-  // image) -- 256 buckets: what the order is for is that the RoIs in flight at a time tap one band of one pyramid
-  // level, and a band already holds fewer RoIs than are in flight; inside a bucket the order is whatever the LDS
-  // atomics give (results do not depend on the processing order).  ~1 us instead of the ~8 us of a full sort.
+  // the assigned RoIs were written by this workgroup just above.  A counting sort by d_roi_order_bucket (level, column
+  // strip, serpentine y bin) -- 256 buckets per level the launch has, in the dynamic LDS (the walk's staging area is dead
+  // by now; see scan_order_lds); inside a bucket the order is whatever the LDS atomics give (results do not depend on the
+  // processing order).  ~1 us instead of the ~8 us of a full sort.
   // Without an assignment (job not finished yet / reported empty) the order is the identity, so that the RoI kernel
   // visits -- and zero-fills -- every row.
   int32_t* __restrict__ order = sp.as_order.v[img];
@@ -1069,36 +1105,28 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_nms_scan(ScanParams sp) {
     // (round 6) the common case -- one chunk finished the job: every kept candidate still holds its box, its level and its row
     // of the assigned list in registers, so the counting sort runs on those instead of re-reading ao.rois / ao.level from
     // memory behind the stores above (a store -> load round trip through L2 in the middle of a one-workgroup launch)
-    __syncthreads();                               // (lvl_cnt / lvl_tot were read above; they become the buckets now)
     const int tid = threadIdx.x;
-    int* ocnt = &lvl_cnt[0][0];                    // [256]
-    int* obase = ocnt + 256;                       // [256]
-    for (int i = tid; i < 256; i += SCAN_THREADS) ocnt[i] = 0;
+    int* ocnt = reinterpret_cast<int*>(mat);       // [nl * 256]: counts, then their exclusive prefix (in place)
+    const int nb = nl * ROI_ORDER_BUCKETS_PER_LEVEL;
+    for (int i = tid; i < nb; i += SCAN_THREADS) ocnt[i] = 0;
     __syncthreads();
     int bktq[SCAN_Q], slotq[SCAN_Q];
 #pragma unroll
     for (int q = 0; q < TQ; ++q) {
       bktq[q] = -1;
       if (mylv[q] >= 0) {
-        const float4 bx = obox[q];
-        const int l = min(max(mylv[q], 0), 7);
-        const int qy = min(max((int)((bx.y + bx.w) * 0.5f * sp.ord_inv_h * 4096.0f), 0), 4095);
-        bktq[q] = l * 32 + (qy >> 7);
+        int qy, qx;
+        bktq[q] = d_roi_order_bucket(obox[q], min(mylv[q], nl - 1), sp.ord_inv_h, sp.ord_inv_w, &qy, &qx);
         slotq[q] = atomicAdd(&ocnt[bktq[q]], 1);
       }
     }
     for (int r = nkf + tid; r < K; r += SCAN_THREADS) order[r] = r;     // padded rows stay behind the valid ones
     __syncthreads();
-    {
-      int total;
-      const int v = (tid < 256) ? ocnt[tid] : 0;
-      const int ex = block_excl_scan(v, keptpre, &total);
-      if (tid < 256) obase[tid] = ex;
-    }
+    scan_order_buckets(ocnt, nb, keptpre);
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < TQ; ++q)
-      if (bktq[q] >= 0) order[obase[bktq[q]] + slotq[q]] = myrank[q];
+      if (bktq[q] >= 0) order[ocnt[bktq[q]] + slotq[q]] = myrank[q];
   } else if (order) {
     __threadfence_block();
     __syncthreads();
@@ -1107,9 +1135,10 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_nms_scan(ScanParams sp) {
     const float4* __restrict__ osrc = want_assign ? ao.rois : ((done && !ao.rois) ? out_boxes : nullptr);
     const int32_t* __restrict__ olvl = want_assign ? ao.level : nullptr;
     if (osrc) {
-      int* ocnt = &lvl_cnt[0][0];                  // [256] (the level assignment is done with it)
-      int* obase = ocnt + 256;                     // [256]
-      for (int i = tid; i < 256; i += SCAN_THREADS) ocnt[i] = 0;
+      int* ocnt = reinterpret_cast<int*>(mat);     // [nlo * 256]: counts, then their exclusive prefix (in place)
+      const int nlo = olvl ? nl : 1;
+      const int nb = nlo * ROI_ORDER_BUCKETS_PER_LEVEL;
+      for (int i = tid; i < nb; i += SCAN_THREADS) ocnt[i] = 0;
       __syncthreads();
       int bkt[2], slot[2];
 #pragma unroll
@@ -1117,26 +1146,20 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_nms_scan(ScanParams sp) {
         const int r = tid + e * SCAN_THREADS;
         bkt[e] = -1;
         if (r < nkf) {
-          const float4 bx = osrc[r];
-          const int l = olvl ? min(max(olvl[r], 0), 7) : 0;
-          const int qy = min(max((int)((bx.y + bx.w) * 0.5f * sp.ord_inv_h * 4096.0f), 0), 4095);
-          bkt[e] = l * 32 + (qy >> 7);
+          const int l = olvl ? min(max(olvl[r], 0), nlo - 1) : 0;
+          int qy, qx;
+          bkt[e] = d_roi_order_bucket(osrc[r], l, sp.ord_inv_h, sp.ord_inv_w, &qy, &qx);
           slot[e] = atomicAdd(&ocnt[bkt[e]], 1);
         } else if (r < K) {
           order[r] = r;                            // padded rows stay behind the valid ones
         }
       }
       __syncthreads();
-      {
-        int total;
-        const int v = (tid < 256) ? ocnt[tid] : 0;
-        const int ex = block_excl_scan(v, keptpre, &total);
-        if (tid < 256) obase[tid] = ex;
-      }
+      scan_order_buckets(ocnt, nb, keptpre);
       __syncthreads();
 #pragma unroll
       for (int e = 0; e < 2; ++e)
-        if (bkt[e] >= 0) order[obase[bkt[e]] + slot[e]] = tid + e * SCAN_THREADS;
+        if (bkt[e] >= 0) order[ocnt[bkt[e]] + slot[e]] = tid + e * SCAN_THREADS;
     } else {
       if (tid < K) order[tid] = tid;
       if (tid + SCAN_THREADS < K) order[tid + SCAN_THREADS] = tid + SCAN_THREADS;
@@ -1359,7 +1382,7 @@ static int nms_run(NmsJob& J, hipStream_t st) {
   sp.as_perm = per_img<int64_t*>(J, [&](int i) { return J.img[i].assign.perm; });
   sp.as_counts = per_img<int32_t*>(J, [&](int i) { return J.img[i].assign.counts; });
   sp.as_order = per_img<int32_t*>(J, [&](int i) { return K <= ODET_FUSED_ORDER_MAX_ROIS ? J.img[i].assign.order : nullptr; });
-  sp.ord_inv_h = 1.0f / (J.prep.hmax + 1.0f);
+  sp.ord_inv_h = 1.0f / (J.prep.hmax + 1.0f); sp.ord_inv_w = 1.0f / (J.prep.wmax + 1.0f);
   sp.n = n; sp.use_init = 0; sp.K = K;
   const int blind_n = J.blind_chunks < 1 ? 1 : J.blind_chunks;
   const bool fail_empty = J.fail_empty && J.img[0].out_done != nullptr;
@@ -1373,7 +1396,7 @@ static int nms_run(NmsJob& J, hipStream_t st) {
     if (lds0)
       hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<true>), dim3(1, B), dim3(SCAN_THREADS), SCAN_DYN_LDS, st, sp);
     else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, B), dim3(SCAN_THREADS), 0, st, sp);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, B), dim3(SCAN_THREADS), scan_order_lds(sp), st, sp);
     ODET_LAUNCH_CHECK();
   }
   int blind = J.blind_chunks < 1 ? 1 : J.blind_chunks;
@@ -1434,7 +1457,7 @@ static int nms_run(NmsJob& J, hipStream_t st) {
       hipLaunchKernelGGL(k_nms_mask, dim3(tri_tiles(cap), 1), dim3(256), 0, st, cst, csb, J.thr, lt, dg, 0);
       ODET_LAUNCH_CHECK();
       si.fail_empty = (!host_checks && fail_empty && c == max_chunks) ? 1 : 0;
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, 1), dim3(SCAN_THREADS), 0, st, si);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, 1), dim3(SCAN_THREADS), scan_order_lds(si), st, si);
       ODET_LAUNCH_CHECK();
     }
     return ODET_OK;
@@ -1457,7 +1480,7 @@ static int nms_run(NmsJob& J, hipStream_t st) {
       ODET_LAUNCH_CHECK();
       hipLaunchKernelGGL(k_nms_mask, dim3(tri_tiles(cap), B), dim3(256), 0, st, cstates, csboxes, J.thr, Lts, diags, 0);
       ODET_LAUNCH_CHECK();
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, B), dim3(SCAN_THREADS), 0, st, s1);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, B), dim3(SCAN_THREADS), scan_order_lds(s1), st, s1);
       ODET_LAUNCH_CHECK();
     }
     // chunks 2..: the full order of every image (radix sort of all n keys) and further chunks of NMS_CHUNK candidates,
@@ -1485,7 +1508,7 @@ static int nms_run(NmsJob& J, hipStream_t st) {
         hipLaunchKernelGGL(k_nms_mask, dim3(tri_tiles(cap), B), dim3(256), 0, st, cstates, csboxes, J.thr, Lts, diags, 0);
         ODET_LAUNCH_CHECK();
         s2.fail_empty = (fail_empty && c == blind - 1) ? 1 : 0;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, B), dim3(SCAN_THREADS), 0, st, s2);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, B), dim3(SCAN_THREADS), scan_order_lds(s2), st, s2);
         ODET_LAUNCH_CHECK();
       }
     }

@@ -348,17 +348,38 @@ __device__ __forceinline__ unsigned long long bitonic_sort_1024_reg(unsigned lon
 }
 
 
-// Processing-order key of RoI row r for the RoI kernel (odet_roi_order): (level, y centre, x centre) quantised to
-// 12 bits each, row index in the low word; rows >= cnt (padding of the static shape) sort last, rows >= n never.
+// THE processing order of the RoI kernel (the only place that defines it; tools/roi_order_model.py restates it on the
+// host): a level's map is cut into ROI_ORDER_STRIPS column strips by the box centre's x, a strip is walked in
+// ROI_ORDER_YBINS bins of the centre's y, downwards on even strips and upwards on odd ones (serpentine: the turn into the
+// next strip starts where the last one ended, so the halo the two strips share is still in L2).  What the RoIs in flight
+// at a time tap is then a window one strip wide and a few bins tall, which fits a third of an XCD's L2; a y band across
+// the whole map (the order before) did not.  qy / qx: the centre quantised to 12 bits, clamped.
+#define ROI_ORDER_STRIPS 8
+#define ROI_ORDER_YBINS 32
+#define ROI_ORDER_BUCKETS_PER_LEVEL (ROI_ORDER_STRIPS * ROI_ORDER_YBINS)
+__device__ __forceinline__ int d_roi_order_bucket(float4 b, int l, float inv_h, float inv_w, int* qy_out, int* qx_out) {
+  const int qy = min(max((int)((b.y + b.w) * 0.5f * inv_h * 4096.0f), 0), 4095);
+  const int qx = min(max((int)((b.x + b.z) * 0.5f * inv_w * 4096.0f), 0), 4095);
+  const int strip = qx >> 9;
+  int yb = qy >> 7;
+  if (strip & 1) yb = ROI_ORDER_YBINS - 1 - yb;
+  *qy_out = qy; *qx_out = qx;
+  return (l * ROI_ORDER_STRIPS + strip) * ROI_ORDER_YBINS + yb;
+}
+
+// Processing-order key of RoI row r for the RoI kernel (odet_roi_order): (bucket of d_roi_order_bucket: 11 bits, then qy,
+// qx: 12 bits each, then the row: 14 bits, n <= 8192), so the stand-alone order visits the buckets in the sequence of the
+// fused one (k_nms_scan) and is deterministic inside a bucket; rows >= cnt (padding of the static shape) sort last, rows
+// >= n never.  The row is the low ROI_ORDER_ROW_BITS bits.
+#define ROI_ORDER_ROW_BITS 14
 __device__ __forceinline__ unsigned long long d_roi_order_key(int r, int n, int cnt, const float4* rois, const int32_t* lvl,
                                                                float inv_h, float inv_w) {
   if (r >= n) return ~0ull;
   if (r >= cnt) return (0xFFFFFFFEull << 32) | (unsigned)r;          // padded rows last (they are zero-filled)
-  const float4 b = rois[r];
   const int l = lvl ? min(max(lvl[r], 0), 7) : 0;
-  const int qy = min(max((int)((b.y + b.w) * 0.5f * inv_h * 4096.0f), 0), 4095);
-  const int qx = min(max((int)((b.x + b.z) * 0.5f * inv_w * 4096.0f), 0), 4095);
-  return ((unsigned long long)((l << 24) | (qy << 12) | qx) << 32) | (unsigned)r;
+  int qy, qx;
+  const int bucket = d_roi_order_bucket(rois[r], l, inv_h, inv_w, &qy, &qx);
+  return ((((unsigned long long)bucket << 24) | (unsigned long long)((qy << 12) | qx)) << ROI_ORDER_ROW_BITS) | (unsigned)r;
 }
 
 // model/fpn/base_fpn_model.py:303-324 _assign_levels by ONE workgroup of THREADS threads: level per RoI,

@@ -763,8 +763,9 @@ int odet_roi_pool_batch(const RoiImageIO* io, int B, int num_levels, int C, int 
 
 // ---- spatial processing order -------------------------------------------------------------------
 // Output row r always holds RoI r; only the ORDER in which workgroups pick RoIs changes: sorted by
-// (level, y centre, x centre) so that the RoIs an XCD processes (a contiguous chunk of the order) tap one
-// band of one pyramid level -- fewer lines fetched by several XCDs, and a sliding working set in each L2.
+// (level, column strip, serpentine y bin, then y, x centre; d_roi_order_key) so that the RoIs an XCD processes (a
+// contiguous chunk of the order) tap a window one strip wide of one pyramid level -- a working set that slides
+// through the L2 and still fits when two or three launches share it.
 struct RoiOrderParams {
   PerImg<const float4*> rois;
   PerImg<const int32_t*> roi_level;
@@ -787,18 +788,19 @@ __global__ void __launch_bounds__(1024) k_roi_order(RoiOrderParams p) {
   if (p.P2 <= 1024) {
     unsigned long long k = make_key(tid);
     k = bitonic_sort_1024_reg(k, okeys);
-    if (tid < p.n) order[tid] = (int32_t)(k & 0xFFFFFFFFull);
+    if (tid < p.n) order[tid] = (int32_t)(k & ((1ull << ROI_ORDER_ROW_BITS) - 1));
   } else {
     for (int i = tid; i < p.P2; i += 1024) okeys[i] = make_key(i);
     __syncthreads();
     bitonic_sort_u64(okeys, p.P2, 1024);
-    for (int i = tid; i < p.n; i += 1024) order[i] = (int32_t)(okeys[i] & 0xFFFFFFFFull);
+    for (int i = tid; i < p.n; i += 1024) order[i] = (int32_t)(okeys[i] & ((1ull << ROI_ORDER_ROW_BITS) - 1));
   }
 }
 
 int odet_roi_order_batch(const RoiOrderIO* io, int B, int n, int image_h, int image_w, hipStream_t st) {
   ODET_REQUIRE(io && B >= 1 && B <= ODET_MAX_BATCH, "odet_roi_order: bad batch");
   ODET_REQUIRE(n >= 0 && n <= 8192, "odet_roi_order: n %d out of range (<= 8192)", n);
+  static_assert(8192 <= (1 << ROI_ORDER_ROW_BITS), "the key keeps the row in its low bits");
   ODET_REQUIRE(image_h > 0 && image_w > 0, "odet_roi_order: bad image shape");
   if (n == 0) return ODET_OK;
   RoiOrderParams p;

@@ -1147,7 +1147,10 @@ class ProfEvent:
 
 
 def roi_order(rois, roi_level, image_shape, count_dev=None, out=None):
-    """Spatial processing order (int32 [n]) of the RoIs for roi_pool(order=...): sorted by (level, y, x)."""
+    """Spatial processing order (int32 [n]) of the RoIs for roi_pool(order=...): sorted by (level, column strip of 1/8 of the
+    image by the box centre's x, bin of 1/32 of the image by its y -- downwards on even strips, upwards on odd ones --, then
+    y, x, row); rows >= count_dev[0] follow in row order.  The proposal stage writes the same bucket sequence itself up to
+    FUSED_ORDER_MAX_ROIS proposals (arbitrary order inside a bucket there)."""
     rois = _boxes(rois, 'rois')
     n = rois.shape[0]
     if out is None:
