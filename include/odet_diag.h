@@ -53,7 +53,7 @@ typedef struct odet_debug_tile {
 /* entry `index` of the family's tile list, read from the table the launchers dispatch on (kTiles / F32_FOR_TILES / X3_FOR_TILES
  * then X2_FOR_TILES); returns 1 past the end */
 int odet_debug_tile_table(int family, int index, odet_debug_tile_t* out);
-/* on: the launchers of the three files and the RoI launcher (csrc/roi.hip) check their arguments, plan, record and return ODET_OK before any HIP call (the kernels'
+/* on: the launchers of the three files, the RoI launcher (csrc/roi.hip) and the NMS driver (csrc/nms.hip) check their arguments, plan, record and return ODET_OK before any HIP call (the kernels'
  * one-time set-up included) -- plans can be read on a machine without a GPU, with pointer-valued integers for the arrays */
 int odet_debug_plan_only(int on);
 /* ---- which RoI launch ran (csrc/roi.hip).  odet_roi_pool_batch -- behind every odet_roi_pool* entry point and the RoI stage of
@@ -75,6 +75,33 @@ typedef struct odet_debug_roi_plan {
 int odet_debug_last_roi_plan(odet_debug_roi_plan_t* out);
 /* the same planning function on its own: what a launch of B images, n RoIs each, would be */
 int odet_debug_roi_plan(int B, int C, int n, int pool_size, int f16, int pool_mode, int norm_mode, odet_debug_roi_plan_t* out);
+/* ---- what the NMS driver planned (csrc/nms.hip).  nms_run -- behind odet_nms, odet_region_proposal, odet_fpn_proposals,
+ * odet_frcnn_proposals and the proposal stage of odet_fpn_step_enqueue[_batch] -- plans a job from (n, K, first_chunk,
+ * blind_chunks, mode, B) alone; chunk c = 0 is the one from the radix selection, chunks c >= 1 the further ones. */
+typedef struct odet_debug_nms_plan {
+  int n, K, first_chunk, B;
+  int sync_free;        /* 1: out_done given (exactly `blind` chunks, no host read-back), 0: exact mode */
+  int blind;            /* blind_chunks, at least 1 */
+  int target;           /* candidates chunk 0 asks the selection for */
+  int lds0, limit;      /* chunk 0 on the LDS-resident scan; capacity of the chunk-0 scan */
+  int wide;             /* the selection also ranks chunk 1's candidates */
+  int sel_target, sel_limit;
+  int prep_grid, sel_grid, rank_wgs; /* grid.x of k_rp_prepare, of the k_sel_* launches, of k_sel_rank */
+  int cap0, tiles0;     /* chunk 0: padded candidates, workgroups of k_nms_mask */
+  int cap, tiles;       /* the same for every further chunk */
+  int further;          /* sync-free: further chunks enqueued (blind - 1) */
+  int sel_chunks;       /* sync-free: chunks 1 .. sel_chunks read the ranked selection, later ones the full order */
+  int full_sort;        /* sync-free: the radix sort of all n keys is enqueued */
+  int fail_empty_chunk; /* sync-free: the one chunk whose scan may report an incomplete job empty; exact: -1 */
+  int max_chunks;       /* exact: bound of the host-checked loop over further chunks; sync-free: 0 */
+  long long count;      /* NMS jobs recorded by this process so far (0 from odet_debug_nms_plan) */
+} odet_debug_nms_plan_t;
+/* the plan of this process's latest NMS job, written after the driver's argument and workspace checks and before its first HIP
+ * call (in plan-only mode: before it returns; the trivial n == 0 / max_output == 0 results then return before their memsets
+ * and record nothing); count == 0 and all else zero before the first one */
+int odet_debug_last_nms_plan(odet_debug_nms_plan_t* out);
+/* the same planning function on its own: what a job of B images, n candidates each, would be */
+int odet_debug_nms_plan(int n, int K, int first_chunk, int blind_chunks, int sync_free, int B, odet_debug_nms_plan_t* out);
 /* the float32 -> float16 conversion of the library's epilogues on its own (the packed conversion of csrc/odet_internal.h under
  * the product's compiler flags): n float32 values (n % 8 == 0, device, 16-byte aligned) -> their float16 bits, once through
  * d_cvt8_f16 (out_pk) and once through d_cvt_pk_f16 + d_pack8_f16 (out_pack8); values 2k / 2k + 1 share one packed instruction */

@@ -1025,6 +1025,29 @@ def test_nms_sync_free_chunks_from_selection_then_full_order():
         np.testing.assert_array_equal(h(idx[:m]), want[:m])
 
 
+def test_nms_exact_mode_with_unchecked_chunks():
+    """Exact mode (no `done`) with blind_chunks > 1: 9000 boxes that are exact copies of 50 mutually disjoint ones, K = 100.
+    Greedy NMS keeps 50 < K, so the walk has to reach the end of the order: chunk 0 (256 candidates) and three further
+    chunks of the full order, of which blind_chunks = 3 enqueues two without asking and checks the state before the third.
+    The result equals the C oracle, the host-checked walk (blind_chunks = 1) and the sync-free one, which completes."""
+    rng = np.random.default_rng(35)
+    n, k = 9000, 100
+    base = np.float32([[120 * (i % 10), 80 * (i // 10), 120 * (i % 10) + 100, 80 * (i // 10) + 60] for i in range(50)])
+    boxes = base[rng.permutation(n) % 50]
+    scores = syn.scores_distinct(n, rng)
+    want = co.nms(boxes, scores, k, 0.5)
+    assert len(want) == 50
+    idx, cnt = ops.nms(g(boxes), g(scores), k, 0.5, blind_chunks=3)
+    got = h(idx[:int(cnt.item())])
+    np.testing.assert_array_equal(got, want)
+    idx, cnt = ops.nms(g(boxes), g(scores), k, 0.5, blind_chunks=1)
+    np.testing.assert_array_equal(h(idx[:int(cnt.item())]), got)
+    done = torch.zeros(1, dtype=torch.int32, device='cuda')
+    idx, cnt = ops.nms(g(boxes), g(scores), k, 0.5, blind_chunks=5, done=done)
+    assert int(done.item()) == 1
+    np.testing.assert_array_equal(h(idx[:int(cnt.item())]), got)
+
+
 @pytest.mark.parametrize('name', ['config1_vgg16_600x800', 'config2_resnet_c4_800x1333', 'config3_resnet101_fpn_800x1333',
                                   'config5_resnet101_fpn_1333x1333_81_classes'])
 def test_full_size_hashes_from_the_hip_path(name):

@@ -70,7 +70,7 @@ def test_shipped_library_has_no_debug_hooks():
     diag = open(os.path.join(ROOT, 'include', 'odet_diag.h')).read()
     hooks = ('odet_debug_conv_tile', 'odet_debug_x3_tile', 'odet_debug_f32_tile', 'odet_debug_last_plan', 'odet_debug_tile_table',
              'odet_debug_plan_only', 'odet_debug_cvt_f16', 'odet_debug_tg_key_mask', 'odet_debug_last_roi_plan',
-             'odet_debug_roi_plan')
+             'odet_debug_roi_plan', 'odet_debug_last_nms_plan', 'odet_debug_nms_plan')
     declared = sorted(set(re.findall(r'\b(odet_debug_[a-z0-9_]+)\s*\(', re.sub(r'/\*.*?\*/', '', diag, flags=re.S))))
     assert declared == sorted(hooks)
     lib = _build.build_diag()
@@ -78,7 +78,7 @@ def test_shipped_library_has_no_debug_hooks():
     assert sorted(set(re.findall(r'\b(odet_debug_[a-z0-9_]+)\b', out))) == sorted(hooks)
     from tools import _diag
     assert sorted(_diag.DIAG_SIGNATURES) == sorted(hooks)
-    assert 'conv_f32.hip' in _build.DIAG_SOURCES and 'roi.hip' in _build.DIAG_SOURCES
+    assert 'conv_f32.hip' in _build.DIAG_SOURCES and 'roi.hip' in _build.DIAG_SOURCES and 'nms.hip' in _build.DIAG_SOURCES
 
 
 def test_f32_form_is_per_thread_context():

@@ -71,11 +71,11 @@ def build(force=False, verbose=False):
     return LIB
 
 
-# ---- the DIAGNOSTIC build: the same sources, the files with hooks (tile forcing, the targets' key mask) compiled with -DODET_DIAG
+# ---- the DIAGNOSTIC build: the same sources, the files with hooks (tile forcing, the targets' key mask, the launch plans) compiled with -DODET_DIAG
 # (include/odet_diag.h).
 # Test / tool infrastructure (tools/_diag.py loads it explicitly); the product never loads it and the shipped library has no hook.
 DIAG_LIB = os.path.join(os.path.dirname(PKG), 'tools', 'libodet_hip_diag.so')
-DIAG_SOURCES = ['conv3x3.hip', 'conv_f32.hip', 'conv_x3.hip', 'targets.hip', 'roi.hip']
+DIAG_SOURCES = ['conv3x3.hip', 'conv_f32.hip', 'conv_x3.hip', 'targets.hip', 'roi.hip', 'nms.hip']
 
 
 def build_diag(force=False, verbose=False):

@@ -41,7 +41,7 @@
 #include <algorithm>
 #include <mutex>
 
-#include "odet_internal.h"
+#include "conv_diag.h"   // (odet_internal.h; in the diagnostic build the plan-only switch)
 
 #define NMS_CHUNK 4096
 #define NMS_SEL_MAX (2 * NMS_CHUNK)   // most candidates one radix selection hands over (first chunk + one more)
@@ -1227,6 +1227,107 @@ static inline int tri_tiles(int cap) {
   return nb * (nb + 1) / 2;
 }
 
+// ---- the launch plan ------------------------------------------------------------------------------------------
+// Everything nms_run decides about a job from its sizes alone (host; the diagnostic build records it,
+// include/odet_diag.h).  The prepare mode picks the kernel instantiation, not the plan.
+struct NmsPlan {
+  int n, K, first_chunk, B, sync_free;
+  int blind;              // blind_chunks, at least 1: chunks enqueued without asking the host
+  int target;             // candidates chunk 0 asks the selection for (first_chunk_target)
+  int lds0, limit;        // chunk 0 on the LDS-resident scan (its candidates fit 24 blocks); capacity of the chunk-0 scan
+  int wide;               // the selection also ranks the candidates of chunk 1 (sync-free jobs with a second chunk)
+  int sel_target, sel_limit;
+  int prep_grid, sel_grid, rank_wgs;
+  int cap0, tiles0;       // chunk 0: padded candidates, 64x64 tiles of the lower triangle
+  int cap, tiles;         // the same for every further chunk
+  int further;            // sync-free: further chunks enqueued (blind - 1)
+  int sel_chunks;         // sync-free: how many of them (chunk 1) read the ranked selection; the others the full order
+  int full_sort;          // sync-free: the radix sort of all n keys is enqueued (blind > 2)
+  int fail_empty_chunk;   // sync-free: the one chunk that reports an incomplete job empty (the last, blind - 1); exact: -1
+  int max_chunks;         // exact: bound of the host-checked loop over further chunks
+};
+
+static int nms_plan(int n, int K, int first_chunk, int blind_chunks, int sync_free, int B, NmsPlan* out) {
+  NmsPlan p;
+  p.n = n; p.K = K; p.first_chunk = first_chunk; p.B = B; p.sync_free = sync_free ? 1 : 0;
+  p.blind = blind_chunks < 1 ? 1 : blind_chunks;
+  p.target = first_chunk_target(n, K, first_chunk);
+  p.lds0 = p.target <= SCAN_LDS_CAND ? 1 : 0;
+  p.limit = p.lds0 ? SCAN_LDS_CAND : NMS_CHUNK;
+  // Sync-free jobs that ask for a second chunk get it from the SAME radix selection: one NMS_CHUNK more candidates
+  // are selected and ranked, and chunk 1 runs on that order -- no radix sort of all anchors for it.
+  p.wide = (p.sync_free && p.blind >= 2) ? 1 : 0;
+  p.sel_target = p.wide ? (int)std::min<long long>(n, (long long)p.target + NMS_CHUNK) : p.target;
+  p.sel_limit = p.wide ? NMS_SEL_MAX : p.limit;
+  p.prep_grid = (n + PREP_TILE - 1) / PREP_TILE;
+  p.sel_grid = (n + SEL_TILE - 1) / SEL_TILE;
+  // the tie split's scratch is the bit-matrix buffer (idle during the selection): per block 256 counters of 2 bytes fit
+  // its 2 MiB up to ~8.4 M anchors
+  if (p.wide)
+    ODET_REQUIRE((size_t)p.sel_grid * 256 * sizeof(unsigned short) <= (size_t)NMS_WORDS * NMS_CHUNK * sizeof(u64),
+                 "odet_nms: %d anchors exceed the tie split's scratch (the bit-matrix buffer)", n);
+  p.rank_wgs = (std::min(n, p.sel_limit) + 63) / 64;
+  p.cap0 = std::min(p.limit, (n + 63) / 64 * 64);
+  p.tiles0 = tri_tiles(p.cap0);
+  p.cap = std::min(NMS_CHUNK, (n + 63) / 64 * 64);
+  p.tiles = tri_tiles(p.cap);
+  p.further = p.sync_free ? p.blind - 1 : 0;
+  p.sel_chunks = p.further >= 1 ? 1 : 0;
+  p.full_sort = p.further >= 2 ? 1 : 0;
+  p.fail_empty_chunk = p.sync_free ? p.blind - 1 : -1;
+  p.max_chunks = p.sync_free ? 0 : (n + NMS_CHUNK - 1) / NMS_CHUNK + 1;
+  *out = p;
+  return ODET_OK;
+}
+
+#ifdef ODET_DIAG
+// Diagnostic build only (include/odet_diag.h): the plan of the latest NMS job, written after nms_run's checks and before its
+// first HIP call, and the plan-only mode of csrc/conv_diag.h (the switch lives in conv3x3.hip).  The shipped library has neither.
+static std::mutex g_nms_plan_mutex;
+static odet_debug_nms_plan_t g_last_nms_plan;
+static void nms_plan_to_record(const NmsPlan& p, odet_debug_nms_plan_t* r, long long count) {
+  *r = odet_debug_nms_plan_t{p.n, p.K, p.first_chunk, p.B, p.sync_free, p.blind, p.target, p.lds0, p.limit, p.wide,
+                             p.sel_target, p.sel_limit, p.prep_grid, p.sel_grid, p.rank_wgs, p.cap0, p.tiles0, p.cap,
+                             p.tiles, p.further, p.sel_chunks, p.full_sort, p.fail_empty_chunk, p.max_chunks, count};
+}
+static void nms_diag_record(const NmsPlan& p) {
+  std::lock_guard<std::mutex> lock(g_nms_plan_mutex);
+  nms_plan_to_record(p, &g_last_nms_plan, g_last_nms_plan.count + 1);
+}
+extern "C" int odet_debug_last_nms_plan(odet_debug_nms_plan_t* out) {
+  ODET_REQUIRE(out, "odet_debug_last_nms_plan: null record");
+  std::lock_guard<std::mutex> lock(g_nms_plan_mutex);
+  *out = g_last_nms_plan;       // (count == 0, everything else zero: no job yet)
+  return ODET_OK;
+}
+extern "C" int odet_debug_nms_plan(int n, int K, int first_chunk, int blind_chunks, int sync_free, int B,
+                                   odet_debug_nms_plan_t* out) {
+  ODET_REQUIRE(out && n > 0 && K > 0 && first_chunk >= 0 && first_chunk <= NMS_CHUNK && B >= 1 && B <= ODET_MAX_BATCH &&
+               (sync_free || B == 1), "odet_debug_nms_plan: bad arguments");
+  NmsPlan p;
+  const int rc = nms_plan(n, K, first_chunk, blind_chunks, sync_free, B, &p);
+  if (rc == ODET_OK) nms_plan_to_record(p, out, 0);
+  return rc;
+}
+#define ODET_DIAG_NMS_PLAN(plan)               \
+  do {                                         \
+    nms_diag_record(plan);                     \
+    if (odet_diag_plan_only()) return ODET_OK; \
+  } while (0)
+// (the trivial results of the entry points -- n == 0, max_output == 0 -- are memsets: none in plan-only mode)
+#define ODET_DIAG_NMS_TRIVIAL()                \
+  do {                                         \
+    if (odet_diag_plan_only()) return ODET_OK; \
+  } while (0)
+#else
+#define ODET_DIAG_NMS_PLAN(plan) \
+  do {                           \
+  } while (0)
+#define ODET_DIAG_NMS_TRIVIAL() \
+  do {                          \
+  } while (0)
+#endif
+
 struct NmsImage {           // per-image pointers of a job
   const float4* boxes_in;   // PREP_NMS: boxes; PREP_RP: anchors
   const float* deltas;
@@ -1263,13 +1364,83 @@ static PerImg<T> per_img(const NmsJob& J, F get) {
   return t;
 }
 
-// Chunk 0 (select path) is always enqueued.  blind_chunks > 1: the fallback (full sort + further
-// chunks) is enqueued without looking at the device state; its kernels exit at once when chunk 0
-// finished the job.  out_done == nullptr: exact mode -- afterwards the host reads the state (one
-// sync per further chunk) until the device reports done.  out_done != nullptr: sync-free mode --
-// exactly blind_chunks chunks, *out_done tells the caller whether the result is complete.
-// Batches (B > 1) run chunk 0 of every image in the same launches (blockIdx.y = image); the
-// fallback is per image, so batches require the sync-free mode with blind_chunks == 1.
+// the LDS-resident scan of chunk 0 stages the bit matrix in more than 64 KB of dynamic LDS: allowed once per device
+static int nms_scan_setup() {
+  static OdetPerDeviceOnce once;    // (executor threads may arrive here together)
+  ODET_HIP(once.run([] {
+    return hipFuncSetAttribute((const void*)k_nms_scan<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SCAN_DYN_LDS);
+  }));
+  return ODET_OK;
+}
+
+// 1. prepare: the job's mode picks the instantiation
+static int nms_prepare(const NmsJob& J, const NmsPlan& P, hipStream_t st) {
+  const dim3 grid(P.prep_grid, P.B), block(256);
+  if (J.mode == PREP_NMS)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rp_prepare<PREP_NMS>), grid, block, 0, st, J.prep);
+  else if (J.mode == PREP_RP)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rp_prepare<PREP_RP>), grid, block, 0, st, J.prep);
+  else if (J.mode == PREP_FRCNN)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rp_prepare<PREP_FRCNN>), grid, block, 0, st, J.prep);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rp_prepare<PREP_FPN>), grid, block, 0, st, J.prep);
+  ODET_LAUNCH_CHECK();
+  return ODET_OK;
+}
+
+// One further chunk (every chunk after chunk 0) of all images of a job: NMS_CHUNK candidates from wherever the walk stopped,
+// k_nms_gather -> k_nms_cross against the boxes kept so far -> k_nms_mask -> k_nms_scan<false>, blockIdx.y = image.  Every
+// launch is guarded by the image's device-side `done` word: an image that is finished skips all four.
+struct NmsChunks {
+  const NmsJob& J;
+  const NmsPlan& P;
+  hipStream_t st;
+  ScanParams sp;            // chunk 0's; a further chunk differs in use_init, sorted_idx and fail_empty
+  // the per-image tables, built once from the carved workspaces
+  PerImg<const NmsState*> cstates;
+  PerImg<float4*> sboxes, sorig;
+  PerImg<const float4*> csboxes, kept;
+  PerImg<u64*> Lt, diag, rinit;
+
+  // from_sel: `sorted_idx` is the ranked selection (chunk 1 of a sync-free job), else the full order
+  int launch(int from_sel, const PerImg<const uint32_t*>& sorted_idx, int fail_empty) const {
+    const dim3 rows((P.cap + 255) / 256, P.B), block(256);
+    hipLaunchKernelGGL(k_nms_gather, rows, block, 0, st, sp.st, P.n, P.cap, from_sel, J.prep, J.mode, sorted_idx, sboxes, sorig);
+    ODET_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_nms_cross, rows, block, 0, st, cstates, csboxes, kept, J.thr, rinit);
+    ODET_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_nms_mask, dim3(P.tiles, P.B), block, 0, st, cstates, csboxes, J.thr, Lt, diag, 0);
+    ODET_LAUNCH_CHECK();
+    ScanParams s = sp;
+    s.use_init = 1; s.sorted_idx = sorted_idx; s.fail_empty = fail_empty;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, P.B), dim3(SCAN_THREADS), scan_order_lds(s), st, s);
+    ODET_LAUNCH_CHECK();
+    return ODET_OK;
+  }
+};
+
+// reads an image's state back: one stream sync (exact mode only)
+static int nms_done_on_host(const NmsState* state, hipStream_t st, bool* done) {
+  NmsState h;
+  ODET_HIP(hipMemcpyAsync(&h, state, sizeof(h), hipMemcpyDeviceToHost, st));
+  ODET_HIP(hipStreamSynchronize(st));
+  *done = h.done != 0;
+  return ODET_OK;
+}
+
+// The driver.  nms_plan decides everything that follows from the sizes; every launch covers the whole batch (blockIdx.y =
+// image).  Chunk 0 is always enqueued: prepare, the radix selection and its ranking, the bit matrix, the scan (LDS-resident
+// when the plan says its candidates fit).  What follows depends on the mode:
+//  * sync-free (out_done != nullptr; the only mode of a batch, B > 1): exactly `blind` chunks are enqueued and the host never
+//    looks at the device; *out_done tells the caller whether the result is complete.  Chunk 1 reads the ranked selection (the
+//    selection was asked for one NMS_CHUNK more candidates: plan.wide).  Only with blind > 2 is the full radix sort of all n
+//    keys enqueued, once for the batch, and chunks 2 .. blind - 1 read that order.  The kernels of a further chunk exit at once
+//    for an image that is done.
+//  * exact (out_done == nullptr, one image): the full sort, then further chunks from the full order until the device reports
+//    done.  Chunks c < blind are enqueued unchecked; from there on the host reads the state back before each chunk (one sync
+//    per chunk), and with blind == 1 once before the sort as well.  The loop ends at plan.max_chunks.
+// fail_empty (the fused proposal stages: an incomplete sync-free job reports zero proposals) is set on ONE scan only, that of
+// the job's last sync-free chunk (plan.fail_empty_chunk); exact jobs never set it.
 static int nms_run(NmsJob& J, hipStream_t st) {
   const int n = J.n, K = J.K, B = J.B;
   if (B < 1 || B > ODET_MAX_BATCH) return odet_set_error(ODET_E_INVALID, "odet_nms: batch %d out of range", B);
@@ -1285,10 +1456,12 @@ static int nms_run(NmsJob& J, hipStream_t st) {
       if (!J.img[i].out_done)
         return odet_set_error(ODET_E_INVALID, "odet_nms: batches need the sync-free mode (out_done)");
   }
-  static OdetPerDeviceOnce once;    // (executor threads may arrive here together)
-  ODET_HIP(once.run([] {
-    return hipFuncSetAttribute((const void*)k_nms_scan<true>, hipFuncAttributeMaxDynamicSharedMemorySize, SCAN_DYN_LDS);
-  }));
+  NmsPlan P;
+  const int prc = nms_plan(n, K, J.first_chunk, J.blind_chunks, J.img[0].out_done != nullptr, B, &P);
+  if (prc != ODET_OK) return prc;
+  ODET_DIAG_NMS_PLAN(P);
+  int rc = nms_scan_setup();
+  if (rc != ODET_OK) return rc;
   const PerImg<NmsHeader*> hdrs = per_img<NmsHeader*>(J, [&](int i) { return w[i].hdr; });
   const PerImg<const uint32_t*> keys = per_img<const uint32_t*>(J, [&](int i) { return (const uint32_t*)w[i].keys_a; });
   if (!J.ws_clean) {
@@ -1304,46 +1477,23 @@ static int nms_run(NmsJob& J, hipStream_t st) {
   J.prep.boxes_out = per_img<float4*>(J, [&](int i) { return J.img[i].boxes_out; });
   J.prep.keys = per_img<uint32_t*>(J, [&](int i) { return w[i].keys_a; });
   J.prep.hdr = hdrs;
+  rc = nms_prepare(J, P, st);
+  if (rc != ODET_OK) return rc;
+  // 2. select + order the first chunk (plan.wide: and chunk 1)
+  const uint32_t sel_target = (uint32_t)P.sel_target;
+  NmsChunks ch{J, P, st};
+  ch.sboxes = per_img<float4*>(J, [&](int i) { return w[i].sboxes; });
+  ch.sorig = per_img<float4*>(J, [&](int i) { return w[i].sorig; });
   {
-    dim3 grid((n + PREP_TILE - 1) / PREP_TILE, B), block(256);
-    if (J.mode == PREP_NMS)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rp_prepare<PREP_NMS>), grid, block, 0, st, J.prep);
-    else if (J.mode == PREP_RP)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rp_prepare<PREP_RP>), grid, block, 0, st, J.prep);
-    else if (J.mode == PREP_FRCNN)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rp_prepare<PREP_FRCNN>), grid, block, 0, st, J.prep);
-    else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rp_prepare<PREP_FPN>), grid, block, 0, st, J.prep);
-    ODET_LAUNCH_CHECK();
-  }
-  // 2. select + order the first chunk
-  const uint32_t target = (uint32_t)first_chunk_target(n, K, J.first_chunk);
-  // chunk 0 runs on the LDS-resident scan when its candidates are guaranteed to fit 24 blocks
-  const bool lds0 = target <= (uint32_t)SCAN_LDS_CAND;
-  const uint32_t limit = lds0 ? (uint32_t)SCAN_LDS_CAND : (uint32_t)NMS_CHUNK;      // capacity of the chunk-0 scan
-  // Sync-free jobs that ask for a second chunk get it from the SAME radix selection: one NMS_CHUNK more candidates
-  // are selected and ranked, and chunk 1 runs on that order in launches shared by the whole batch -- no per-image
-  // radix sort of all anchors for it.
-  const int blind_req = J.blind_chunks < 1 ? 1 : J.blind_chunks;
-  const bool wide = J.img[0].out_done != nullptr && blind_req >= 2;
-  const uint32_t sel_target = wide ? (uint32_t)std::min<long long>(n, (long long)target + NMS_CHUNK) : target;
-  const uint32_t sel_limit = wide ? (uint32_t)NMS_SEL_MAX : limit;
-  const PerImg<const float4*> nboxes = per_img<const float4*>(J, [&](int i) { return J.img[i].boxes; });
-  const PerImg<float4*> sboxes = per_img<float4*>(J, [&](int i) { return w[i].sboxes; });
-  const PerImg<float4*> sorig = per_img<float4*>(J, [&](int i) { return w[i].sorig; });
-  {
-    dim3 grid((n + SEL_TILE - 1) / SEL_TILE, B), block(SEL_BLOCK);
+    dim3 grid(P.sel_grid, B), block(SEL_BLOCK);
     hipLaunchKernelGGL(k_sel_hist2, grid, block, 0, st, hdrs, keys, n, sel_target);
     ODET_LAUNCH_CHECK();
     const PerImg<u64*> cand = per_img<u64*>(J, [&](int i) { return w[i].cand; });
-    hipLaunchKernelGGL(k_sel_compact, grid, block, 0, st, hdrs, keys, n, sel_target, sel_limit, cand);
+    hipLaunchKernelGGL(k_sel_compact, grid, block, 0, st, hdrs, keys, n, sel_target, (uint32_t)P.sel_limit, cand);
     ODET_LAUNCH_CHECK();
-    if (wide) {
+    if (P.wide) {
       // a boundary bin too large for the selection (thousands of equal keys: a saturated RPN) is split exactly in
       // (key, index) order; both launches exit at once when the bin fitted.  Scratch: the bit-matrix buffer (idle here).
-      // (per block 256 counters of 2 bytes: fits the 2 MiB of the matrix buffer up to ~8.4 M anchors)
-      ODET_REQUIRE((size_t)grid.x * 256 * sizeof(unsigned short) <= (size_t)NMS_WORDS * NMS_CHUNK * sizeof(u64),
-                   "odet_nms: %d anchors exceed the tie split's scratch (the bit-matrix buffer)", n);
       const PerImg<unsigned short*> bh = per_img<unsigned short*>(J, [&](int i) { return (unsigned short*)w[i].Lt; });
       hipLaunchKernelGGL(k_sel_tie_hist, grid, block, 0, st, hdrs, keys, n, bh);
       ODET_LAUNCH_CHECK();
@@ -1353,25 +1503,27 @@ static int nms_run(NmsJob& J, hipStream_t st) {
                          per_img<const unsigned short*>(J, [&](int i) { return (const unsigned short*)w[i].Lt; }), cand);
       ODET_LAUNCH_CHECK();
     }
-    const int rank_wgs = (std::min(n, (int)sel_limit) + 63) / 64;
-    hipLaunchKernelGGL(k_sel_rank, dim3(rank_wgs, B), dim3(RANK_THREADS), 0, st, hdrs, n, (int)limit,
+    hipLaunchKernelGGL(k_sel_rank, dim3(P.rank_wgs, B), dim3(RANK_THREADS), 0, st, hdrs, n, P.limit,
                        per_img<const u64*>(J, [&](int i) { return (const u64*)w[i].cand; }), J.prep, J.mode,
-                       per_img<uint32_t*>(J, [&](int i) { return w[i].vals_b; }), sboxes, sorig);
+                       per_img<uint32_t*>(J, [&](int i) { return w[i].vals_b; }), ch.sboxes, ch.sorig);
     ODET_LAUNCH_CHECK();
   }
   // 3./4. chunk 0
-  const PerImg<const NmsState*> cstates = per_img<const NmsState*>(J, [&](int i) { return (const NmsState*)&w[i].hdr->st; });
-  const PerImg<const float4*> csboxes = per_img<const float4*>(J, [&](int i) { return (const float4*)w[i].sboxes; });
-  const PerImg<u64*> Lts = per_img<u64*>(J, [&](int i) { return w[i].Lt; });
-  const PerImg<u64*> diags = per_img<u64*>(J, [&](int i) { return w[i].diag; });
-  ScanParams sp;
+  ch.cstates = per_img<const NmsState*>(J, [&](int i) { return (const NmsState*)&w[i].hdr->st; });
+  ch.csboxes = per_img<const float4*>(J, [&](int i) { return (const float4*)w[i].sboxes; });
+  ch.kept = per_img<const float4*>(J, [&](int i) { return (const float4*)w[i].kept_boxes; });
+  ch.Lt = per_img<u64*>(J, [&](int i) { return w[i].Lt; });
+  ch.diag = per_img<u64*>(J, [&](int i) { return w[i].diag; });
+  ch.rinit = per_img<u64*>(J, [&](int i) { return w[i].removed_init; });
+  const PerImg<const uint32_t*> ranked = per_img<const uint32_t*>(J, [&](int i) { return (const uint32_t*)w[i].vals_b; });
+  ScanParams& sp = ch.sp;
   sp.st = per_img<NmsState*>(J, [&](int i) { return &w[i].hdr->st; });
   sp.Lt = per_img<const u64*>(J, [&](int i) { return (const u64*)w[i].Lt; });
   sp.diag_up = per_img<const u64*>(J, [&](int i) { return (const u64*)w[i].diag; });
   sp.removed_init = per_img<const u64*>(J, [&](int i) { return (const u64*)w[i].removed_init; });
-  sp.sboxes = csboxes;
+  sp.sboxes = ch.csboxes;
   sp.sorig = per_img<const float4*>(J, [&](int i) { return (const float4*)w[i].sorig; });
-  sp.sorted_idx = per_img<const uint32_t*>(J, [&](int i) { return (const uint32_t*)w[i].vals_b; });
+  sp.sorted_idx = ranked;
   sp.out_idx = per_img<int32_t*>(J, [&](int i) { return J.img[i].out_idx; });
   sp.out_boxes = per_img<float4*>(J, [&](int i) { return (float4*)J.img[i].out_boxes; });
   sp.kept_boxes = per_img<float4*>(J, [&](int i) { return w[i].kept_boxes; });
@@ -1384,140 +1536,52 @@ static int nms_run(NmsJob& J, hipStream_t st) {
   sp.as_order = per_img<int32_t*>(J, [&](int i) { return K <= ODET_FUSED_ORDER_MAX_ROIS ? J.img[i].assign.order : nullptr; });
   sp.ord_inv_h = 1.0f / (J.prep.hmax + 1.0f); sp.ord_inv_w = 1.0f / (J.prep.wmax + 1.0f);
   sp.n = n; sp.use_init = 0; sp.K = K;
-  const int blind_n = J.blind_chunks < 1 ? 1 : J.blind_chunks;
-  const bool fail_empty = J.fail_empty && J.img[0].out_done != nullptr;
-  sp.fail_empty = (fail_empty && blind_n == 1) ? 1 : 0;         // (set on the LAST sync-free chunk only)
+  auto fail_empty = [&](int c) { return (J.fail_empty && c == P.fail_empty_chunk) ? 1 : 0; };
+  sp.fail_empty = fail_empty(0);
   sp.min_level = J.img[0].assign.min_level; sp.max_level = J.img[0].assign.max_level;
-  {
-    const int cap0 = std::min((int)limit, (n + 63) / 64 * 64);
-    hipLaunchKernelGGL(k_nms_mask, dim3(tri_tiles(cap0), B), dim3(256), 0, st, cstates, csboxes, J.thr, Lts, diags,
-                       lds0 ? 1 : 0);
-    ODET_LAUNCH_CHECK();
-    if (lds0)
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<true>), dim3(1, B), dim3(SCAN_THREADS), SCAN_DYN_LDS, st, sp);
-    else
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, B), dim3(SCAN_THREADS), scan_order_lds(sp), st, sp);
-    ODET_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_nms_mask, dim3(P.tiles0, B), dim3(256), 0, st, ch.cstates, ch.csboxes, J.thr, ch.Lt, ch.diag, P.lds0);
+  ODET_LAUNCH_CHECK();
+  if (P.lds0)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<true>), dim3(1, B), dim3(SCAN_THREADS), SCAN_DYN_LDS, st, sp);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, B), dim3(SCAN_THREADS), scan_order_lds(sp), st, sp);
+  ODET_LAUNCH_CHECK();
+  // 5. further chunks
+  if (P.sync_free) {
+    for (int c = 1; c <= P.sel_chunks && rc == ODET_OK; ++c) rc = ch.launch(1, ranked, fail_empty(c));
+    if (rc != ODET_OK || !P.full_sort) return rc;
+    // with heavily overlapping proposals (a random-init or a real RPN: 5-6 candidates per kept box) every image of a batch
+    // comes here: one sort and one set of launches per chunk for the whole batch
+    OdetSortImage si[ODET_MAX_BATCH];
+    for (int i = 0; i < B; ++i)
+      si[i] = OdetSortImage{w[i].keys_a, w[i].vals_a, w[i].keys_b, w[i].vals_b, w[i].hist, &w[i].hdr->st.done};
+    rc = odet_sort_keys_desc_batch(n, B, si, st);
+    const PerImg<const uint32_t*> order = per_img<const uint32_t*>(J, [&](int i) { return (const uint32_t*)w[i].vals_a; });
+    for (int c = P.sel_chunks + 1; c <= P.further && rc == ODET_OK; ++c) rc = ch.launch(0, order, fail_empty(c));
+    return rc;
   }
-  int blind = J.blind_chunks < 1 ? 1 : J.blind_chunks;
-  // 5. fallback of image i: full order, then chunks of 4096 from wherever chunk 0 stopped.  Every launch is
-  //    guarded by the image's device-side `done` word.  Batches (sync-free by construction) run exactly
-  //    blind - 1 further chunks per image, one image after the other: ~13 launches per image that exit at once
-  //    where chunk 0 has already finished -- the price of never asking the host.
-  auto fallback = [&](int i, bool host_checks, int chunks) -> int {
-    NmsState* state = &w[i].hdr->st;
-    const NmsWorkspace& wi = w[i];
-    auto shift = [&](auto tbl) { auto t = tbl; for (int k = 0; k < ODET_MAX_BATCH; ++k) t.v[k] = tbl.v[i]; return t; };
-    if (host_checks && blind == 1) {
-      NmsState h;
-      ODET_HIP(hipMemcpyAsync(&h, state, sizeof(h), hipMemcpyDeviceToHost, st));
-      ODET_HIP(hipStreamSynchronize(st));
-      if (h.done) return ODET_OK;
-    }
-    uint32_t* sorted = nullptr;
-    int rc = odet_sort_keys_desc(n, wi.keys_a, wi.vals_a, wi.keys_b, wi.vals_b, wi.hist, &state->done, &sorted, st);
-    if (rc != ODET_OK) return rc;
-    ScanParams si = sp;
-    si.st = shift(sp.st); si.Lt = shift(sp.Lt); si.diag_up = shift(sp.diag_up); si.removed_init = shift(sp.removed_init);
-    si.sboxes = shift(sp.sboxes); si.sorig = shift(sp.sorig); si.out_idx = shift(sp.out_idx);
-    si.out_boxes = shift(sp.out_boxes); si.kept_boxes = shift(sp.kept_boxes); si.out_count = shift(sp.out_count);
-    si.out_done = shift(sp.out_done); si.as_rois = shift(sp.as_rois); si.as_level = shift(sp.as_level);
-    si.as_perm = shift(sp.as_perm); si.as_counts = shift(sp.as_counts); si.as_order = shift(sp.as_order);
-    si.use_init = 1;
-    si.fail_empty = 0;
-    for (int k = 0; k < ODET_MAX_BATCH; ++k) si.sorted_idx.v[k] = (const uint32_t*)sorted;
-    const PerImg<const NmsState*> cst = shift(cstates);
-    const PerImg<const float4*> csb = shift(csboxes);
-    const PerImg<u64*> lt = shift(Lts), dg = shift(diags);
-    const int max_chunks = host_checks ? (n + NMS_CHUNK - 1) / NMS_CHUNK + 1 : chunks;
-    PrepParams prep_i = J.prep;                 // image i at entry 0 (grid.y == 1)
-    prep_i.boxes_in = shift(J.prep.boxes_in); prep_i.deltas = shift(J.prep.deltas);
-    PerImg<NmsState*> st_i;
-    PerImg<const float4*> boxes_i, kept_i;
-    PerImg<const uint32_t*> sorted_i;
-    PerImg<float4*> sb_i, so_i;
-    PerImg<u64*> ri_i;
-    for (int k = 0; k < ODET_MAX_BATCH; ++k) {
-      st_i.v[k] = state; boxes_i.v[k] = J.img[i].boxes; sorted_i.v[k] = sorted; sb_i.v[k] = wi.sboxes;
-      so_i.v[k] = wi.sorig; kept_i.v[k] = wi.kept_boxes; ri_i.v[k] = wi.removed_init;
-    }
-    for (int c = 1; c <= max_chunks; ++c) {
-      if (host_checks && c >= blind && !(c == 1 && blind == 1)) {   // (c == 1 && blind == 1: just seen "not done")
-        NmsState h;
-        ODET_HIP(hipMemcpyAsync(&h, state, sizeof(h), hipMemcpyDeviceToHost, st));
-        ODET_HIP(hipStreamSynchronize(st));
-        if (h.done) break;
-      }
-      const int cap = std::min(NMS_CHUNK, (n + 63) / 64 * 64);
-      hipLaunchKernelGGL(k_nms_gather, dim3((cap + 255) / 256, 1), dim3(256), 0, st, st_i, n, cap, 0, prep_i, J.mode,
-                         sorted_i, sb_i, so_i);
-      ODET_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_nms_cross, dim3((cap + 255) / 256, 1), dim3(256), 0, st, cst, csb, kept_i, J.thr, ri_i);
-      ODET_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_nms_mask, dim3(tri_tiles(cap), 1), dim3(256), 0, st, cst, csb, J.thr, lt, dg, 0);
-      ODET_LAUNCH_CHECK();
-      si.fail_empty = (!host_checks && fail_empty && c == max_chunks) ? 1 : 0;
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, 1), dim3(SCAN_THREADS), scan_order_lds(si), st, si);
-      ODET_LAUNCH_CHECK();
-    }
-    return ODET_OK;
-  };
-  const bool sync_free = J.img[0].out_done != nullptr;    // (batches: checked above for every image)
-  if (sync_free) {
-    if (blind == 1) return ODET_OK;              // one chunk: the caller checks *out_done
-    // chunk 1 of every image from the ranked selection, in launches shared by the batch
-    {
-      ScanParams s1 = sp;
-      s1.use_init = 1;                           // (sorted_idx stays the ranked selection)
-      s1.fail_empty = (fail_empty && blind == 2) ? 1 : 0;
-      const int cap = std::min(NMS_CHUNK, (n + 63) / 64 * 64);
-      hipLaunchKernelGGL(k_nms_gather, dim3((cap + 255) / 256, B), dim3(256), 0, st, sp.st, n, cap, 1, J.prep, J.mode,
-                         sp.sorted_idx, sboxes, sorig);
-      ODET_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_nms_cross, dim3((cap + 255) / 256, B), dim3(256), 0, st, cstates, csboxes,
-                         per_img<const float4*>(J, [&](int i) { return (const float4*)w[i].kept_boxes; }), J.thr,
-                         per_img<u64*>(J, [&](int i) { return w[i].removed_init; }));
-      ODET_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_nms_mask, dim3(tri_tiles(cap), B), dim3(256), 0, st, cstates, csboxes, J.thr, Lts, diags, 0);
-      ODET_LAUNCH_CHECK();
-      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, B), dim3(SCAN_THREADS), scan_order_lds(s1), st, s1);
-      ODET_LAUNCH_CHECK();
-    }
-    // chunks 2..: the full order of every image (radix sort of all n keys) and further chunks of NMS_CHUNK candidates,
-    // all in launches shared by the batch (blockIdx.y = image; an image that is done skips every one of them): with
-    // heavily overlapping proposals (a random-init or a real RPN: 5-6 candidates per kept box) every image of a batch
-    // comes here, and one image after the other this was 13 launches = 140 us PER IMAGE.
-    if (blind > 2) {
-      OdetSortImage si_[ODET_MAX_BATCH];
-      for (int i = 0; i < B; ++i)
-        si_[i] = OdetSortImage{w[i].keys_a, w[i].vals_a, w[i].keys_b, w[i].vals_b, w[i].hist, &w[i].hdr->st.done};
-      const int rc = odet_sort_keys_desc_batch(n, B, si_, st);
-      if (rc != ODET_OK) return rc;
-      ScanParams s2 = sp;
-      s2.use_init = 1;
-      s2.sorted_idx = per_img<const uint32_t*>(J, [&](int i) { return (const uint32_t*)w[i].vals_a; });
-      const PerImg<const float4*> kept = per_img<const float4*>(J, [&](int i) { return (const float4*)w[i].kept_boxes; });
-      const PerImg<u64*> rinit = per_img<u64*>(J, [&](int i) { return w[i].removed_init; });
-      const int cap = std::min(NMS_CHUNK, (n + 63) / 64 * 64);
-      for (int c = 2; c < blind; ++c) {
-        hipLaunchKernelGGL(k_nms_gather, dim3((cap + 255) / 256, B), dim3(256), 0, st, sp.st, n, cap, 0, J.prep, J.mode,
-                           s2.sorted_idx, sboxes, sorig);
-        ODET_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_nms_cross, dim3((cap + 255) / 256, B), dim3(256), 0, st, cstates, csboxes, kept, J.thr, rinit);
-        ODET_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_nms_mask, dim3(tri_tiles(cap), B), dim3(256), 0, st, cstates, csboxes, J.thr, Lts, diags, 0);
-        ODET_LAUNCH_CHECK();
-        s2.fail_empty = (fail_empty && c == blind - 1) ? 1 : 0;
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nms_scan<false>), dim3(1, B), dim3(SCAN_THREADS), scan_order_lds(s2), st, s2);
-        ODET_LAUNCH_CHECK();
-      }
-    }
-    return ODET_OK;
+  // exact mode (one image): the host follows the chunks
+  const NmsState* state = &w[0].hdr->st;
+  bool done = false;
+  if (P.blind == 1) {
+    rc = nms_done_on_host(state, st, &done);
+    if (rc != ODET_OK || done) return rc;
   }
-  return fallback(0, true, 0);                   // exact mode (single image): the host follows the chunks
+  uint32_t* sorted = nullptr;
+  rc = odet_sort_keys_desc(n, w[0].keys_a, w[0].vals_a, w[0].keys_b, w[0].vals_b, w[0].hist, &w[0].hdr->st.done, &sorted, st);
+  const PerImg<const uint32_t*> order = per_img<const uint32_t*>(J, [&](int) { return (const uint32_t*)sorted; });
+  for (int c = 1; c <= P.max_chunks && rc == ODET_OK; ++c) {
+    if (c >= P.blind && !(c == 1 && P.blind == 1)) {   // (c == 1 && blind == 1: just seen "not done")
+      rc = nms_done_on_host(state, st, &done);
+      if (rc != ODET_OK || done) break;
+    }
+    rc = ch.launch(0, order, 0);
+  }
+  return rc;
 }
 
 static int nms_trivial(int32_t* out_count, int32_t* out_done, hipStream_t st) {
+  ODET_DIAG_NMS_TRIVIAL();
   ODET_HIP(hipMemsetAsync(out_count, 0, sizeof(int32_t), st));
   if (out_done) {
     ODET_HIP(hipMemsetAsync(out_done, 0, sizeof(int32_t), st));
@@ -1537,6 +1601,12 @@ static void job_init(NmsJob* J, int mode, int n, int K, float thr, int blind_chu
   // the fused proposal stages feed further kernels through out_count: incomplete sync-free results are reported empty
   J->fail_empty = (mode == PREP_FPN || mode == PREP_FRCNN) ? 1 : 0;
   for (int i = 0; i < ODET_MAX_BATCH; ++i) no_assign(&J->img[i].assign);
+}
+
+// box coding and clip of the proposal stages
+static void prep_coding(PrepParams* p, const float* means, const float* stds, int image_h, int image_w) {
+  for (int k = 0; k < 4; ++k) { p->means.v[k] = means[k]; p->stds.v[k] = stds[k]; }
+  p->wmax = (float)(image_w - 1); p->hmax = (float)(image_h - 1);
 }
 
 extern "C" int odet_nms(const float* boxes, const float* scores, int n, int max_output, float iou_threshold,
@@ -1601,14 +1671,37 @@ extern "C" int odet_region_proposal(const float* deltas, const float* anchors, c
   im.boxes_in = (const float4*)anchors;
   im.deltas = deltas;
   im.scores = scores;
-  for (int k = 0; k < 4; ++k) { J.prep.means.v[k] = means[k]; J.prep.stds.v[k] = stds[k]; }
-  J.prep.wmax = (float)(image_w - 1); J.prep.hmax = (float)(image_h - 1);
+  prep_coding(&J.prep, means, stds, image_h, image_w);
   im.out_boxes = out_rois; im.out_count = out_count; im.out_done = out_done;
   return nms_run(J, (hipStream_t)stream);
 }
 
 extern "C" size_t odet_fpn_proposals_workspace_bytes(int n, int max_output) {
   return rp_workspace_bytes(n, max_output);
+}
+
+// One image of a fused proposal stage (odet_fpn_proposals_batch / odet_frcnn_proposals_batch), after the caller's checks of
+// `a`: the trivial result of a stage without anchors, else the workspace and the image's inputs and outputs.  `levels`: the
+// kept RoIs are assigned to pyramid levels min_level .. max_level.
+static int proposal_image(const FpnProposalIO& a, NmsImage* im, const char* who, bool levels, int n, int K, int min_level,
+                          int max_level, hipStream_t st) {
+  if (n == 0) {
+    ODET_DIAG_NMS_TRIVIAL();
+    if (levels) ODET_HIP(hipMemsetAsync(a.out_level_counts, 0, sizeof(int32_t) * (max_level - min_level + 1), st));
+    return nms_trivial(a.out_count, a.out_done, st);
+  }
+  int rc = rp_carve(n, K, a.workspace, a.workspace_bytes, who, im, a.out_idx);
+  if (rc != ODET_OK) return rc;
+  im->logits = (const float2*)a.rpn_logits;
+  im->deltas = a.rpn_deltas;
+  im->out_boxes = a.out_rois; im->out_count = a.out_count; im->out_done = a.out_done;
+  if (levels) {
+    im->assign.rois = (float4*)a.out_sorted_rois; im->assign.level = a.out_level; im->assign.perm = a.out_perm;
+    im->assign.counts = a.out_level_counts;
+    im->assign.order = a.out_order;
+  }
+  im->assign.min_level = min_level; im->assign.max_level = max_level;
+  return ODET_OK;
 }
 
 // shared by odet_fpn_proposals (B = 1) and odet_fpn_step_enqueue_batch (B images in the same launches)
@@ -1643,8 +1736,7 @@ int odet_fpn_proposals_batch(const FpnProposalIO* io, int B, int num_levels, int
   for (int i = 0; i < num_levels * A * 2; ++i) p.wh[i] = wh[i];
   const int n = (int)total;
   J.n = n;
-  for (int k = 0; k < 4; ++k) { J.prep.means.v[k] = means[k]; J.prep.stds.v[k] = stds[k]; }
-  J.prep.wmax = (float)(image_w - 1); J.prep.hmax = (float)(image_h - 1);
+  prep_coding(&J.prep, means, stds, image_h, image_w);
   for (int i = 0; i < B; ++i) {
     const FpnProposalIO& a = io[i];
     ODET_REQUIRE(a.rpn_logits && a.rpn_deltas && a.out_rois && a.out_count, "odet_fpn_proposals: null pointer");
@@ -1656,24 +1748,8 @@ int odet_fpn_proposals_batch(const FpnProposalIO* io, int B, int num_levels, int
         return odet_set_error(ODET_E_LIMIT, "odet_fpn_proposals: max_output %d exceeds %d", max_output,
                               ODET_ASSIGN_MAX_ROIS);
     }
-    if (n == 0) {
-      if (assign) ODET_HIP(hipMemsetAsync(a.out_level_counts, 0, sizeof(int32_t) * (max_level - min_level + 1), st));
-      int rc0 = nms_trivial(a.out_count, a.out_done, st);
-      if (rc0 != ODET_OK) return rc0;
-      continue;
-    }
-    NmsImage& im = J.img[i];
-    int rc = rp_carve(n, max_output, a.workspace, a.workspace_bytes, "odet_fpn_proposals", &im, a.out_idx);
+    int rc = proposal_image(a, &J.img[i], "odet_fpn_proposals", assign, n, max_output, min_level, max_level, st);
     if (rc != ODET_OK) return rc;
-    im.logits = (const float2*)a.rpn_logits;
-    im.deltas = a.rpn_deltas;
-    im.out_boxes = a.out_rois; im.out_count = a.out_count; im.out_done = a.out_done;
-    if (assign) {
-      im.assign.rois = (float4*)a.out_sorted_rois; im.assign.level = a.out_level; im.assign.perm = a.out_perm;
-      im.assign.counts = a.out_level_counts;
-      im.assign.order = a.out_order;
-    }
-    im.assign.min_level = min_level; im.assign.max_level = max_level;
   }
   if (n == 0) return ODET_OK;
   return nms_run(J, st);
@@ -1721,25 +1797,15 @@ int odet_frcnn_proposals_batch(const FpnProposalIO* io, int B, const float* anch
   J.prep.fpn.fw[0] = fw;
   J.prep.fpn.stride[0] = feat_stride;
   for (int i = 0; i < A * 4; ++i) J.prep.fpn.wh[i] = anchor_base[i];
-  for (int k = 0; k < 4; ++k) { J.prep.means.v[k] = means[k]; J.prep.stds.v[k] = stds[k]; }
-  J.prep.wmax = (float)(image_w - 1); J.prep.hmax = (float)(image_h - 1);
+  prep_coding(&J.prep, means, stds, image_h, image_w);
   for (int i = 0; i < B; ++i) {
     const FpnProposalIO& a = io[i];
     ODET_REQUIRE(a.rpn_logits && a.rpn_deltas && a.out_rois && a.out_count, "odet_frcnn_proposals: null pointer");
     ODET_REQUIRE(!a.out_order || max_output <= ODET_FUSED_ORDER_MAX_ROIS,
                  "odet_frcnn_proposals: out_order needs max_output <= %d", ODET_FUSED_ORDER_MAX_ROIS);
-    if (n == 0) {
-      int rc0 = nms_trivial(a.out_count, a.out_done, st);
-      if (rc0 != ODET_OK) return rc0;
-      continue;
-    }
-    NmsImage& im = J.img[i];
-    int rc = rp_carve(n, max_output, a.workspace, a.workspace_bytes, "odet_frcnn_proposals", &im, a.out_idx);
+    int rc = proposal_image(a, &J.img[i], "odet_frcnn_proposals", false, n, max_output, 0, 0, st);
     if (rc != ODET_OK) return rc;
-    im.logits = (const float2*)a.rpn_logits;
-    im.deltas = a.rpn_deltas;
-    im.out_boxes = a.out_rois; im.out_count = a.out_count; im.out_done = a.out_done;
-    im.assign.order = a.out_order;             // (no level assignment: the order is taken over the kept RoIs themselves)
+    J.img[i].assign.order = a.out_order;       // (no level assignment: the order is taken over the kept RoIs themselves)
   }
   if (n == 0) return ODET_OK;
   return nms_run(J, st);

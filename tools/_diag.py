@@ -65,6 +65,10 @@ class DebugPlan(_lib.C.Structure):
 ROI_PLAN_FIELDS = ('B', 'C', 'n', 'P', 'f16', 'pool_mode', 'norm_mode', 'waves', 'slices', 'roi_groups', 'rois_per_xcd',
                    'blocks_per_xcd', 'nblocks', 'xcd_images', 'xcds_per_img', 'grid_x', 'grid_y', 'threads')
 
+NMS_PLAN_FIELDS = ('n', 'K', 'first_chunk', 'B', 'sync_free', 'blind', 'target', 'lds0', 'limit', 'wide', 'sel_target', 'sel_limit',
+                   'prep_grid', 'sel_grid', 'rank_wgs', 'cap0', 'tiles0', 'cap', 'tiles', 'further', 'sel_chunks', 'full_sort',
+                   'fail_empty_chunk', 'max_chunks')
+
 
 class DebugTile(_lib.C.Structure):
     """odet_debug_tile_t"""
@@ -74,6 +78,11 @@ class DebugTile(_lib.C.Structure):
 class DebugRoiPlan(_lib.C.Structure):
     """odet_debug_roi_plan_t"""
     _fields_ = [(n, _lib.C.c_int) for n in ROI_PLAN_FIELDS] + [('count', _lib.C.c_longlong)]
+
+
+class DebugNmsPlan(_lib.C.Structure):
+    """odet_debug_nms_plan_t"""
+    _fields_ = [(n, _lib.C.c_int) for n in NMS_PLAN_FIELDS] + [('count', _lib.C.c_longlong)]
 
 
 FAMILY_F16, FAMILY_F32, FAMILY_SPLIT = 0, 1, 2
@@ -89,6 +98,8 @@ DIAG_SIGNATURES = {
     'odet_debug_plan_only': (_lib._i, [_lib._i]),
     'odet_debug_last_roi_plan': (_lib._i, [_lib.C.POINTER(DebugRoiPlan)]),
     'odet_debug_roi_plan': (_lib._i, [_lib._i] * 7 + [_lib.C.POINTER(DebugRoiPlan)]),
+    'odet_debug_last_nms_plan': (_lib._i, [_lib.C.POINTER(DebugNmsPlan)]),
+    'odet_debug_nms_plan': (_lib._i, [_lib._i] * 6 + [_lib.C.POINTER(DebugNmsPlan)]),
     'odet_debug_cvt_f16': (_lib._i, [_lib._vp, _lib._vp, _lib._vp, _lib.C.c_longlong, _lib._vp]),
     'odet_debug_tg_key_mask': (_lib._i, [_lib.C.c_ulonglong]),
 }
@@ -139,6 +150,22 @@ def roi_plan(B, C, n, P, f16=0, pool_mode=0, norm_mode=0, handle=None):
     p = DebugRoiPlan()
     _lib.check(h.odet_debug_roi_plan(B, C, n, P, int(f16), int(pool_mode), int(norm_mode), _lib.C.byref(p)))
     return {n_: getattr(p, n_) for n_ in ROI_PLAN_FIELDS}
+
+
+def last_nms_plan(handle=None):
+    """the latest NMS job (csrc/nms.hip: nms_run) as a dict of odet_debug_nms_plan_t's fields; 'count' is 0 before the first one"""
+    h = handle or diag_handle()
+    p = DebugNmsPlan()
+    _lib.check(h.odet_debug_last_nms_plan(_lib.C.byref(p)))
+    return dict([(n, getattr(p, n)) for n in NMS_PLAN_FIELDS] + [('count', p.count)])
+
+
+def nms_plan(n, K, first_chunk=0, blind_chunks=1, sync_free=True, B=1, handle=None):
+    """what the NMS driver plans for B images of n candidates each (the planning function alone: no launch, no record)"""
+    h = handle or diag_handle()
+    p = DebugNmsPlan()
+    _lib.check(h.odet_debug_nms_plan(n, K, first_chunk, blind_chunks, int(bool(sync_free)), B, _lib.C.byref(p)))
+    return {n_: getattr(p, n_) for n_ in NMS_PLAN_FIELDS}
 
 
 def tile_table(family, handle=None):
