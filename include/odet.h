@@ -40,8 +40,11 @@ extern "C" {
  * (odet_anchor_target, odet_proposal_target) and the fused training losses with their gradients (odet_rpn_loss,
  * odet_rpn_loss_backward, odet_roi_loss) and odet_preprocess_train (the training input stage) and the training step
  * (odet_opt_step, odet_l2_loss, odet_opt_partials_bytes with the odet_opt_*_t records) and the float32 Dense backward
- * (odet_dense_dgrad_f32, odet_dense_wgrad_f32, odet_dense_grad_workspace_bytes) and the RoI pooling backward
- * (odet_roi_pool_argmax, odet_roi_pool_backward); no existing entry point or struct changed. */
+ * (odet_dense_dgrad_f32, odet_dense_wgrad_f32, odet_dense_grad_workspace_bytes), the 3x3 convolution's weight gradient
+ * (odet_conv3x3_wgrad_f32_levels, odet_conv3x3_wgrad_workspace_bytes, odet_rpn_unpack_pair) and the RoI pooling backward
+ * (odet_roi_pool_argmax, odet_roi_pool_backward); no existing struct or signature changed.  One documented order did: from
+ * 4096 rows on, odet_dense_wgrad_f32 adds db in 256 running sums per column, not 4 (its own comment; below 4096 rows every bit is
+ * as before). */
 #define ODET_VERSION 103
 
 #define ODET_OK 0
@@ -1151,14 +1154,52 @@ int odet_l2_loss(const odet_opt_config_t* cfg, const odet_opt_tensor_t* tensors,
  * contraction (few output tiles, contraction >= 256), 16-byte aligned, contents arbitrary.
  * Order of sums: a function of the shape alone, no atomics -- an element adds its products in ascending k, four per matrix
  * instruction (each product and sum rounded to float32 once); a split launch leaves its parts (equal runs of whole 32-k steps)
- * in the workspace and adds them in ascending order; db adds the rows r = p, p + 4, ... in ascending r for p = 0 .. 3, then the
- * four sums left to right.  Exact on integer data whose partial sums stay below 2^24.  No allocation, no host read
+ * in the workspace and adds them in ascending order; db adds the rows r = p, p + P, ... in ascending r for p = 0 .. P - 1, then
+ * the P sums left to right, P = 4 below 4096 rows and 256 from there on.  Exact on integer data whose partial sums stay below 2^24.  No allocation, no host read
  * (graph-capturable after one eager call per device, which raises the kernels' LDS limit). */
 size_t odet_dense_grad_workspace_bytes(int wgrad, int rows, int cin, int cout);
 int odet_dense_dgrad_f32(const float* dy, const float* w, const float* y_relu, const float* x_relu, float* dx, int rows, int cin,
                          int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream);
 int odet_dense_wgrad_f32(const float* dy, const float* x, const float* y_relu, float* dw, float* db, int rows, int cin, int cout,
                          void* workspace, size_t workspace_bytes, odet_stream_t stream);
+
+/* ---- 3x3 convolution backward, float32 (added within 103) ----------------------------------------------------------
+ * The weight gradient of odet_conv3x3_f32_levels (a 3x3 stride-1 'same' convolution with shared weights over up to
+ * ODET_MAX_LEVELS maps: the RpnHead over the pyramid, base_fpn_model.py:393-434) on the exact-float32 matrix instruction:
+ *   dw[co][ky][kx][ci] = sum over levels, images, rows, columns of dz[b,y,x,co] * x[b, y+ky-1, x+kx-1, ci]  (taps outside the
+ *   map are zero);   db[co] (nullable) = the same sum of dz[b,y,x,co].
+ * A level is {x [batch,H,W,cin], dy [batch,H,W,cout], y_relu (nullable, the forward output, as dy), H, W}: the forward's own
+ * contiguous NHWC float32 tensors; dw [cout][3][3][cin] is its weight layout.  dz = y_relu > 0 ? dy : 0 (a select, strict '>')
+ * formed while staging, dy itself for a level without y_relu.  Nothing is transposed, copied or written but dw, db and the
+ * workspace.  (The input gradient needs no entry point: it is the forward convolution of dz with the flipped, transposed
+ * weight w'[ci][ky][kx][co] = w[co][2-ky][2-kx][ci].)
+ * Rules (ODET_E_INVALID before any GPU work): the forward's -- 1..ODET_MAX_LEVELS levels, batch >= 1, H, W >= 1,
+ * cin % 32 == 0, cout % 64 == 0, fewer than 2^31 - 2^16 pixels in all; pointers 16-byte aligned (db: 4).  ODET_E_WORKSPACE: a
+ * workspace smaller than odet_conv3x3_wgrad_workspace_bytes (same levels' H and W; their pointers are not read) --
+ * parts * cout * 9 * cin * 4 bytes when the launch cuts its contraction into parts > 1, else 0; 16-byte aligned, contents
+ * arbitrary.
+ * Order of sums: a function of (num_levels, every H and W, batch, cin, cout) alone, no atomics, every element written once.
+ * The pixels of all levels are numbered through (levels in the order given; image, row, column); an element adds its products
+ * in ascending pixel order, four per matrix instruction, inside each of `parts` equal runs of whole 32-pixel steps (as many as
+ * bring the launch to 512 workgroups, at most 16, each at least 64 pixels, none below 256 pixels), and a second launch adds the
+ * parts in ascending order.  db adds the pixels r = p, p + P, ... in ascending r for p = 0 .. P - 1, then the P sums left to
+ * right, P = 4 below 4096 pixels in all and 256 from there on.  Exact on integer data whose partial sums stay below 2^24.  No allocation, no host read (graph-capturable after one
+ * eager call per device, which raises the kernels' LDS limit). */
+typedef struct {
+  const void* x; const void* dy; const void* y_relu;
+  int32_t H, W;
+} odet_conv_grad_level_t;
+size_t odet_conv3x3_wgrad_workspace_bytes(const odet_conv_grad_level_t* levels, int num_levels, int batch, int cin, int cout);
+int odet_conv3x3_wgrad_f32_levels(const odet_conv_grad_level_t* levels, int num_levels, float* dw, float* db, int batch, int cin,
+                                  int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream);
+/* The inverse of odet_rpn_pack_pair's index map, for the backward pass of the RpnHead's two 1x1 convolutions run as one
+ * contraction: from d_scores [B,N,2] and d_deltas [B,N,4] (float32; image strides and the level's offsets in VALUES, as in
+ * odet_rpn_pack_pair) the level's gradient level_grad [B * pixels, channels] of the PADDED pair output -- columns 0 .. 2A - 1
+ * the score channels, 2A .. 6A - 1 the delta channels, 6A .. channels - 1 zeros (channels >= 6A).  Every element of level_grad
+ * is written once; packing it again with a zero bias returns the inputs' slices. */
+int odet_rpn_unpack_pair(const float* d_scores, long long scores_image_stride, long long scores_offset, const float* d_deltas,
+                         long long deltas_image_stride, long long deltas_offset, long long pixels, int A, int B, int channels,
+                         float* level_grad, odet_stream_t stream);
 
 /* ---- RoI pooling backward, float32 (added within 103) --------------------------------------------------------------
  * The gradient of odet_roi_pool with respect to the float32 feature maps (TF r1.13 CropAndResizeGradImage and the max-pool

@@ -28,6 +28,11 @@ class OdetConvLevel(C.Structure):
     _fields_ = [('x', C.c_void_p), ('y', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32)]
 
 
+class OdetConvGradLevel(C.Structure):
+    """odet_conv_grad_level_t"""
+    _fields_ = [('x', C.c_void_p), ('dy', C.c_void_p), ('y_relu', C.c_void_p), ('H', C.c_int32), ('W', C.c_int32)]
+
+
 MAX_LEVELS = 8
 MAX_ANCHORS_PER_CELL = 32
 
@@ -225,6 +230,10 @@ SIGNATURES = {
     'odet_dense_grad_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'odet_dense_dgrad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     'odet_dense_wgrad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    'odet_conv3x3_wgrad_workspace_bytes': (_sz, [_vp, _i, _i, _i, _i]),
+    'odet_conv3x3_wgrad_f32_levels': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    'odet_rpn_unpack_pair': (_i, [_vp, C.c_longlong, C.c_longlong, _vp, C.c_longlong, C.c_longlong, C.c_longlong, _i, _i, _i, _vp,
+                                  _vp]),
     'odet_roi_pool_argmax': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     'odet_roi_pool_backward': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
 }

@@ -12,7 +12,8 @@
 //   wgrad    x  [rows][cin]           dz [rows][cout]  (K-major)     dw [cout][cin]
 //   dgrad    w  [cout][cin]           dz [rows][cout]  (N-major)     dx [rows][cin]
 //
-// Tiling.  A workgroup of 4 waves (2 along m x 2 along n) owns a (32 WT)^2 tile, WT = 4 (128 x 128) or 2 (64 x 64); a wave
+// Tiling (the routine itself is grad_gemm.h's dg_tile, which conv_grad.hip runs too; this file supplies the operand fetch).  A
+// workgroup of 4 waves (2 along m x 2 along n) owns a (32 WT)^2 tile, WT = 4 (128 x 128) or 2 (64 x 64); a wave
 // holds WT x WT MFMA tiles.  A is the MFMA's first operand, so a lane ends with four CONSECUTIVE m of one output row n: the
 // four lanes of a row store 64 contiguous bytes per instruction and every element of C is written once.  A K-step is 32: the
 // tile's rows go global -> registers (16-byte loads, the mask applied there) -> LDS while the previous step's MFMAs run (two
@@ -24,18 +25,14 @@
 // Order of sums (a function of the shape alone; no atomics): an element adds its products in ascending k, four per matrix
 // instruction.  A launch with few tiles and a long contraction is SPLIT along k into `ksplit` equal parts of whole K-steps
 // (dg_plan: a rule on (M, N, K) only); each part leaves its float32 partial tile in the caller's workspace and a second
-// launch adds the parts in the order 0 .. ksplit - 1 and applies the epilogue mask.  db: a column's rows r = p, p + 4, ... are
-// added in ascending r for p = 0 .. 3, then the four sums left to right.
+// launch adds the parts in the order 0 .. ksplit - 1 and applies the epilogue mask.  db: a column's rows r = p, p + P, ... are
+// added in ascending r for p = 0 .. P - 1, then the P sums left to right; P = 4, or 256 from 4096 rows on (a rule on the row
+// count alone: a Dense layer run over a pyramid's pixels).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
-#include "conv_f32_common.h"
-
-#define DG_BK 32                  // k per K-step
-#define DG_PADK 16                // K-major LDS rows: T + 16 floats
-#define DG_STRN (DG_BK + 4)       // N-major LDS rows: 36 floats
-#define DG_LDS_MAX (80 * 1024)
+#include "grad_gemm.h"
 
 struct DenseGradParams {
   const float* a;                 // [K][M]
@@ -46,16 +43,12 @@ struct DenseGradParams {
   int M, N, K, kper;              // part z of a launch takes k in [z * kper, min(K, (z + 1) * kper)); kper % DG_BK == 0
 };
 
+// the tile routine of grad_gemm.h on operands that are plain row-major matrices
 template <int WT, bool BKMAJOR>
 __global__ void __launch_bounds__(256) k_dense_grad_f32(DenseGradParams p) {
-  constexpr int T = 32 * WT;                              // tile edge (m and n)
-  constexpr int STRK = T + DG_PADK;
-  constexpr int A_ST = DG_BK * STRK;                      // floats per stage and operand (N-major: T * 36 <= A_ST for T <= 128)
-  constexpr int PER = T / 32;                             // 16-byte loads per thread, operand and K-step
-  extern __shared__ __align__(16) float dg_lds[];
+  constexpr int T = 32 * WT;
+  constexpr int PER = T / 32;
   const int tid = threadIdx.x;
-  const int lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
-  const int wv = tid >> 6, wm = wv & 1, wn = wv >> 1;
   const int tiles_m = (p.M + T - 1) / T;
   const int m0 = (int)(blockIdx.x % (unsigned)tiles_m) * T, n0 = (int)(blockIdx.x / (unsigned)tiles_m) * T;
   const int kbeg = (int)blockIdx.z * p.kper;
@@ -63,8 +56,7 @@ __global__ void __launch_bounds__(256) k_dense_grad_f32(DenseGradParams p) {
   const int M = p.M, N = p.N;
   const long long ldb = BKMAJOR ? N : p.K;
 
-  c3f4 ra[PER], rb[PER];
-  auto fetch = [&](int k0) {
+  auto fetch = [&](int k0, c3f4 (&ra)[PER], c3f4 (&rb)[PER]) {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
       const int idx = tid + 256 * i;
@@ -93,72 +85,7 @@ __global__ void __launch_bounds__(256) k_dense_grad_f32(DenseGradParams p) {
       }
     }
   };
-  auto stash = [&](int stage) {
-    float* sa = dg_lds + stage * 2 * A_ST;
-    float* sb = sa + A_ST;
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int idx = tid + 256 * i;
-      *reinterpret_cast<c3f4*>(sa + (idx / (T / 4)) * STRK + (idx % (T / 4)) * 4) = ra[i];
-      if constexpr (BKMAJOR) *reinterpret_cast<c3f4*>(sb + (idx / (T / 4)) * STRK + (idx % (T / 4)) * 4) = rb[i];
-      else *reinterpret_cast<c3f4*>(sb + (idx / (DG_BK / 4)) * DG_STRN + (idx % (DG_BK / 4)) * 4) = rb[i];
-    }
-  };
-
-  c3f4 acc[WT][WT];
-#pragma unroll
-  for (int mt = 0; mt < WT; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < WT; ++nt) acc[mt][nt] = (c3f4){0.0f, 0.0f, 0.0f, 0.0f};
-
-  const int aoff = wm * (T / 2) + l15;
-  const int boff = BKMAJOR ? wn * (T / 2) + l15 : (wn * (T / 2) + l15) * DG_STRN;
-  const int steps = (kend - kbeg + DG_BK - 1) / DG_BK;    // (>= 1: the host gives every part at least one k)
-  fetch(kbeg);
-  stash(0);
-  __syncthreads();
-  for (int s = 0; s < steps; ++s) {
-    const int stage = s & 1;
-    if (s + 1 < steps) fetch(kbeg + (s + 1) * DG_BK);
-    const float* sa = dg_lds + stage * 2 * A_ST;
-    const float* sb = sa + A_ST;
-#pragma unroll
-    for (int kk = 0; kk < DG_BK / 4; ++kk) {
-      const int k = kk * 4 + lq;                          // lane (l15, lq) feeds k = lq of the instruction's four
-      float af[WT], bf[WT];
-#pragma unroll
-      for (int mt = 0; mt < WT; ++mt) af[mt] = sa[k * STRK + aoff + mt * 16];
-#pragma unroll
-      for (int nt = 0; nt < WT; ++nt) bf[nt] = BKMAJOR ? sb[k * STRK + boff + nt * 16] : sb[boff + nt * 16 * DG_STRN + k];
-#pragma unroll
-      for (int mt = 0; mt < WT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < WT; ++nt)
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[mt], bf[nt], acc[mt][nt], 0, 0, 0);
-    }
-    if (s + 1 < steps) stash(stage ^ 1);                  // (the stage read in step s - 1: everyone passed the barrier since)
-    __syncthreads();
-  }
-
-  // lane: output row n = .. + l15, columns m = .. + 4 lq .. + 3 of every MFMA tile
-  float* out = p.out + (long long)blockIdx.z * N * M;
-#pragma unroll
-  for (int nt = 0; nt < WT; ++nt) {
-    const int n = n0 + wn * (T / 2) + nt * 16 + l15;
-    if (n >= N) continue;
-#pragma unroll
-    for (int mt = 0; mt < WT; ++mt) {
-      const int m = m0 + wm * (T / 2) + mt * 16 + lq * 4;
-      if (m >= M) continue;
-      c3f4 v = acc[mt][nt];
-      if (p.omask) {
-        const c3f4 y = *reinterpret_cast<const c3f4*>(p.omask + (long long)n * M + m);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = y[j] > 0.0f ? v[j] : 0.0f;
-      }
-      *reinterpret_cast<c3f4*>(out + (long long)n * M + m) = v;
-    }
-  }
+  dg_tile<WT, BKMAJOR>(fetch, kbeg, kend, m0, n0, M, N, M, p.omask, p.out + (long long)blockIdx.z * N * M);
 }
 
 // the parts of a split launch, added in the order 0 .. ksplit - 1, and the epilogue mask
@@ -180,23 +107,106 @@ __global__ void __launch_bounds__(256) k_dense_grad_reduce(const float* __restri
   }
 }
 
-// db[c] = sum over the rows of dz[:, c]: thread (c, p) adds rows p, p + 4, ... in ascending order, then p = 0 .. 3 left to right
-__global__ void __launch_bounds__(256) k_dense_bias_grad(const float* __restrict__ dy, const float* __restrict__ y, float* __restrict__ db,
-                                                         int rows, int cout) {
+// db[c] = sum over the rows of dz[:, c], the rows of the listed matrices numbered through: thread (c, p) adds rows p, p + 4, ...
+// in ascending order, then p = 0 .. 3 left to right
+__global__ void __launch_bounds__(256) k_dense_bias_grad(DgBiasRows q, float* __restrict__ db, int cout) {
   __shared__ float part[4][64];
   const int c = (int)blockIdx.x * 64 + (threadIdx.x & 63), ph = threadIdx.x >> 6;
   float s = 0.0f;
   if (c < cout) {
-    for (int r = ph; r < rows; r += 4) {
-      const long long off = (long long)r * cout + c;
-      float v = dy[off];
-      if (y) v = y[off] > 0.0f ? v : 0.0f;
-      s = s + v;
+    int first = ph;                                       // this thread's first row of the matrix at hand
+#pragma unroll
+    for (int l = 0; l < ODET_MAX_LEVELS; ++l) {
+      if (l >= q.count) break;
+      const float* __restrict__ dy = q.dy[l];
+      const float* __restrict__ y = q.y[l];
+      const long long rows = q.rows[l];
+      for (long long r = first; r < rows; r += 4) {
+        const long long off = r * cout + c;
+        float v = dy[off];
+        if (y) v = y[off] > 0.0f ? v : 0.0f;
+        s = s + v;
+      }
+      first = (int)((first + 4 - rows % 4) % 4);
     }
   }
   part[ph][threadIdx.x & 63] = s;
   __syncthreads();
   if (ph == 0 && c < cout) db[c] = ((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x];
+}
+
+int dg_reduce_parts(const float* parts, int nparts, long long total4, const float* omask, float* out, hipStream_t st) {
+  const unsigned blocks = (unsigned)std::min<long long>((total4 + 255) / 256, 256 * 16);
+  hipLaunchKernelGGL(k_dense_grad_reduce, dim3(blocks), dim3(256), 0, st, parts, nparts, total4, omask, out);
+  ODET_LAUNCH_CHECK();
+  return ODET_OK;
+}
+
+// The same sums for a LONG list of rows (a layer run over pixels: the RpnHead's 89 023 at 800 x 1333, where four running sums
+// per channel take milliseconds): 256 running sums per channel.  A workgroup owns 16 channels; thread (phase p, quad) adds
+// rows r = p, p + 256, ... of the list in ascending r for its four channels (eight loads in flight, the adds in order), then
+// one thread per quad adds the phases p = 0 .. 255 left to right.  cout % 16 == 0
+__global__ void __launch_bounds__(1024) k_dense_bias_grad_long(DgBiasRows q, float* __restrict__ db, int cout) {
+  __shared__ c3f4 part[DG_BIAS_LONG_PHASES][4];
+  const int cq = threadIdx.x & 3, ph = threadIdx.x >> 2;
+  const int c = (int)blockIdx.x * 16 + cq * 4;
+  c3f4 s = (c3f4){0.0f, 0.0f, 0.0f, 0.0f};
+  long long first = ph;                                   // this thread's first row of the matrix at hand
+#pragma unroll
+  for (int l = 0; l < ODET_MAX_LEVELS; ++l) {
+    if (l >= q.count) break;
+    const float* __restrict__ dy = q.dy[l] + c;
+    const float* __restrict__ y = q.y[l] ? q.y[l] + c : nullptr;
+    const long long rows = q.rows[l];
+    auto load = [&](long long r) {
+      c3f4 v = *reinterpret_cast<const c3f4*>(dy + r * cout);
+      if (y) {
+        const c3f4 yv = *reinterpret_cast<const c3f4*>(y + r * cout);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = yv[j] > 0.0f ? v[j] : 0.0f;
+      }
+      return v;
+    };
+    long long r = first;
+    for (; r + 7 * DG_BIAS_LONG_PHASES < rows; r += 8 * DG_BIAS_LONG_PHASES) {
+      c3f4 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = load(r + u * DG_BIAS_LONG_PHASES);
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s[j] = s[j] + v[u][j];
+    }
+    for (; r < rows; r += DG_BIAS_LONG_PHASES) {
+      const c3f4 v = load(r);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[j] = s[j] + v[j];
+    }
+    first = (first + DG_BIAS_LONG_PHASES - rows % DG_BIAS_LONG_PHASES) % DG_BIAS_LONG_PHASES;
+  }
+  part[ph][cq] = s;
+  __syncthreads();
+  if (ph == 0) {
+    c3f4 t = part[0][cq];
+    for (int p = 1; p < DG_BIAS_LONG_PHASES; ++p) {
+      const c3f4 v = part[p][cq];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) t[j] = t[j] + v[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) db[c + j] = t[j];        // (db is only 4-byte aligned)
+  }
+}
+
+int dg_bias_grad(const DgBiasRows& rows, float* db, int cout, hipStream_t st) {
+  long long total = 0;
+  for (int l = 0; l < rows.count; ++l) total += rows.rows[l];
+  if (total >= DG_BIAS_LONG_ROWS && cout % 16 == 0)
+    hipLaunchKernelGGL(k_dense_bias_grad_long, dim3((unsigned)(cout / 16)), dim3(1024), 0, st, rows, db, cout);
+  else
+    hipLaunchKernelGGL(k_dense_bias_grad, dim3((unsigned)((cout + 63) / 64)), dim3(256), 0, st, rows, db, cout);
+  ODET_LAUNCH_CHECK();
+  return ODET_OK;
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
@@ -255,17 +265,13 @@ static int dg_launch(const char* who, const float* a, const float* b, const floa
   DenseGradParams p;
   p.a = a; p.b = b; p.bmask = bmask; p.omask = need ? nullptr : omask; p.out = need ? (float*)workspace : out;
   p.M = M; p.N = N; p.K = K; p.kper = pl.kper;
-  const int T = 32 * pl.wt;
-  const unsigned lds = (unsigned)(2 * 2 * DG_BK * (T + DG_PADK) * sizeof(float));
+  const unsigned lds = dg_lds_bytes(pl.wt);
   const dim3 grid((unsigned)pl.tiles, 1, (unsigned)pl.ksplit);
   if (pl.wt == 4) hipLaunchKernelGGL((k_dense_grad_f32<4, BKMAJOR>), grid, dim3(256), lds, st, p);
   else hipLaunchKernelGGL((k_dense_grad_f32<2, BKMAJOR>), grid, dim3(256), lds, st, p);
   ODET_LAUNCH_CHECK();
   if (need) {
-    const long long total4 = (long long)N * M / 4;
-    const unsigned blocks = (unsigned)std::min<long long>((total4 + 255) / 256, 256 * 16);
-    hipLaunchKernelGGL(k_dense_grad_reduce, dim3(blocks), dim3(256), 0, st, (const float*)workspace, pl.ksplit, total4, omask, out);
-    ODET_LAUNCH_CHECK();
+    return dg_reduce_parts((const float*)workspace, pl.ksplit, (long long)N * M / 4, omask, out, st);
   }
   return ODET_OK;
 }
@@ -292,8 +298,9 @@ extern "C" int odet_dense_wgrad_f32(const float* dy, const float* x, const float
   const int rl = dg_launch<true>(who, x, dy, y_relu, nullptr, dw, cin, cout, rows, workspace, workspace_bytes, (hipStream_t)stream);
   if (rl != ODET_OK) return rl;
   if (db) {
-    hipLaunchKernelGGL(k_dense_bias_grad, dim3((unsigned)(cout / 64)), dim3(256), 0, (hipStream_t)stream, dy, y_relu, db, rows, cout);
-    ODET_LAUNCH_CHECK();
+    DgBiasRows q = {};
+    q.dy[0] = dy; q.y[0] = y_relu; q.rows[0] = rows; q.count = 1;
+    return dg_bias_grad(q, db, cout, (hipStream_t)stream);
   }
   return ODET_OK;
 }

@@ -291,3 +291,47 @@ extern "C" int odet_rpn_pack_pair(const void* level_out, const void* bias, long 
   ODET_LAUNCH_CHECK();
   return ODET_OK;
 }
+
+// The inverse index map, for the head's backward pass: the level's [B * pixels, chp] gradient of the PADDED pair output (2A
+// score columns, 4A delta columns, zeros up to chp) gathered from d scores [B, N, 2] and d deltas [B, N, 4].  One element per
+// thread step, every element written once.
+struct RpnUnpackPairParams {
+  const float* scores; const float* deltas; float* out;
+  long long pixels, scores_image_stride, scores_offset, deltas_image_stride, deltas_offset, total;
+  int A, chp;
+};
+
+__global__ void __launch_bounds__(256) k_rpn_unpack_pair(RpnUnpackPairParams p) {
+  const int sc = 2 * p.A, ch = 6 * p.A;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < p.total; i += (long long)gridDim.x * 256) {
+    const long long row = i / p.chp;
+    const int c = (int)(i - row * p.chp);
+    const long long b = row / p.pixels, px = row - b * p.pixels;
+    float v = 0.0f;
+    if (c < sc) v = p.scores[b * p.scores_image_stride + p.scores_offset + px * sc + c];
+    else if (c < ch) v = p.deltas[b * p.deltas_image_stride + p.deltas_offset + px * (ch - sc) + (c - sc)];
+    p.out[i] = v;
+  }
+}
+
+extern "C" int odet_rpn_unpack_pair(const float* d_scores, long long scores_image_stride, long long scores_offset,
+                                    const float* d_deltas, long long deltas_image_stride, long long deltas_offset, long long pixels,
+                                    int A, int B, int channels, float* level_grad, odet_stream_t stream) {
+  ODET_REQUIRE(d_scores && d_deltas && level_grad, "odet_rpn_unpack_pair: null pointer");
+  ODET_REQUIRE(pixels >= 0 && A > 0 && B >= 0 && scores_offset >= 0 && deltas_offset >= 0 && channels >= 6 * A,
+               "odet_rpn_unpack_pair: bad sizes");
+  ODET_REQUIRE(scores_offset + pixels * 2 * A <= scores_image_stride && deltas_offset + pixels * 4 * A <= deltas_image_stride,
+               "odet_rpn_unpack_pair: level does not fit the concatenated arrays");
+  RpnUnpackPairParams p;
+  p.scores = d_scores; p.deltas = d_deltas; p.out = level_grad;
+  p.pixels = pixels;
+  p.scores_image_stride = scores_image_stride; p.scores_offset = scores_offset;
+  p.deltas_image_stride = deltas_image_stride; p.deltas_offset = deltas_offset;
+  p.total = (long long)B * pixels * channels;
+  p.A = A; p.chp = channels;
+  if (p.total == 0) return ODET_OK;
+  const int grid = (int)std::min<long long>((p.total + 255) / 256, 256 * 16);
+  hipLaunchKernelGGL(k_rpn_unpack_pair, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
+  ODET_LAUNCH_CHECK();
+  return ODET_OK;
+}

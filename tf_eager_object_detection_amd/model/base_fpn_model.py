@@ -13,7 +13,9 @@ the GPU; every detection op is a HIP kernel behind the C ABI.  Training (`traini
 forward pass (:232-264) on the target layers of this package; the dense kernels are inference kernels (no backward), except
 the FPN RoI head with `train_roi_head=True` (float32, exact form): its four Dense layers then run ops.dense_trainable and the two
 RoI losses carry a graph into fc1, fc2, score and bbox -- and, when the maps handed to the pooling require a gradient, through
-ops.roi_pool_trainable into those maps (the models' own maps never do: the neck and the extractor have no backward yet)."""
+ops.roi_pool_trainable into those maps (the models' own maps never do: the neck and the extractor have no backward yet).
+Likewise the RpnHead with `train_rpn_head=True`: its three convolutions run fpn_detector's rpn_trainable over all levels at once and
+the two RPN losses carry a graph into rpn_conv, rpn_score and rpn_bbox."""
 import torch
 
 from .. import ops
@@ -86,11 +88,13 @@ class BaseFPN(torch.nn.Module):
                  roi_training_total_num_samples=128, roi_training_max_pos_samples=32,
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0., training_targets='torch',
-                 training_losses='torch', train_roi_head=False):
+                 training_losses='torch', train_roi_head=False, train_rpn_head=False):
         super().__init__()
         self._training_losses = check_training_losses(training_losses, training_targets)
         # True: the training branches run the RoI head with a backward pass (the two RoI losses carry a graph into its layers)
         self._train_roi_head = bool(train_roi_head)
+        # True: the training branches run the RpnHead with a backward pass (the two RPN losses carry a graph into its layers)
+        self._train_rpn_head = bool(train_rpn_head)
         self.roi_feature_size = roi_feature_size
         self.num_classes = num_classes
         self.weight_decay = weight_decay
@@ -190,10 +194,16 @@ class BaseFPN(torch.nn.Module):
         with torch.no_grad():
             c_list = self._extractor(image, training=training)
             p_list = self._neck(c_list, training=training)
-            all_fpn_scores, all_fpn_bbox_pred = self._get_fpn_head_results(p_list)
+            if not (training and self._train_rpn_head):
+                all_fpn_scores, all_fpn_bbox_pred = self._get_fpn_head_results(p_list)
+        if training and self._train_rpn_head:
+            # the head of all levels at once, OUTSIDE no_grad: the RPN losses below see these tensors and carry their graph;
+            # anchors, softmax and proposals see detached values
+            all_fpn_scores, all_fpn_bbox_pred = self._get_trainable_fpn_head_results(p_list)
+        with torch.no_grad():
             all_anchors = self._get_anchors(image_shape)
-            cur_scores = self._fg_scores(all_fpn_scores)
-            rois = self._rpn_proposal((all_fpn_bbox_pred, all_anchors, cur_scores, image_shape), training=training)
+            cur_scores = self._fg_scores(all_fpn_scores.detach())
+            rois = self._rpn_proposal((all_fpn_bbox_pred.detach(), all_anchors, cur_scores, image_shape), training=training)
         if training and self._training_losses == 'hip':
             return self._fused_losses(all_fpn_scores, all_fpn_bbox_pred, all_anchors, rois, gt_bboxes, gt_labels, p_list,
                                       image_shape, training)
@@ -264,6 +274,10 @@ class BaseFPN(torch.nn.Module):
 
     def _get_trainable_roi_head(self):
         raise NotImplementedError('train_roi_head=True needs a dense part with a trainable RoI head')
+
+    def _get_trainable_fpn_head_results(self, p_list):
+        """_get_fpn_head_results with a graph into the RpnHead's layers: ([N,2], [N,4]) of all levels, bit-equal to it"""
+        raise NotImplementedError('train_rpn_head=True needs a dense part with a trainable RPN head')
 
     def _get_rpn_loss(self, rpn_score, rpn_bbox_txtytwth, anchor_target_labels, anchor_target_bboxes_txtytwth,
                       anchor_target_in_weights, anchor_target_out_weights):
@@ -365,12 +379,15 @@ class ResnetV1Fpn(BaseFPN):
                  roi_training_total_num_samples=256, roi_training_max_pos_samples=64,
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3, dtype=torch.float32, device='cuda',
-                 f32_form='exact', training_targets='torch', training_losses='torch', train_roi_head=False):
+                 f32_form='exact', training_targets='torch', training_losses='torch', train_roi_head=False, train_rpn_head=False):
         from .fpn_detector import ResNetFpnDetector, check_caller_f32_form
         check_caller_f32_form(f32_form)
         if train_roi_head and (dtype != torch.float32 or f32_form != 'exact'):
             raise ValueError("ResnetV1Fpn: train_roi_head=True needs dtype=torch.float32 and f32_form='exact' (the Dense backward "
                              "has no float16 or split-precision form), got %s, %r" % (dtype, f32_form))
+        if train_rpn_head and (dtype != torch.float32 or f32_form != 'exact'):
+            raise ValueError("ResnetV1Fpn: train_rpn_head=True needs dtype=torch.float32 and f32_form='exact' (the convolution "
+                             "backward has no float16 or split-precision form), got %s, %r" % (dtype, f32_form))
         if top_down_dims != 256 or tuple(roi_feature_size) != (roi_pool_size, roi_pool_size, top_down_dims):
             raise ValueError('ResnetV1Fpn: the dense kernels are built for 256 top-down channels and %dx%dx256 RoI features'
                              % (roi_pool_size, roi_pool_size))
@@ -405,7 +422,8 @@ class ResnetV1Fpn(BaseFPN):
             prediction_max_objects_per_image=prediction_max_objects_per_image,
             prediction_max_objects_per_class=prediction_max_objects_per_class,
             prediction_nms_iou_threshold=prediction_nms_iou_threshold, prediction_score_threshold=prediction_score_threshold,
-            training_targets=training_targets, training_losses=training_losses, train_roi_head=train_roi_head)
+            training_targets=training_targets, training_losses=training_losses, train_roi_head=train_roi_head,
+            train_rpn_head=train_rpn_head)
         self.dense = dense
 
     def _get_roi_head(self):
@@ -413,6 +431,10 @@ class ResnetV1Fpn(BaseFPN):
 
     def _get_trainable_roi_head(self):
         return self._dense_ref.roi_head_trainable
+
+    def _get_trainable_fpn_head_results(self, p_list):
+        scores, deltas = self._dense_ref.rpn_trainable(list(p_list))
+        return scores.reshape(-1, 2), deltas.reshape(-1, 4)
 
     def _get_extractor(self):
         return _Part(self._dense_ref.extractor)

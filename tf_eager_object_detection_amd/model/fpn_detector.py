@@ -424,6 +424,13 @@ class ResNetFpnDetector(Detector):
             off += int(h.shape[1]) * int(h.shape[2]) * self.A
         return scores, deltas
 
+    @_in_f32_form
+    def rpn_trainable(self, p_list):
+        """rpn with a backward pass into rpn_conv, rpn_score and rpn_bbox (float32, f32_form 'exact'; model/rpn_trainable.py):
+        outputs bit-equal to rpn()'s, and a gradient into those maps of p_list that require one"""
+        from .rpn_trainable import rpn_trainable
+        return rpn_trainable(self, p_list)
+
     def head_activation(self, roi_features):
         """flatten(7,7,256) -> fc 1024 -> fc 1024 (resnet_fpn.py:292-326): the input of the score / bbox layers; the Dense
         layers on the pointwise GEMM kernel with bias + ReLU in its epilogue"""

@@ -1010,6 +1010,184 @@ def dense_trainable(x, weight, bias, relu=False):
     return _DenseTrainable.apply(x if x.is_contiguous() else x.contiguous(), weight, bias, bool(relu))
 
 
+def _conv_grad_maps(who, named_lists):
+    """the checks the 3x3 convolution's backward fronts share (the style of _dense_grad_args): float32 only, the exact form only,
+    contiguous NHWC GPU tensors of one batch size, 1..MAX_LEVELS of them, the lists equally long and shaped level by level ->
+    (levels, batch, the named tensors for _conv_grad_on_gpu, which the caller runs after its shape rules)"""
+    lists = [(name, ts) for name, ts in named_lists if ts is not None]
+    n = len(lists[0][1])
+    if not 1 <= n <= MAX_LEVELS or any(len(ts) != n for _, ts in lists):
+        raise ValueError('%s: between 1 and %d maps expected, as many in every list' % (who, MAX_LEVELS))
+    every = [('%s[%d]' % (name, i), t) for name, ts in lists for i, t in enumerate(ts) if t is not None]
+    for name, t in every:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError('%s: %s must be a float32 tensor (the convolution backward has no float16 form), got %s'
+                             % (who, name, getattr(t, 'dtype', type(t).__name__)))
+    if current_f32_form() != 'exact':
+        raise ValueError("%s: the convolution backward runs only under f32_form 'exact' (no split-precision backward), not %r"
+                         % (who, current_f32_form()))
+    for name, t in every:
+        if t.dim() != 4 or not t.is_contiguous():
+            raise ValueError('%s: %s must be a contiguous NHWC tensor [B,H,W,C]' % (who, name))
+    B = int(lists[0][1][0].shape[0])
+    for i in range(n):
+        hw = tuple(lists[0][1][i].shape[:3])
+        for name, ts in lists:
+            chans = next(int(t.shape[3]) for t in ts if t is not None)
+            if ts[i] is not None and (tuple(ts[i].shape[:3]) != hw or int(ts[i].shape[3]) != chans or hw[0] != B):
+                raise ValueError('%s: %s[%d] %s does not go with %s[%d] %s (one batch size, one channel count per list)'
+                                 % (who, name, i, tuple(ts[i].shape), lists[0][0], i, tuple(lists[0][1][i].shape)))
+    return n, B, every
+
+
+def _conv_grad_on_gpu(who, every):
+    for name, t in every:
+        if not t.is_cuda:
+            raise ValueError('%s: %s must be a GPU tensor' % (who, name))
+
+
+def conv3x3_wgrad_f32_levels(xs, dys, y_relus=None, with_bias=True, out=None):
+    """The parameter gradients of conv3x3_f32_levels (odet_conv3x3_wgrad_f32_levels): xs [B,H,W,cin] (the layer's inputs) and dys
+    [B,H,W,cout] per level, contiguous NHWC float32 -> (dw [cout,3,3,cin], the forward's weight layout, summed over the levels;
+    db [cout], or None without with_bias).  dz = dy where y_relu > 0 else 0 for the levels whose y_relus entry (the forward
+    output) is given.  cin % 32 == 0, cout % 64 == 0."""
+    who = 'conv3x3_wgrad_f32_levels'
+    if y_relus is not None and all(y is None for y in y_relus):
+        y_relus = None
+    n, B, every = _conv_grad_maps(who, [('xs', xs), ('dys', dys), ('y_relus', y_relus)])
+    cin, cout = int(xs[0].shape[3]), int(dys[0].shape[3])
+    if y_relus is not None and any(y is not None and int(y.shape[3]) != cout for y in y_relus):
+        raise ValueError('%s: y_relus must have the shapes of dys' % who)
+    if cin % 32 or cout % 64:
+        raise ValueError('%s: cin %d must be a multiple of 32, cout %d a multiple of 64' % (who, cin, cout))
+    _conv_grad_on_gpu(who, every)
+    lv = (L.OdetConvGradLevel * n)()
+    for i in range(n):
+        y = y_relus[i] if y_relus is not None else None
+        lv[i].x, lv[i].dy, lv[i].y_relu = xs[i].data_ptr(), dys[i].data_ptr(), (y.data_ptr() if y is not None else None)
+        lv[i].H, lv[i].W = int(xs[i].shape[1]), int(xs[i].shape[2])
+    dev = xs[0].device
+    dw = _out(out, (cout, 3, 3, cin), torch.float32, dev)
+    db = torch.empty((cout,), dtype=torch.float32, device=dev) if with_bias else None
+    nbytes = int(L.lib().odet_conv3x3_wgrad_workspace_bytes(lv, n, B, cin, cout))
+    ws = L.workspace(nbytes, dev) if nbytes else None
+    L.call('odet_conv3x3_wgrad_f32_levels', lv, n, L.dptr(dw), L.dptr(db), B, cin, cout,
+           C.c_void_p(ws.data_ptr()) if nbytes else None, nbytes, L.stream())
+    return dw, db
+
+
+def conv3x3_flipped_weight(weight):
+    """w'[ci][ky][kx][co] = w[co][2-ky][2-kx][ci]: the weight whose FORWARD convolution is `weight`'s input gradient, as a
+    contiguous [cin,3,3,cout] tensor (weight: [cout,cin,3,3] channels_last or contiguous, or [cout,3,3,cin])"""
+    if weight.dim() != 4 or weight.dtype != torch.float32:
+        raise ValueError('conv3x3_flipped_weight: weight must be float32 [cout,cin,3,3] or [cout,3,3,cin]')
+    w = _conv3x3_weight_nhwc(weight, 'conv3x3_flipped_weight')
+    with torch.no_grad():
+        return w.flip(1, 2).permute(3, 1, 2, 0).contiguous()
+
+
+def conv3x3_dgrad_f32_levels(dzs, weight, outs=None, flipped=None):
+    """The input gradient of conv3x3_f32_levels: dx[b,y,x,ci] = sum over taps and co of dz[b,y-ky+1,x-kx+1,co] * w[co][ky][kx][ci] --
+    the FORWARD kernel on dz (cin and cout exchanged) with the flipped, transposed weight (conv3x3_flipped_weight; `flipped`: a
+    caller's cached one), no kernel of its own.  dzs [B,H,W,cout] per level must already be gated by the layer's ReLU.  The
+    forward's rules with the roles exchanged: cout % 32 == 0, cin % 64 == 0."""
+    who = 'conv3x3_dgrad_f32_levels'
+    _, _, every = _conv_grad_maps(who, [('dzs', dzs)])
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32 or weight.dim() != 4:
+        raise ValueError('%s: weight must be a float32 [cout,cin,3,3] or [cout,3,3,cin] tensor' % who)
+    cout = int(dzs[0].shape[3])
+    cin = weight.numel() // (9 * cout) if cout else 0
+    if int(weight.shape[0]) != cout or cout % 32 or cin % 64 or cin < 64:
+        raise ValueError('%s: cout %d must be a multiple of 32 (the weight has %d output channels), cin %d a multiple of 64'
+                         % (who, cout, int(weight.shape[0]), cin))
+    _conv_grad_on_gpu(who, every + [('weight', weight)])
+    wf = conv3x3_flipped_weight(weight) if flipped is None else flipped
+    if tuple(wf.shape) != (cin, 3, 3, cout) or not wf.is_contiguous():
+        raise ValueError('%s: flipped must be a contiguous [cin,3,3,cout] tensor' % who)
+    return _conv3x3_levels(torch.float32, list(dzs), wf, None, False, outs)
+
+
+class _Conv3x3Trainable(torch.autograd.Function):
+    """ops.conv3x3_f32_levels forward; one odet_conv3x3_wgrad_f32_levels over all levels (and, only when an input needs a gradient,
+    the forward kernel on the flipped weight) backward"""
+
+    @staticmethod
+    def forward(ctx, weight, bias, relu, *xs):
+        ys = conv3x3_f32_levels(list(xs), weight, bias, relu)
+        ctx.relu, ctx.has_bias, ctx.n = bool(relu), bias is not None, len(xs)
+        ctx.save_for_backward(weight, *xs, *(ys if relu else ()))
+        return tuple(ys)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *dys):
+        weight, xs = ctx.saved_tensors[0], list(ctx.saved_tensors[1:1 + ctx.n])
+        ys = list(ctx.saved_tensors[1 + ctx.n:]) if ctx.relu else None
+        dys = [d if d.is_contiguous() else d.contiguous() for d in dys]
+        dw = db = None
+        dxs = [None] * ctx.n
+        need_b = ctx.has_bias and ctx.needs_input_grad[1]
+        if ctx.needs_input_grad[0] or need_b:
+            dw, db = conv3x3_wgrad_f32_levels(xs, dys, ys, with_bias=need_b)
+            dw = _conv3x3_weight_grad(dw, weight) if ctx.needs_input_grad[0] else None
+        if any(ctx.needs_input_grad[3:]):
+            dzs = dys if ys is None else [torch.where(y > 0, d, torch.zeros_like(d)) for y, d in zip(ys, dys)]
+            got = conv3x3_dgrad_f32_levels(dzs, weight)
+            dxs = [g if need else None for g, need in zip(got, ctx.needs_input_grad[3:])]
+        return (dw, db, None) + tuple(dxs)
+
+
+def _conv3x3_weight_nhwc(weight, who):
+    """the [cout,3,3,cin] view of a [cout,cin,3,3] or [cout,3,3,cin] weight; a [cout,3,3,3] one reads either way and is refused"""
+    a, b = tuple(weight.shape[1:3]) == (3, 3), tuple(weight.shape[2:]) == (3, 3)
+    if a == b:
+        raise ValueError('%s: weight %s is not [cout,cin,3,3] or [cout,3,3,cin] (or, with 3 channels, reads as both)'
+                         % (who, tuple(weight.shape)))
+    return weight if a else weight.permute(0, 2, 3, 1)
+
+
+def _conv3x3_weight_grad(dw, weight):
+    """the kernel's dw [cout,3,3,cin] in the parameter's own shape and memory format (what training.train_step takes as it is): a
+    [cout,cin,3,3] parameter gets the permuted view -- channels_last memory, the same bytes -- or, when it is contiguous in the
+    plain format, a contiguous copy"""
+    if tuple(weight.shape[1:3]) == (3, 3):                # an explicit [cout,3,3,cin] parameter (cin % 32 == 0: never 3)
+        return dw
+    g = dw.permute(0, 3, 1, 2)
+    if weight.is_contiguous(memory_format=torch.channels_last):
+        return g
+    return g.contiguous()
+
+
+def conv3x3_trainable_levels(xs, weight, bias, relu=False):
+    """ops.conv3x3_f32_levels with a backward pass (float32, f32_form 'exact'): the forward is conv3x3_f32_levels, bit for bit;
+    `.backward()` leaves weight.grad in the parameter's own shape and memory format and bias.grad [cout], from ONE wgrad launch
+    over all levels (plus its reduce and bias launches), and computes input gradients only when a map requires one."""
+    if current_f32_form() != 'exact':
+        raise ValueError("conv3x3_trainable_levels: the convolution backward runs only under f32_form 'exact', not %r"
+                         % current_f32_form())
+    if weight.dtype != torch.float32 or any(x.dtype != torch.float32 for x in xs):
+        raise ValueError('conv3x3_trainable_levels: maps and weight must be float32 (the convolution backward has no float16 form)')
+    return list(_Conv3x3Trainable.apply(weight, bias, bool(relu), *[x if x.is_contiguous() else x.contiguous() for x in xs]))
+
+
+def rpn_unpack_pair(d_scores, d_deltas, num_anchors, pixels, anchor_offset, out):
+    """The inverse of rpn_pack_pair's index map (odet_rpn_unpack_pair): from ``d_scores`` [B,N,2] and ``d_deltas`` [B,N,4] the
+    gradient ``out`` [B * pixels, 64 k] of one level's PADDED pair output (2A score columns, 4A delta columns, then zeros), the
+    level starting at anchor ``anchor_offset``."""
+    A, B = int(num_anchors), int(d_scores.shape[0])
+    for t, k in ((d_scores, 2), (d_deltas, 4)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 3 or t.shape[0] != B or t.shape[2] != k:
+            raise ValueError('d_scores / d_deltas must be contiguous float32 [B, N, 2] / [B, N, 4] tensors')
+    if out.dtype != torch.float32 or out.dim() != 2 or not out.is_contiguous() or out.shape[0] != B * int(pixels) \
+            or out.shape[1] < 6 * A:
+        raise ValueError('out must be a contiguous float32 [B * pixels, >= 6A] tensor')
+    if not (d_scores.is_cuda and d_deltas.is_cuda and out.is_cuda):
+        raise ValueError('rpn_unpack_pair: d_scores, d_deltas and out must be GPU tensors')
+    L.call('odet_rpn_unpack_pair', L.dptr(d_scores), d_scores.numel() // max(B, 1), int(anchor_offset) * 2, L.dptr(d_deltas),
+           d_deltas.numel() // max(B, 1), int(anchor_offset) * 4, int(pixels), A, B, int(out.shape[1]), L.dptr(out), L.stream())
+    return out
+
+
 def lateral_merge(x, weight, bias, top, out=None):
     """The FPN neck's lateral 1x1 convolution with the top-down merge in its epilogue (odet_lateral_merge_f16 / _f32;
     resnet_fpn.py:385-398): 0.5 * resize_bilinear(top) + 0.5 * (x . w^T + bias); ``x`` [B,H,W,cin], ``top`` [B,h,w,cout]
