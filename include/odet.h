@@ -42,7 +42,8 @@ extern "C" {
  * (odet_opt_step, odet_l2_loss, odet_opt_partials_bytes with the odet_opt_*_t records) and the float32 Dense backward
  * (odet_dense_dgrad_f32, odet_dense_wgrad_f32, odet_dense_grad_workspace_bytes), the 3x3 convolution's weight gradient
  * (odet_conv3x3_wgrad_f32_levels, odet_conv3x3_wgrad_workspace_bytes, odet_rpn_unpack_pair) and the RoI pooling backward
- * (odet_roi_pool_argmax, odet_roi_pool_backward); no existing struct or signature changed.  One documented order did: from
+ * (odet_roi_pool_argmax, odet_roi_pool_backward) and the FPN top-down merge's backward (odet_fpn_topdown_backward_f32); no
+ * existing struct or signature changed.  One documented order did: from
  * 4096 rows on, odet_dense_wgrad_f32 adds db in 256 running sums per column, not 4 (its own comment; below 4096 rows every bit is
  * as before). */
 #define ODET_VERSION 103
@@ -571,6 +572,30 @@ int odet_preprocess_train(const void* const* images, const int* raw_h, const int
  * arithmetic, one rounding at the end), C % 8 == 0; otherwise float32, C % 4 == 0. */
 int odet_fpn_topdown_merge(const void* top, int h, int w, const void* lateral, int H, int W,
                            int B, int C, void* out, int f16, odet_stream_t stream);
+
+/* The BACKWARD of that merge, float32 (added within 103): model/fpn/resnet_fpn.py:385-398 read in reverse -- the transpose
+ * of up = resize_bilinear(top, (H, W)) as a gather per coarse pixel, with the other summands of the coarse map's gradient
+ * folded in:
+ *   d_top[b,Y,X,c] = out_scale * ( base[b,Y,X,c] + sub[b,Y/2,X/2,c] (only where Y and X are even) + S[b,Y,X,c] )
+ * NHWC: fine [B,H,W,C] (the gradient with respect to `up`: the caller has applied the merge's 0.5), base and d_top
+ * [B,h,w,C], sub [B,ceil(h/2),ceil(w/2),C] (the gradient of the stride-2 subsample p5[:, :, ::2, ::2], i.e. of P6).  fine,
+ * base and sub are each nullable; an absent term is skipped, not added as a zero (without fine there is no S term and H, W
+ * only have to be positive).  The terms are added left to right as written; the multiply by out_scale is one float32 multiply.
+ * S, the sum of taps: for every fine pixel (y, x) in ascending y, then ascending x, with the forward's own float32
+ * expressions ys = (float)h / (float)H, fy = (float)y * ys, y0 = floor(fy), y1 = min(y0 + 1, h - 1), yl = fy - y0 (likewise
+ * x), the taps in the order TL (y0,x0), TR (y0,x1), BL (y1,x0), BR (y1,x1); each tap that lands on (Y, X) adds
+ * (g * wy) * wx, g = fine[b,y,x,c], wy = 1 - yl (top row) or yl (bottom row), wx = 1 - xl (left) or xl (right): two float32
+ * multiplies and a separate add, no FMA, onto an accumulator that starts at +0.  A clamped edge (y1 == y0 or x1 == x0)
+ * gives two separate additions, in that order.  It is the order of a serial loop over (y, x) that accumulates into the
+ * coarse map (TF's ResizeBilinearGrad on the CPU), restated in tests/neck_grad_np.py.  Taps of weight exactly zero are
+ * skipped where that leaves the bits of finite data alone; non-finite gradients are outside the contract.
+ * No atomics, no workspace, no allocation, no host read (graph-capturable); every element of d_top is written exactly once
+ * (a coarse pixel no fine pixel taps -- a downscale -- gets S = +0); the result depends on the data and the shapes only.  Any
+ * h, w, H, W combination the forward takes.  C % 4 == 0.  B == 0 is a no-op.
+ * Errors, all before any HIP call: ODET_E_INVALID (null d_top; fine, base and sub all null; h, w, H or W <= 0; B < 0; C no
+ * positive multiple of 4; a pointer not 16-byte aligned). */
+int odet_fpn_topdown_backward_f32(const float* fine, int H, int W, const float* base, const float* sub, float out_scale,
+                                  float* d_top, int h, int w, int B, int C, odet_stream_t stream);
 
 /* Convolution epilogue of the dense path, in place on an NHWC activation x [npix, C]:
  * x = relu?((x + bias[C]) (+ residual[npix, C])) -- the frozen-BatchNormalization bias, the

@@ -13,9 +13,12 @@ the GPU; every detection op is a HIP kernel behind the C ABI.  Training (`traini
 forward pass (:232-264) on the target layers of this package; the dense kernels are inference kernels (no backward), except
 the FPN RoI head with `train_roi_head=True` (float32, exact form): its four Dense layers then run ops.dense_trainable and the two
 RoI losses carry a graph into fc1, fc2, score and bbox -- and, when the maps handed to the pooling require a gradient, through
-ops.roi_pool_trainable into those maps (the models' own maps never do: the neck and the extractor have no backward yet).
+ops.roi_pool_trainable into those maps (without `train_neck` the models' own maps never do).
 Likewise the RpnHead with `train_rpn_head=True`: its three convolutions run fpn_detector's rpn_trainable over all levels at once and
-the two RPN losses carry a graph into rpn_conv, rpn_score and rpn_bbox."""
+the two RPN losses carry a graph into rpn_conv, rpn_score and rpn_bbox.  With `train_neck=True` (and at least one of the two heads
+trainable) the neck runs fpn_detector's neck_trainable: P2..P6 require a gradient, the RoI pooling takes its trainable form, the
+RpnHead returns its input gradient, the two heads' gradients meet in P2..P5 and the four losses carry a graph into the neck's seven
+convolutions -- every parameter downstream of the extractor, which stays under no_grad (it has no backward)."""
 import torch
 
 from .. import ops
@@ -38,6 +41,14 @@ def check_training_losses(training_losses, training_targets):
     if training_losses == 'hip' and training_targets != 'hip':
         raise ValueError("training_losses='hip' needs training_targets='hip', got training_targets=%r" % (training_targets,))
     return training_losses
+
+
+def check_train_neck(train_neck, train_rpn_head, train_roi_head):
+    """train_neck needs a trainable head: the neck's outputs receive a gradient only through the RpnHead's input gradient or the
+    trainable RoI pooling"""
+    if train_neck and not (train_rpn_head or train_roi_head):
+        raise ValueError('train_neck=True needs train_rpn_head=True or train_roi_head=True: no gradient reaches the neck otherwise')
+    return bool(train_neck)
 
 
 def _image_nhwc(image):
@@ -88,9 +99,11 @@ class BaseFPN(torch.nn.Module):
                  roi_training_total_num_samples=128, roi_training_max_pos_samples=32,
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0., training_targets='torch',
-                 training_losses='torch', train_roi_head=False, train_rpn_head=False):
+                 training_losses='torch', train_roi_head=False, train_rpn_head=False, train_neck=False):
         super().__init__()
         self._training_losses = check_training_losses(training_losses, training_targets)
+        # True: the training branches run the neck with a backward pass (P2..P6 require a gradient; needs a trainable head)
+        self._train_neck = check_train_neck(train_neck, train_rpn_head, train_roi_head)
         # True: the training branches run the RoI head with a backward pass (the two RoI losses carry a graph into its layers)
         self._train_roi_head = bool(train_roi_head)
         # True: the training branches run the RpnHead with a backward pass (the two RPN losses carry a graph into its layers)
@@ -193,7 +206,13 @@ class BaseFPN(torch.nn.Module):
         image_shape = [int(image.shape[1]), int(image.shape[2])]
         with torch.no_grad():
             c_list = self._extractor(image, training=training)
-            p_list = self._neck(c_list, training=training)
+            if not (training and self._train_neck):
+                p_list = self._neck(c_list, training=training)
+        if training and self._train_neck:
+            # the neck OUTSIDE no_grad (the extractor stays inside: it has no backward): P2..P6 require a gradient, which the
+            # RpnHead's input gradient and the trainable RoI pooling below deliver
+            p_list = self._get_trainable_neck_results(c_list)
+        with torch.no_grad():
             if not (training and self._train_rpn_head):
                 all_fpn_scores, all_fpn_bbox_pred = self._get_fpn_head_results(p_list)
         if training and self._train_rpn_head:
@@ -261,7 +280,7 @@ class BaseFPN(torch.nn.Module):
     def _training_roi_head(self, rois_list, p_list, image_shape, training):
         """pooling + RoI head of both training branches: under no_grad, unless train_roi_head -- then the head runs its trainable
         form outside it, so the two RoI losses carry a graph.  The pooling stays under no_grad as long as no map of p_list requires
-        a gradient (the models' own maps never do); when one does, the pooling layer takes its trainable form, the head's first
+        a gradient (the models' own maps do with train_neck); when one does, the pooling layer takes its trainable form, the head's first
         layer receives an input that requires a gradient and computes fc1's input gradient, and odet_roi_pool_backward carries
         it into the maps."""
         if self._train_roi_head and any(isinstance(p, torch.Tensor) and p.requires_grad for p in p_list):
@@ -274,6 +293,10 @@ class BaseFPN(torch.nn.Module):
 
     def _get_trainable_roi_head(self):
         raise NotImplementedError('train_roi_head=True needs a dense part with a trainable RoI head')
+
+    def _get_trainable_neck_results(self, c_list):
+        """_neck with a graph into the neck's layers: (P2..P6), bit-equal to it"""
+        raise NotImplementedError('train_neck=True needs a dense part with a trainable neck')
 
     def _get_trainable_fpn_head_results(self, p_list):
         """_get_fpn_head_results with a graph into the RpnHead's layers: ([N,2], [N,4]) of all levels, bit-equal to it"""
@@ -379,9 +402,14 @@ class ResnetV1Fpn(BaseFPN):
                  roi_training_total_num_samples=256, roi_training_max_pos_samples=64,
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3, dtype=torch.float32, device='cuda',
-                 f32_form='exact', training_targets='torch', training_losses='torch', train_roi_head=False, train_rpn_head=False):
+                 f32_form='exact', training_targets='torch', training_losses='torch', train_roi_head=False, train_rpn_head=False,
+                 train_neck=False):
         from .fpn_detector import ResNetFpnDetector, check_caller_f32_form
         check_caller_f32_form(f32_form)
+        if train_neck and (dtype != torch.float32 or f32_form != 'exact'):
+            raise ValueError("ResnetV1Fpn: train_neck=True needs dtype=torch.float32 and f32_form='exact' (the neck's backward "
+                             "has no float16 or split-precision form), got %s, %r" % (dtype, f32_form))
+        check_train_neck(train_neck, train_rpn_head, train_roi_head)
         if train_roi_head and (dtype != torch.float32 or f32_form != 'exact'):
             raise ValueError("ResnetV1Fpn: train_roi_head=True needs dtype=torch.float32 and f32_form='exact' (the Dense backward "
                              "has no float16 or split-precision form), got %s, %r" % (dtype, f32_form))
@@ -423,7 +451,7 @@ class ResnetV1Fpn(BaseFPN):
             prediction_max_objects_per_class=prediction_max_objects_per_class,
             prediction_nms_iou_threshold=prediction_nms_iou_threshold, prediction_score_threshold=prediction_score_threshold,
             training_targets=training_targets, training_losses=training_losses, train_roi_head=train_roi_head,
-            train_rpn_head=train_rpn_head)
+            train_rpn_head=train_rpn_head, train_neck=train_neck)
         self.dense = dense
 
     def _get_roi_head(self):
@@ -435,6 +463,9 @@ class ResnetV1Fpn(BaseFPN):
     def _get_trainable_fpn_head_results(self, p_list):
         scores, deltas = self._dense_ref.rpn_trainable(list(p_list))
         return scores.reshape(-1, 2), deltas.reshape(-1, 4)
+
+    def _get_trainable_neck_results(self, c_list):
+        return self._dense_ref.neck_trainable(list(c_list))
 
     def _get_extractor(self):
         return _Part(self._dense_ref.extractor)

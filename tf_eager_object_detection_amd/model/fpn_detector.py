@@ -378,6 +378,13 @@ class ResNetFpnDetector(Detector):
         p2 = self._lateral_merge(p3, self.l2, c2)
         return _conv_epi(self.s2, p2), _conv_epi(self.s3, p3), _conv_epi(self.s4, p4), p5, p6
 
+    @_in_f32_form
+    def neck_trainable(self, c_list):
+        """neck with a backward pass into p5, l4, l3, l2, s4, s3 and s2 (float32, f32_form 'exact'; model/neck_trainable.py): outputs
+        bit-equal to neck()'s with its shapes and strides, and a gradient into those maps of c_list that require one"""
+        from .neck_trainable import neck_trainable
+        return neck_trainable(self, c_list)
+
     def _lateral_merge(self, top, conv, c):
         """P_k = 0.5 * resize_bilinear(P_{k+1}) + 0.5 * lateral(C_k) (resnet_fpn.py:385-398) in ONE launch: the merge rides in
         the epilogue of the lateral 1x1 convolution (ops.lateral_merge: the lateral map is never written; 226 vs 301 us for
@@ -447,9 +454,9 @@ class ResNetFpnDetector(Detector):
     def roi_head_trainable(self, roi_features):
         """roi_head with a backward pass into fc1, fc2, score and bbox (float32, f32_form 'exact'): the same four layers through
         ops.dense_trainable, outputs bit-equal to roi_head's.  Features that require no gradient (the pooling of the models' own
-        maps) cost nothing more: fc1's input gradient -- a read of its 51 MB of weights -- is then never computed.  Features from
+        maps without train_neck) cost nothing more: fc1's input gradient -- a read of its 51 MB of weights -- is then never computed.  Features from
         ops.roi_pool_trainable require one: fc1's dense_dgrad produces the [n,P,P,C] gradient that odet_roi_pool_backward
-        carries into the feature maps."""
+        carries into the feature maps, where neck_trainable consumes it."""
         if self.dtype != torch.float32 or self.f32_form != 'exact':
             raise ValueError("roi_head_trainable needs dtype=torch.float32 and f32_form='exact' (got %s, %r)"
                              % (self.dtype, self.f32_form))

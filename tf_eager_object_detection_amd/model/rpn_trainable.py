@@ -84,7 +84,7 @@ def rpn_trainable(det, p_list):
     """det.rpn(p_list) with a backward pass into rpn_conv, rpn_score and rpn_bbox: `.backward()` leaves the six parameters'
     gradients in their own shapes and memory formats -- the pair's from the padded [64, 512] contraction, handed out as row
     slices the way _FinalTrainable does -- and carries a gradient into those maps of p_list that require one (the models' own
-    maps never do: the neck has no backward yet)."""
+    maps do with train_neck=True: neck_trainable consumes it)."""
     if det.dtype != torch.float32 or det.f32_form != 'exact':
         raise ValueError("rpn_trainable needs dtype=torch.float32 and f32_form='exact' (got %s, %r)" % (det.dtype, det.f32_form))
     p0 = p_list[0]

@@ -517,6 +517,49 @@ def fpn_topdown_merge(top, lateral, out=None):
     return out
 
 
+def fpn_topdown_backward(fine, top_hw, base=None, sub=None, out_scale=1.0, out=None):
+    """The backward of the top-down merge's resize with the coarse map's other gradient terms folded in
+    (odet_fpn_topdown_backward_f32; resnet_fpn.py:385-398 in reverse): d_top [B,h,w,C] = out_scale * (base + sub placed at the even
+    pixels + the transpose of resize_bilinear(top, (H, W)) applied to fine), added in that order, in one launch without atomics.
+    ``fine`` [B,H,W,C] (the gradient with respect to the resized map, the merge's 0.5 already applied), ``base`` [B,h,w,C] and
+    ``sub`` [B,ceil(h/2),ceil(w/2),C] (the gradient of top[:, ::2, ::2]) are contiguous NHWC float32 GPU tensors; each may be
+    None (its term is skipped), not all three.  ``top_hw`` = (h, w).  float32, f32_form 'exact' only."""
+    who = 'fpn_topdown_backward'
+    named = [(n, t) for n, t in (('fine', fine), ('base', base), ('sub', sub)) if t is not None]
+    if not named:
+        raise ValueError('%s: at least one of fine, base and sub is needed' % who)
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError('%s: %s must be a float32 tensor (the neck backward has no float16 form), got %s'
+                             % (who, name, getattr(t, 'dtype', type(t).__name__)))
+    if current_f32_form() != 'exact':
+        raise ValueError("%s: the neck backward runs only under f32_form 'exact' (no split-precision backward), not %r"
+                         % (who, current_f32_form()))
+    for name, t in named:
+        if t.dim() != 4 or not t.is_contiguous():
+            raise ValueError('%s: %s must be a contiguous NHWC tensor [B,H,W,C]' % (who, name))
+    h, w = int(top_hw[0]), int(top_hw[1])
+    B, Cc = int(named[0][1].shape[0]), int(named[0][1].shape[3])
+    if h < 1 or w < 1 or Cc < 4 or Cc % 4:
+        raise ValueError('%s: top_hw %s must be positive and C %d a multiple of 4' % (who, (h, w), Cc))
+    want = {'base': (B, h, w, Cc), 'sub': (B, (h + 1) // 2, (w + 1) // 2, Cc)}
+    for name, t in named:
+        if name == 'fine':
+            if int(t.shape[1]) < 1 or int(t.shape[2]) < 1:
+                raise ValueError('%s: fine %s must have a positive size' % (who, tuple(t.shape)))
+        elif tuple(t.shape) != want[name]:
+            raise ValueError('%s: %s %s does not go with top_hw %s and %s %s (expected %s)'
+                             % (who, name, tuple(t.shape), (h, w), named[0][0], tuple(named[0][1].shape), want[name]))
+    for name, t in named:
+        if not t.is_cuda:
+            raise ValueError('%s: %s must be a GPU tensor' % (who, name))
+    out = _out(out, (B, h, w, Cc), torch.float32, named[0][1].device)
+    H, W = (int(fine.shape[1]), int(fine.shape[2])) if fine is not None else (h, w)
+    L.call('odet_fpn_topdown_backward_f32', L.dptr(fine), H, W, L.dptr(base), L.dptr(sub), float(out_scale), L.dptr(out), h, w, B,
+           Cc, L.stream())
+    return out
+
+
 def bias_act_(x, bias, residual=None, relu=True):
     """In place on an NHWC (or any [..., C] contiguous) activation: x = relu?((x + bias) (+ residual)) -- the
     convolution epilogue of the reference's ResNet blocks / RPN head (resnet_fpn.py:154-205) in one pass."""
