@@ -42,7 +42,8 @@ extern "C" {
  * (odet_opt_step, odet_l2_loss, odet_opt_partials_bytes with the odet_opt_*_t records) and the float32 Dense backward
  * (odet_dense_dgrad_f32, odet_dense_wgrad_f32, odet_dense_grad_workspace_bytes), the 3x3 convolution's weight gradient
  * (odet_conv3x3_wgrad_f32_levels, odet_conv3x3_wgrad_workspace_bytes, odet_rpn_unpack_pair) and the RoI pooling backward
- * (odet_roi_pool_argmax, odet_roi_pool_backward) and the FPN top-down merge's backward (odet_fpn_topdown_backward_f32); no
+ * (odet_roi_pool_argmax, odet_roi_pool_backward) and the FPN top-down merge's backward (odet_fpn_topdown_backward_f32) and the
+ * two elementwise launches of the ResNet bottleneck's backward (odet_stride_gather_f32, odet_block_input_grad_f32); no
  * existing struct or signature changed.  One documented order did: from
  * 4096 rows on, odet_dense_wgrad_f32 adds db in 256 running sums per column, not 4 (its own comment; below 4096 rows every bit is
  * as before). */
@@ -596,6 +597,37 @@ int odet_fpn_topdown_merge(const void* top, int h, int w, const void* lateral, i
  * positive multiple of 4; a pointer not 16-byte aligned). */
 int odet_fpn_topdown_backward_f32(const float* fine, int H, int W, const float* base, const float* sub, float out_scale,
                                   float* d_top, int h, int w, int B, int C, odet_stream_t stream);
+
+/* ---- ResNet bottleneck backward: the two elementwise launches (added within 103) ------------------------------------------ */
+
+/* The stride-s subsample of an NHWC float32 map, model/fpn/resnet_fpn.py:154-205 (Conv2D(1x1, strides=2, 'valid') on the first
+ * block of conv3..conv5 reads every second pixel):
+ *   out[b,i,j,c] = x[b, i*stride, j*stride, c],  x [B,H,W,C], out [B,Ho,Wo,C], Ho = (H-1)/stride + 1, Wo = (W-1)/stride + 1.
+ * The forward convolution reads the map strided and never writes this; the Dense weight gradient of such a layer needs its input
+ * as contiguous [rows, cin].  stride is 1 (a copy) or 2.  A copy of bits: no arithmetic.  No workspace, no host read
+ * (graph-capturable); every element of out is written exactly once.  B == 0 is a no-op.
+ * Errors, all before any HIP call: ODET_E_INVALID (a null pointer; H or W <= 0; B < 0; C no positive multiple of 4; a stride other
+ * than 1 or 2; a pointer not 16-byte aligned). */
+int odet_stride_gather_f32(const float* x, int B, int H, int W, int C, int stride, float* out, odet_stream_t stream);
+
+/* The gradient with respect to a bottleneck block's INPUT (model/fpn/resnet_fpn.py:154-205 in reverse: Add([shortcut, x]) +
+ * Activation('relu') at the block's end, the two branches that read the block's input at its start), dx [B,H,W,C] NHWC float32, in
+ * one of two forms chosen by which pointers are null:
+ *   identity shortcut (dy, y, d1 non-null [B,H,W,C]; d2 null; stride 1):
+ *       dx[i] = (y[i] > 0 ? dy[i] : +0) + d1[i]
+ *     y: the block's output (after the final ReLU), dy: its gradient -- the first term is the shortcut's gradient through that ReLU
+ *     (strictly greater: y == +0 or -0 closes the gate) --, d1: the input gradient of the block's first convolution.
+ *   convolutional shortcut (dy and y null; d1 and the nullable d2 [B,Ho,Wo,C], Ho = (H-1)/stride + 1, Wo likewise):
+ *       dx[b,Y,X,c] = d1[b,Y/stride,X/stride,c] + d2[b,Y/stride,X/stride,c]   where Y % stride == 0 and X % stride == 0,
+ *                     +0                                                      elsewhere
+ *     the transpose of odet_stride_gather_f32 applied to the sum of the two branches' input gradients (first convolution, shortcut
+ *     convolution); without d2 the one term is copied.
+ * One float32 add per element (no FMA can arise), so the result is the NumPy statement's, bit for bit (tests/block_grad_np.py).
+ * No atomics, no workspace, no host read (graph-capturable); every element of dx is written exactly once.  B == 0 is a no-op.
+ * Errors, all before any HIP call: ODET_E_INVALID (null dx or d1; a null / non-null pattern that is neither form; H or W <= 0;
+ * B < 0; C no positive multiple of 4; a stride other than 1 or 2; the identity form with stride 2; a pointer not 16-byte aligned). */
+int odet_block_input_grad_f32(const float* dy, const float* y, const float* d1, const float* d2, float* dx, int B, int H, int W,
+                              int C, int stride, odet_stream_t stream);
 
 /* Convolution epilogue of the dense path, in place on an NHWC activation x [npix, C]:
  * x = relu?((x + bias[C]) (+ residual[npix, C])) -- the frozen-BatchNormalization bias, the

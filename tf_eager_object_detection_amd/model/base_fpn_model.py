@@ -18,7 +18,10 @@ Likewise the RpnHead with `train_rpn_head=True`: its three convolutions run fpn_
 the two RPN losses carry a graph into rpn_conv, rpn_score and rpn_bbox.  With `train_neck=True` (and at least one of the two heads
 trainable) the neck runs fpn_detector's neck_trainable: P2..P6 require a gradient, the RoI pooling takes its trainable form, the
 RpnHead returns its input gradient, the two heads' gradients meet in P2..P5 and the four losses carry a graph into the neck's seven
-convolutions -- every parameter downstream of the extractor, which stays under no_grad (it has no backward)."""
+convolutions -- every parameter downstream of the extractor.  With `train_extractor=True` as well (which needs `train_neck`) the
+extractor runs fpn_detector's extractor_trainable outside no_grad: C2..C5 require a gradient, neck_trainable delivers dC2..dC5 and the
+losses carry a graph into every convolution of conv2..conv5 (reference resnet_fpn.py:208-225: trainable, batch-norm frozen); the stem
+(conv1 and its pooling) stays under no_grad -- it has no backward."""
 import torch
 
 from .. import ops
@@ -49,6 +52,13 @@ def check_train_neck(train_neck, train_rpn_head, train_roi_head):
     if train_neck and not (train_rpn_head or train_roi_head):
         raise ValueError('train_neck=True needs train_rpn_head=True or train_roi_head=True: no gradient reaches the neck otherwise')
     return bool(train_neck)
+
+
+def check_train_extractor(train_extractor, train_neck):
+    """train_extractor needs the trainable neck (and with it a trainable head): C2..C5 receive a gradient only through neck_trainable"""
+    if train_extractor and not train_neck:
+        raise ValueError('train_extractor=True needs train_neck=True: no gradient reaches the extractor otherwise')
+    return bool(train_extractor)
 
 
 def _image_nhwc(image):
@@ -99,9 +109,11 @@ class BaseFPN(torch.nn.Module):
                  roi_training_total_num_samples=128, roi_training_max_pos_samples=32,
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0., training_targets='torch',
-                 training_losses='torch', train_roi_head=False, train_rpn_head=False, train_neck=False):
+                 training_losses='torch', train_roi_head=False, train_rpn_head=False, train_neck=False, train_extractor=False):
         super().__init__()
         self._training_losses = check_training_losses(training_losses, training_targets)
+        # True: the training branches run conv2..conv5 with a backward pass (C2..C5 require a gradient; needs the trainable neck)
+        self._train_extractor = check_train_extractor(train_extractor, train_neck)
         # True: the training branches run the neck with a backward pass (P2..P6 require a gradient; needs a trainable head)
         self._train_neck = check_train_neck(train_neck, train_rpn_head, train_roi_head)
         # True: the training branches run the RoI head with a backward pass (the two RoI losses carry a graph into its layers)
@@ -204,13 +216,18 @@ class BaseFPN(torch.nn.Module):
             image = inputs
         image = _image_nhwc(image)
         image_shape = [int(image.shape[1]), int(image.shape[2])]
+        if training and self._train_extractor:
+            # conv2..conv5 OUTSIDE no_grad (the stem stays inside: it has no backward): C2..C5 require a gradient, which the
+            # trainable neck below delivers
+            c_list = self._get_trainable_extractor_results(image)
         with torch.no_grad():
-            c_list = self._extractor(image, training=training)
+            if not (training and self._train_extractor):
+                c_list = self._extractor(image, training=training)
             if not (training and self._train_neck):
                 p_list = self._neck(c_list, training=training)
         if training and self._train_neck:
-            # the neck OUTSIDE no_grad (the extractor stays inside: it has no backward): P2..P6 require a gradient, which the
-            # RpnHead's input gradient and the trainable RoI pooling below deliver
+            # the neck OUTSIDE no_grad (so is the extractor with train_extractor, and inside otherwise): P2..P6 require a
+            # gradient, which the RpnHead's input gradient and the trainable RoI pooling below deliver
             p_list = self._get_trainable_neck_results(c_list)
         with torch.no_grad():
             if not (training and self._train_rpn_head):
@@ -297,6 +314,10 @@ class BaseFPN(torch.nn.Module):
     def _get_trainable_neck_results(self, c_list):
         """_neck with a graph into the neck's layers: (P2..P6), bit-equal to it"""
         raise NotImplementedError('train_neck=True needs a dense part with a trainable neck')
+
+    def _get_trainable_extractor_results(self, image):
+        """_extractor with a graph into conv2..conv5: (C2..C5), bit-equal to it"""
+        raise NotImplementedError('train_extractor=True needs a dense part with a trainable extractor')
 
     def _get_trainable_fpn_head_results(self, p_list):
         """_get_fpn_head_results with a graph into the RpnHead's layers: ([N,2], [N,4]) of all levels, bit-equal to it"""
@@ -403,9 +424,13 @@ class ResnetV1Fpn(BaseFPN):
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3, dtype=torch.float32, device='cuda',
                  f32_form='exact', training_targets='torch', training_losses='torch', train_roi_head=False, train_rpn_head=False,
-                 train_neck=False):
+                 train_neck=False, train_extractor=False):
         from .fpn_detector import ResNetFpnDetector, check_caller_f32_form
         check_caller_f32_form(f32_form)
+        if train_extractor and (dtype != torch.float32 or f32_form != 'exact'):
+            raise ValueError("ResnetV1Fpn: train_extractor=True needs dtype=torch.float32 and f32_form='exact' (the bottleneck "
+                             "backward has no float16 or split-precision form), got %s, %r" % (dtype, f32_form))
+        check_train_extractor(train_extractor, train_neck)
         if train_neck and (dtype != torch.float32 or f32_form != 'exact'):
             raise ValueError("ResnetV1Fpn: train_neck=True needs dtype=torch.float32 and f32_form='exact' (the neck's backward "
                              "has no float16 or split-precision form), got %s, %r" % (dtype, f32_form))
@@ -451,7 +476,7 @@ class ResnetV1Fpn(BaseFPN):
             prediction_max_objects_per_class=prediction_max_objects_per_class,
             prediction_nms_iou_threshold=prediction_nms_iou_threshold, prediction_score_threshold=prediction_score_threshold,
             training_targets=training_targets, training_losses=training_losses, train_roi_head=train_roi_head,
-            train_rpn_head=train_rpn_head, train_neck=train_neck)
+            train_rpn_head=train_rpn_head, train_neck=train_neck, train_extractor=train_extractor)
         self.dense = dense
 
     def _get_roi_head(self):
@@ -466,6 +491,9 @@ class ResnetV1Fpn(BaseFPN):
 
     def _get_trainable_neck_results(self, c_list):
         return self._dense_ref.neck_trainable(list(c_list))
+
+    def _get_trainable_extractor_results(self, image):
+        return self._dense_ref.extractor_trainable(image)
 
     def _get_extractor(self):
         return _Part(self._dense_ref.extractor)

@@ -1,0 +1,118 @@
+"""The float32 ResNet extractor of model/fpn_detector.py with a backward pass from conv2 up: ResNetFpnDetector.extractor_trainable
+(reference resnet_fpn.py:208-225, 262-289: conv2..conv5 trainable, batch-norm frozen -- _fold_frozen_bn has folded it into the
+weights, so the folded weights ARE the parameters).  One torch.autograd.Function per bottleneck (_Block): the forward is
+_Block.forward's own launches (outputs bit-equal, same shapes and strides); the backward runs the block in reverse on this package's
+kernels -- the 1x1 convolutions as the Dense backward over pixels with the ReLU gates applied while staging, the 3x3 convolution's
+weight gradient as ops.conv3x3_wgrad_f32_levels and its input gradient as the forward kernel on the flipped weight, the block's join
+(shortcut + first convolution, with the stride-2 scatter of a stage's first block) as ops.block_input_grad.  The stem stays frozen
+under no_grad: conv1's 7x7 weight gradient and the max-pooling's backward are not built."""
+import torch
+
+from .. import ops
+from .fpn_detector import _conv_epi, _nhwc, _stem
+from .neck_trainable import _rows, neck_conv_flipped
+
+STAGES = ('conv2', 'conv3', 'conv4', 'conv5')
+
+
+def block_layers(blk):
+    """a bottleneck's convolutions in the order of its parameters: c1, c2, c3 (, short)"""
+    return (blk.c1, blk.c2, blk.c3) + ((blk.short,) if blk.short is not None else ())
+
+
+def _weight2d(w):
+    """a [cout, cin, 1, 1] weight as the Dense backward's [cout, cin] (the same floats in either memory format)"""
+    return w.reshape(int(w.shape[0]), -1).contiguous()
+
+
+class _BlockTrainable(torch.autograd.Function):
+    """One bottleneck with a backward pass.  Forward: _Block.forward's float32 launches (pointwise, conv3x3_f32, then pointwise with
+    the residual or pointwise_dual); saves the block's input x (a strided block: xs = stride_gather(x, s) in its place, the only form
+    the backward reads), c1's output a, c2's output b and the block's output y.  Backward, with dy arriving:
+        c3     dw, db = dense_wgrad(dy, b, y_relu=y);   db_gated = dense_dgrad(dy, w3, y_relu=y, x_relu=b)   (c2's ReLU gate applied)
+        c2     dw, db = conv3x3_wgrad_f32_levels([a], [db_gated]);   da = conv3x3_dgrad_f32_levels([db_gated], w2, flipped)
+        c1     dw, db = dense_wgrad(da, x or xs, y_relu=a);   d1 = dense_dgrad(da, w1, y_relu=a)              (d1, d2, dx only when x
+        short  dw, db = dense_wgrad(dy, x or xs, y_relu=y);   d2 = dense_dgrad(dy, ws, y_relu=y)               requires a gradient)
+        dx = block_input_grad(d1, dy, y)  (identity shortcut)  or  block_input_grad(d1, d2=d2, stride, in_hw)  (convolutional one)
+    The forward's concatenated [w3 | ws] weight is a forward detail: the backward reads the two parameters themselves."""
+
+    @staticmethod
+    def forward(ctx, blk, wf2, x, *params):
+        ctx.set_materialize_grads(False)                                         # (an output nothing reads arrives as None)
+        a = _conv_epi(blk.c1, x, relu=True)
+        b = _conv_epi(blk.c2, a, relu=True)
+        stride = int(blk.c1.stride[0])
+        if blk.short is not None:
+            w, bias = blk._dual_weights()
+            y = ops.pointwise_dual(_nhwc(b), _nhwc(x), w, bias, stride, relu=True).permute(0, 3, 1, 2)
+        else:
+            y = _conv_epi(blk.c3, b, relu=True, residual=x)
+        if wf2 is not None:                                                       # (None: no graph is being recorded)
+            xn = _nhwc(x)
+            ctx.stride, ctx.in_hw = stride, (int(xn.shape[1]), int(xn.shape[2]))
+            ctx.layouts = [(tuple(p.shape), tuple(p.stride())) for p in params]
+            ctx.save_for_backward(wf2, xn if stride == 1 else ops.stride_gather(xn, stride), _nhwc(a), _nhwc(b), _nhwc(y), *params)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        n_params = len(ctx.layouts)
+        if dy is None:
+            return (None,) * (3 + n_params)
+        wf2, xs, a, b, y = ctx.saved_tensors[:5]
+        weights = ctx.saved_tensors[5::2]
+        need_dx = ctx.needs_input_grad[2]
+        dy = _nhwc(dy)
+        # c3, then c2 on the gradient that leaves c3 already gated by c2's ReLU
+        g3 = ops.dense_wgrad(_rows(dy), _rows(b), y_relu=_rows(y))
+        db_gated = ops.dense_dgrad(_rows(dy), _weight2d(weights[2]), y_relu=_rows(y), x_relu=_rows(b)).view(b.shape)
+        dw2, db2 = ops.conv3x3_wgrad_f32_levels([a], [db_gated])
+        da = ops.conv3x3_dgrad_f32_levels([db_gated], weights[1], flipped=wf2)[0]
+        # c1 and the shortcut convolution read the block's (subsampled) input
+        g1 = ops.dense_wgrad(_rows(da), _rows(xs), y_relu=_rows(a))
+        d1 = ops.dense_dgrad(_rows(da), _weight2d(weights[0]), y_relu=_rows(a)) if need_dx else None
+        grads = [g1, (ops._conv3x3_weight_grad(dw2, weights[1]), db2), g3]
+        dx = d2 = None
+        if n_params == 8:
+            grads.append(ops.dense_wgrad(_rows(dy), _rows(xs), y_relu=_rows(y)))
+            if need_dx:
+                d2 = ops.dense_dgrad(_rows(dy), _weight2d(weights[3]), y_relu=_rows(y)).view(xs.shape)
+                dx = ops.block_input_grad(d1.view(xs.shape), d2=d2, stride=ctx.stride, in_hw=ctx.in_hw)
+        elif need_dx:
+            dx = ops.block_input_grad(d1.view(xs.shape), dy=dy, y=y)
+        # in the order of the parameters, each gradient in its parameter's own shape and memory format (a [cout, cin, 1, 1] weight:
+        # the same cout x cin floats in either format)
+        d_params = []
+        for i, (dw, db) in enumerate(grads):
+            if dw.dim() == 2:
+                shape, stride = ctx.layouts[2 * i]
+                dw = torch.as_strided(dw, shape, stride, dw.storage_offset())
+            d_params += [dw, db]
+        return (None, None, None if dx is None else dx.permute(0, 3, 1, 2)) + tuple(d_params)
+
+
+def block_trainable(blk, x):
+    """blk(x) (a fpn_detector._Block on a channels_last float32 map) with a backward pass into the block's 6 or 8 parameters, and into
+    x when it requires a gradient; float32, f32_form 'exact' only"""
+    if x.dtype != torch.float32 or ops.current_f32_form() != 'exact':
+        raise ValueError("block_trainable needs a float32 map and f32_form='exact' (the bottleneck backward has no float16 or "
+                         "split-precision form), got %s, %r" % (x.dtype, ops.current_f32_form()))
+    wf2 = neck_conv_flipped(blk.c2) if torch.is_grad_enabled() else None
+    params = [p for conv in block_layers(blk) for p in (conv.weight, conv.bias)]
+    return _BlockTrainable.apply(blk, wf2, x, *params)
+
+
+def extractor_trainable(det, images_nhwc):
+    """det.extractor(images_nhwc) with a backward pass into conv2..conv5: (C2, C3, C4, C5), bit-equal to extractor()'s.  The stem
+    (conv1 + pooling) runs under no_grad as in extractor(): conv1 stays frozen."""
+    if det.dtype != torch.float32 or det.f32_form != 'exact':
+        raise ValueError("extractor_trainable needs dtype=torch.float32 and f32_form='exact' (got %s, %r)" % (det.dtype, det.f32_form))
+    with torch.no_grad():
+        x = _stem(det.conv1, images_nhwc, det.dtype)
+    outs = []
+    for name in STAGES:
+        for blk in getattr(det, name):
+            x = block_trainable(blk, x)
+        outs.append(x)
+    return tuple(outs)

@@ -363,6 +363,13 @@ class ResNetFpnDetector(Detector):
         c4 = self.conv4(c3)
         return c2, c3, c4, self.conv5(c4)
 
+    @_in_f32_form
+    def extractor_trainable(self, images_nhwc):
+        """extractor with a backward pass into conv2..conv5 (float32, f32_form 'exact'; model/extractor_trainable.py): outputs
+        bit-equal to extractor()'s with its shapes and strides; the stem runs under no_grad and conv1 stays frozen"""
+        from .extractor_trainable import extractor_trainable
+        return extractor_trainable(self, images_nhwc)
+
     def features(self, images_nhwc):
         """[B,H,W,3] -> (P2..P6), each [B,256,h,w] channels_last (= NHWC in memory)."""
         return self.neck(self.extractor(images_nhwc))

@@ -104,7 +104,7 @@ class _NeckTrainable(torch.autograd.Function):
 def neck_trainable(det, c_list):
     """det.neck(c_list) with a backward pass into p5, l4, l3, l2, s4, s3 and s2: `.backward()` leaves the fourteen parameters'
     gradients in their own shapes and memory formats and carries a gradient into those maps of c_list that require one (the
-    models' own maps never do: the extractor has no backward)."""
+    models' own maps do with train_extractor: model/extractor_trainable.py)."""
     if det.dtype != torch.float32 or det.f32_form != 'exact':
         raise ValueError("neck_trainable needs dtype=torch.float32 and f32_form='exact' (got %s, %r)" % (det.dtype, det.f32_form))
     flips = (None, None, None)

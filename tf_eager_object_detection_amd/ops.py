@@ -560,6 +560,79 @@ def fpn_topdown_backward(fine, top_hw, base=None, sub=None, out_scale=1.0, out=N
     return out
 
 
+def _block_grad_maps(who, named):
+    """the checks stride_gather / block_input_grad share (the style of _conv_grad_maps): float32 only, the exact form only,
+    contiguous NHWC tensors with a positive map and C a positive multiple of 4; the caller checks the shapes against each other,
+    then _conv_grad_on_gpu"""
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError('%s: %s must be a float32 tensor (the bottleneck backward has no float16 form), got %s'
+                             % (who, name, getattr(t, 'dtype', type(t).__name__)))
+    if current_f32_form() != 'exact':
+        raise ValueError("%s: the bottleneck backward runs only under f32_form 'exact' (no split-precision backward), not %r"
+                         % (who, current_f32_form()))
+    for name, t in named:
+        if t.dim() != 4 or not t.is_contiguous():
+            raise ValueError('%s: %s must be a contiguous NHWC tensor [B,H,W,C]' % (who, name))
+    for name, t in named:
+        if int(t.shape[1]) < 1 or int(t.shape[2]) < 1 or int(t.shape[3]) < 4 or int(t.shape[3]) % 4:
+            raise ValueError('%s: %s %s must have a positive map size and C a positive multiple of 4' % (who, name, tuple(t.shape)))
+
+
+def _stride_1_or_2(who, stride):
+    if stride not in (1, 2):
+        raise ValueError('%s: stride must be 1 or 2, got %r' % (who, stride))
+    return int(stride)
+
+
+def stride_gather(x, stride, out=None):
+    """x[:, ::stride, ::stride, :] as a contiguous map (odet_stride_gather_f32): the [rows, cin] input that dense_wgrad needs for a
+    strided 1x1 convolution (resnet_fpn.py:154-205: the first block of conv3..conv5).  ``x`` [B,H,W,C] contiguous NHWC float32 on
+    the GPU, C % 4 == 0, stride 1 or 2 -> [B, ceil(H/stride), ceil(W/stride), C].  float32, f32_form 'exact' only."""
+    who = 'stride_gather'
+    _block_grad_maps(who, [('x', x)])
+    stride = _stride_1_or_2(who, stride)
+    _conv_grad_on_gpu(who, [('x', x)])
+    B, H, W, Cc = (int(v) for v in x.shape)
+    out = _out(out, (B, (H - 1) // stride + 1, (W - 1) // stride + 1, Cc), torch.float32, x.device)
+    L.call('odet_stride_gather_f32', L.dptr(x), B, H, W, Cc, stride, L.dptr(out), L.stream())
+    return out
+
+
+def block_input_grad(d1, dy=None, y=None, d2=None, stride=1, in_hw=None, out=None):
+    """The gradient with respect to a bottleneck block's input in one launch (odet_block_input_grad_f32), in one of two forms.
+    Identity shortcut -- ``dy`` and ``y`` given: dx = (y > 0 ? dy : +0) + d1, all [B,H,W,C] (y: the block's output, dy: its
+    gradient, d1: the first convolution's input gradient); no d2, stride 1.  Convolutional shortcut -- no dy / y:
+    dx[b,Y,X] = d1[b,Y/stride,X/stride] + d2[...] at the pixels both of whose coordinates are multiples of stride, +0 elsewhere;
+    ``d1`` and the optional ``d2`` (the shortcut convolution's input gradient) [B,Ho,Wo,C], ``in_hw`` = (H, W) of the block's
+    input with ceil(H/stride) == Ho (default: (Ho, Wo) at stride 1; required at stride 2, where two sizes share an Ho).
+    Contiguous NHWC float32 GPU tensors, C % 4 == 0.  float32, f32_form 'exact' only."""
+    who = 'block_input_grad'
+    if (dy is None) != (y is None):
+        raise ValueError('%s: dy and y come together (the identity form) or not at all (the convolutional-shortcut form)' % who)
+    identity = dy is not None
+    named = [(n, t) for n, t in (('d1', d1), ('dy', dy), ('y', y), ('d2', d2)) if t is not None or n == 'd1']
+    _block_grad_maps(who, named)
+    stride = _stride_1_or_2(who, stride)
+    if identity and (d2 is not None or stride != 1):
+        raise ValueError('%s: the identity form (dy, y, d1) takes no d2 and stride 1 only' % who)
+    B, Ho, Wo, Cc = (int(v) for v in d1.shape)
+    for name, t in named[1:]:
+        if tuple(t.shape) != (B, Ho, Wo, Cc):
+            raise ValueError('%s: %s %s does not go with d1 %s' % (who, name, tuple(t.shape), (B, Ho, Wo, Cc)))
+    if in_hw is None:
+        if stride != 1:
+            raise ValueError('%s: in_hw (the size of the block\'s input) is needed at stride 2' % who)
+        in_hw = (Ho, Wo)
+    H, W = int(in_hw[0]), int(in_hw[1])
+    if H < 1 or W < 1 or ((H - 1) // stride + 1, (W - 1) // stride + 1) != (Ho, Wo):
+        raise ValueError('%s: in_hw %s at stride %d does not go with d1 %s' % (who, (H, W), stride, (B, Ho, Wo, Cc)))
+    _conv_grad_on_gpu(who, named)
+    out = _out(out, (B, H, W, Cc), torch.float32, d1.device)
+    L.call('odet_block_input_grad_f32', L.dptr(dy), L.dptr(y), L.dptr(d1), L.dptr(d2), L.dptr(out), B, H, W, Cc, stride, L.stream())
+    return out
+
+
 def bias_act_(x, bias, residual=None, relu=True):
     """In place on an NHWC (or any [..., C] contiguous) activation: x = relu?((x + bias) (+ residual)) -- the
     convolution epilogue of the reference's ResNet blocks / RPN head (resnet_fpn.py:154-205) in one pass."""
