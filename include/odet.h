@@ -43,7 +43,8 @@ extern "C" {
  * (odet_dense_dgrad_f32, odet_dense_wgrad_f32, odet_dense_grad_workspace_bytes), the 3x3 convolution's weight gradient
  * (odet_conv3x3_wgrad_f32_levels, odet_conv3x3_wgrad_workspace_bytes, odet_rpn_unpack_pair) and the RoI pooling backward
  * (odet_roi_pool_argmax, odet_roi_pool_backward) and the FPN top-down merge's backward (odet_fpn_topdown_backward_f32) and the
- * two elementwise launches of the ResNet bottleneck's backward (odet_stride_gather_f32, odet_block_input_grad_f32); no
+ * two elementwise launches of the ResNet bottleneck's backward (odet_stride_gather_f32, odet_block_input_grad_f32) and the VGG16
+ * training graph's max-pooling and dropout backward (odet_relu_maxpool2_backward_f32, odet_dropout_f32, odet_dropout_backward_f32); no
  * existing struct or signature changed.  One documented order did: from
  * 4096 rows on, odet_dense_wgrad_f32 adds db in 256 running sums per column, not 4 (its own comment; below 4096 rows every bit is
  * as before). */
@@ -628,6 +629,42 @@ int odet_stride_gather_f32(const float* x, int B, int H, int W, int C, int strid
  * B < 0; C no positive multiple of 4; a stride other than 1 or 2; the identity form with stride 2; a pointer not 16-byte aligned). */
 int odet_block_input_grad_f32(const float* dy, const float* y, const float* d1, const float* d2, float* dx, int B, int H, int W,
                               int C, int stride, odet_stream_t stream);
+
+/* ---- VGG16 training graph: max-pooling and dropout backward (added within 103) ---------------------------------------------- */
+
+/* The backward of odet_bias_relu_maxpool's float32 2x2 / stride-2 ceil-mode form -- MaxPooling2D((2,2), 2, 'same') after a ReLU
+ * convolution, model/faster_rcnn/vgg16_faster_rcnn.py:307, 325 (block3_pool, block4_pool) -- as TF computes it: MaxPoolGrad, then
+ * ReluGrad.  z [B,H,W,C] NHWC float32 is the convolution's raw output WITHOUT its bias (what the forward reads), bias [C],
+ * dpool [B,OH,OW,C] with OH = (H+1)/2, OW = (W+1)/2, dz [B,H,W,C]:
+ *   a = max(z + bias, 0)                         one float32 add, the sum the forward forms
+ *   dz[b,y,x,c] = dpool[b,y>>1,x>>1,c]           if a[b,y,x,c] > 0 and (y,x) is the FIRST position of its window, in the row-major
+ *                                                order (0,0),(0,1),(1,0),(1,1), that holds the window's maximum (strict '>' while
+ *                                                scanning); a window whose maximum is 0 passes nothing
+ *                 +0                             otherwise
+ * Windows at an odd bottom or right edge hold only their taps inside the map (TF's 'same' rule pads at the end).  The windows
+ * do not overlap: a gather, no atomics, no workspace, no host read (graph-capturable); every element of dz is written exactly
+ * once.  Algorithmic bytes: 4 * (2 H W + OH OW) * C * B.  B == 0 is a no-op.
+ * Errors, all before any HIP call: ODET_E_INVALID (a null pointer; H or W <= 0; B < 0; C no positive multiple of 4; a pointer not
+ * 16-byte aligned). */
+int odet_relu_maxpool2_backward_f32(const float* z, const float* bias, const float* dpool, float* dz, int B, int H, int W, int C,
+                                    odet_stream_t stream);
+
+/* tf.nn.dropout of TF r1.13 (model/faster_rcnn/vgg16_faster_rcnn.py:250-253: both dropouts of Vgg16RoiHead active in training,
+ * keep_rate 0.5) on a flat float32 tensor of n elements, with the counter-based rule of "training targets" in place of TF's
+ * generator.  Element e takes word e & 3 of philox((e >> 2, image_id, stream_id, 0), (seed low word, seed high word)) and
+ *   u = bitcast<float>((word & 0x7fffff) | 0x3f800000) - 1        TF's Uint32ToFloat, in [0, 1)
+ *   keep = floor(keep_prob + u)                                    a float32 add: 1 with probability keep_prob, else 0
+ *   forward   y[e]  = (x[e] / keep_prob) * keep                    a float32 division, then the multiplication
+ *   backward  dx[e] = (dy[e] * keep) / keep_prob                   the mask is recomputed from the same counters, never stored
+ * keep_prob == 1 copies the input unchanged (TF returns it as it is).  Streams 0-5 belong to the samplers and the input stage; 6
+ * is the dropout after fc1, 7 the one after fc2.  x == y (in place) is allowed.  Any n in [0, 2^34]; n == 0 is a no-op.  No
+ * workspace, no host read (graph-capturable).
+ * Errors, all before any HIP call: ODET_E_INVALID (n outside [0, 2^34]; keep_prob outside (0, 1]; a null pointer; a pointer not
+ * 16-byte aligned). */
+int odet_dropout_f32(const float* x, float* y, long long n, float keep_prob, uint64_t seed, uint32_t image_id, uint32_t stream_id,
+                     odet_stream_t stream);
+int odet_dropout_backward_f32(const float* dy, float* dx, long long n, float keep_prob, uint64_t seed, uint32_t image_id,
+                              uint32_t stream_id, odet_stream_t stream);
 
 /* Convolution epilogue of the dense path, in place on an NHWC activation x [npix, C]:
  * x = relu?((x + bias[C]) (+ residual[npix, C])) -- the frozen-BatchNormalization bias, the

@@ -67,14 +67,14 @@ struct OdetArena {
 #ifdef __HIPCC__
 // ---- the counter-based random rule (include/odet.h "training targets") ---------------------
 // Streams of philox((i, image_id, stream, 0), seed): 0-4 the target samplers (targets.hip), 5 the training input stage's
-// flip decision (preprocess.hip, taken on the host).
+// flip decision (preprocess.hip, taken on the host), 6-7 the RoI head's two dropouts (vgg_grad.hip; an element index in place of i).
 enum { TG_STREAM_ANCHOR_FG = 0, TG_STREAM_ANCHOR_BG = 1, TG_STREAM_ROI_FG = 2, TG_STREAM_ROI_BG = 3, TG_STREAM_ROI_REPLACE = 4,
-       TG_STREAM_IMAGE_FLIP = 5 };
+       TG_STREAM_IMAGE_FLIP = 5, TG_STREAM_DROPOUT_FC1 = 6, TG_STREAM_DROPOUT_FC2 = 7 };
 
-// Philox4x32-10 (Salmon et al., SC'11); only the first two output words are used anywhere.  One routine for the device
-// (the samplers) and the host (the flip flags).
-__host__ __device__ __forceinline__ void odet_philox2(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                                      uint32_t k1, uint32_t* w0, uint32_t* w1) {
+// Philox4x32-10 (Salmon et al., SC'11), all four output words.  One routine for the device (the samplers, the dropout mask) and
+// the host (the flip flags).
+__host__ __device__ __forceinline__ void odet_philox4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                      uint32_t k1, uint32_t* w) {
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
     const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
@@ -83,7 +83,15 @@ __host__ __device__ __forceinline__ void odet_philox2(uint32_t c0, uint32_t c1, 
     c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }
-  *w0 = c0; *w1 = c1;
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
+// its first two words: all the samplers and the flip flags use
+__host__ __device__ __forceinline__ void odet_philox2(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                      uint32_t k1, uint32_t* w0, uint32_t* w1) {
+  uint32_t w[4];
+  odet_philox4(c0, c1, c2, c3, k0, k1, w);
+  *w0 = w[0]; *w1 = w[1];
 }
 
 // ---- device math -------------------------------------------------------------------------

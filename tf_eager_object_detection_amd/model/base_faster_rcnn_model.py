@@ -6,7 +6,14 @@ path, with the reference's constructor arguments, `call(inputs, training=None, m
 `call` composes the reference-named layers in the reference's order (:126-198): `_extractor` -> `_anchor_generator`
 (generate_by_anchor_base_tf) -> `_rpn_head` -> the [A bg | A fg] score re-layout + softmax -> `_rpn_proposal` ->
 `_roi_pooling` (RoiPoolingCropAndResize) -> `_roi_head` -> softmax -> post_ops_prediction, with dynamic shapes and one image
-per call as in the reference.  The static-shape, sync-free arrangement for throughput is model/frcnn_detector.py."""
+per call as in the reference.  The static-shape, sync-free arrangement for throughput is model/frcnn_detector.py.
+
+The training branches run every dense part under no_grad unless a keyword switches its backward pass on (Vgg16FasterRcnn; float32,
+f32_form 'exact'): `train_roi_head` runs the RoI head's trainable form with the reference's two dropouts (the two RoI losses carry a
+graph into fc1, fc2, score and bbox), `train_rpn_head` the RpnHead's (the two RPN losses carry a graph into rpn_conv, rpn_score and
+rpn_bbox), `train_extractor` (with at least one of the two) the extractor's: the shared map requires a gradient, which the RpnHead's
+input gradient and the trainable RoI pooling deliver, and the losses carry a graph into block3_conv1 .. block5_conv3."""
+import contextlib
 import math
 
 import torch
@@ -15,6 +22,7 @@ from .. import ops
 from ..utils.anchor_generator import generate_anchor_base, generate_by_anchor_base_tf
 from .fpn_detector import caller_range_checked
 from .base_fpn_model import _Part, _image_nhwc, check_training_losses
+from .detector_base import check_caller_f32_form
 from .losses import cls_loss, fused_roi_losses, fused_rpn_losses, smooth_l1_loss
 from .prediction import post_ops_prediction
 from .proposal_target import training_target_layers
@@ -46,6 +54,12 @@ class RpnHead(torch.nn.Module):
 class BaseFasterRcnn(torch.nn.Module):
     """reference base_faster_rcnn_model.py:16-118 (same constructor arguments, same private attribute names)."""
 
+    # What the training branches run with a backward pass.  The constructor keeps the reference's arguments, so a concrete model
+    # with trainable dense parts (Vgg16FasterRcnn) sets these on the instance before it calls it.
+    _train_extractor = False   # the extractor: the shared map requires a gradient (needs a trainable head)
+    _train_roi_head = False    # the RoI head: the two RoI losses carry a graph into its layers
+    _train_rpn_head = False    # the RpnHead: the two RPN losses carry a graph into its layers
+
     def __init__(self, num_classes, weight_decay, ratios, scales, extractor_stride, rpn_proposal_means, rpn_proposal_stds,
                  rpn_proposal_num_pre_nms_train, rpn_proposal_num_post_nms_train, rpn_proposal_num_pre_nms_test,
                  rpn_proposal_num_post_nms_test, rpn_proposal_nms_iou_threshold, rpn_sigma,
@@ -57,6 +71,10 @@ class BaseFasterRcnn(torch.nn.Module):
                  training_targets='torch', training_losses='torch'):
         super().__init__()
         self._training_losses = check_training_losses(training_losses, training_targets)
+        check_train_extractor(self._train_extractor, self._train_rpn_head, self._train_roi_head)
+        # the image id of the RoI head's dropout masks: advances once per training call, whatever the target stage does
+        self._next_dropout_image_id = 0
+        self._dropout_image_id = 0
         self.num_classes = num_classes
         self.weight_decay = weight_decay
         self._ratios = ratios
@@ -79,7 +97,8 @@ class BaseFasterRcnn(torch.nn.Module):
             num_post_nms_train=rpn_proposal_num_post_nms_train, num_pre_nms_test=rpn_proposal_num_pre_nms_test,
             num_post_nms_test=rpn_proposal_num_post_nms_test, nms_iou_threshold=rpn_proposal_nms_iou_threshold,
             target_means=rpn_proposal_means, target_stds=rpn_proposal_stds)
-        self._roi_pooling = RoiPoolingCropAndResize(pool_size=roi_pool_size, max_pooling_flag=roi_pooling_max_pooling_flag)
+        self._roi_pooling = RoiPoolingCropAndResize(pool_size=roi_pool_size, max_pooling_flag=roi_pooling_max_pooling_flag,
+                                                    trainable=self._train_roi_head)
         # training_targets: 'torch' = AnchorTarget / ProposalTarget (generator-driven sampling), 'hip' = the fused stage
         self._anchor_target, self._proposal_target = training_target_layers(
             training_targets,
@@ -102,18 +121,57 @@ class BaseFasterRcnn(torch.nn.Module):
     def _get_rpn_head(self, weight_decay):
         return RpnHead(num_anchors=self._num_anchors, weight_decay=weight_decay)
 
+    def _trains_front(self, training):
+        """the call records a graph through the extractor or the RpnHead"""
+        return bool(training) and (self._train_extractor or self._train_rpn_head)
+
     def _anchors_and_proposals(self, image, training):
-        """:130-153 / :279-300: extractor -> anchors -> RpnHead -> fg scores -> RegionProposal"""
+        """:130-153 / :279-300: extractor -> anchors -> RpnHead -> fg scores -> RegionProposal.  The layers themselves run under
+        no_grad; in a training call the extractor and the RpnHead take their trainable forms where the keywords ask for them, and
+        anchors, softmax and proposals see detached values"""
         image_shape = [int(image.shape[1]), int(image.shape[2])]
-        shared_features = self._extractor(image, training=training)
+        if training and self._train_extractor:
+            shared_features = self._get_trainable_extractor_results(image)
+        else:
+            shared_features = self._extractor(image, training=training)
         anchors = self._anchor_generator(self._anchor_base, self._extractor_stride,
                                          int(math.ceil(image_shape[0] / self._extractor_stride)),
                                          int(math.ceil(image_shape[1] / self._extractor_stride)))
-        rpn_score, rpn_bbox_txtytwth = self._rpn_head(shared_features, training=training)
-        # :147-151 (reshape / transpose / softmax / transpose / slice): the fg probabilities of the [A bg | A fg] layout
-        scores = ops.rpn_fg_softmax(rpn_score, self._num_anchors, ops.RPN_LAYOUT_FRCNN)
-        rois = self._rpn_proposal((rpn_bbox_txtytwth, anchors, scores, image_shape), training=training)
+        if training and self._train_rpn_head:
+            rpn_score, rpn_bbox_txtytwth = self._get_trainable_rpn_head_results(shared_features)
+        else:
+            rpn_score, rpn_bbox_txtytwth = self._rpn_head(shared_features, training=training)
+        with torch.no_grad():
+            # :147-151 (reshape / transpose / softmax / transpose / slice): the fg probabilities of the [A bg | A fg] layout
+            scores = ops.rpn_fg_softmax(rpn_score.detach(), self._num_anchors, ops.RPN_LAYOUT_FRCNN)
+            rois = self._rpn_proposal((rpn_bbox_txtytwth.detach(), anchors, scores, image_shape), training=training)
         return image_shape, shared_features, anchors, rpn_score, rpn_bbox_txtytwth, rois
+
+    def _get_trainable_extractor_results(self, image):
+        """_extractor with a graph into its trainable layers, bit-equal to it"""
+        raise NotImplementedError('train_extractor=True needs a dense part with a trainable extractor')
+
+    def _get_trainable_rpn_head_results(self, shared_features):
+        """_rpn_head with a graph into the RpnHead's layers: ([-1, 2A], [-1, 4]), bit-equal to it"""
+        raise NotImplementedError('train_rpn_head=True needs a dense part with a trainable RPN head')
+
+    def _get_trainable_roi_head(self):
+        """_roi_head with a graph into the RoI head's layers, as a callable on the RoI features"""
+        raise NotImplementedError('train_roi_head=True needs a dense part with a trainable RoI head')
+
+    def _training_roi_head(self, shared_features, rois, training):
+        """pooling + RoI head of both training branches: under no_grad, unless train_roi_head -- then the head runs its trainable
+        form outside it, so the two RoI losses carry a graph.  The pooling stays under no_grad as long as the shared map requires
+        no gradient (it does with train_extractor); when it does, the pooling layer takes its trainable form, the head's first
+        layer computes its input gradient and odet_roi_pool_backward carries it into the map."""
+        inputs = (shared_features, rois, self._extractor_stride)
+        if self._train_roi_head and shared_features.requires_grad:
+            return self._get_trainable_roi_head()(self._roi_pooling(inputs, training=training))
+        with torch.no_grad():
+            roi_features = self._roi_pooling(inputs, training=training)
+            if not self._train_roi_head:
+                return self._roi_head(roi_features, training=training)
+        return self._get_trainable_roi_head()(roi_features)
 
     @caller_range_checked
     def forward(self, inputs, training=None, mask=None):
@@ -122,7 +180,11 @@ class BaseFasterRcnn(torch.nn.Module):
         else:
             image = inputs
         image = _image_nhwc(image)
-        with torch.no_grad():
+        if training:
+            self._dropout_image_id = self._next_dropout_image_id
+            self._next_dropout_image_id += 1
+        # (no_grad around the whole front unless this call records a graph through the extractor or the RpnHead)
+        with contextlib.nullcontext() if self._trains_front(training) else torch.no_grad():
             image_shape, shared_features, anchors, rpn_score, rpn_bbox_txtytwth, rois = \
                 self._anchors_and_proposals(image, training)
         if training and self._training_losses == 'hip':
@@ -135,9 +197,7 @@ class BaseFasterRcnn(torch.nn.Module):
                                                             rpn_in_weights, rpn_out_weights)
             final_rois, roi_labels, roi_bbox_target, roi_in_weights, roi_out_weights = self._proposal_target(
                 (rois, gt_bboxes, gt_labels), training)
-            with torch.no_grad():
-                roi_features = self._roi_pooling((shared_features, final_rois, self._extractor_stride), training=training)
-                roi_score, roi_bboxes_txtytwth = self._roi_head(roi_features, training=training)
+            roi_score, roi_bboxes_txtytwth = self._training_roi_head(shared_features, final_rois, training)
             roi_cls_loss, roi_reg_loss = self._get_roi_loss(roi_score, roi_bboxes_txtytwth, roi_labels, roi_bbox_target,
                                                             roi_in_weights, roi_out_weights)
             return rpn_cls_loss, rpn_reg_loss, roi_cls_loss, roi_reg_loss
@@ -171,10 +231,7 @@ class BaseFasterRcnn(torch.nn.Module):
         proposal_targets = pt.batch(rois.reshape(1, -1, 4), gt_bboxes, gt_labels, off, first_image_id=pt._next_image_id,
                                     strict=False)
         pt._next_image_id += 1
-        with torch.no_grad():
-            roi_features = self._roi_pooling((shared_features, proposal_targets.final_rois[0], self._extractor_stride),
-                                             training=training)
-            roi_score, roi_bboxes_txtytwth = self._roi_head(roi_features, training=training)
+        roi_score, roi_bboxes_txtytwth = self._training_roi_head(shared_features, proposal_targets.final_rois[0], training)
         roi_cls_loss, roi_reg_loss = fused_roi_losses(roi_score.float()[None], roi_bboxes_txtytwth.float()[None],
                                                       proposal_targets, self._roi_sigma)
         return rpn_cls_loss[0], rpn_reg_loss[0], roi_cls_loss[0], roi_reg_loss[0]
@@ -229,6 +286,15 @@ class BaseFasterRcnn(torch.nn.Module):
         return torch.softmax(roi_score.float(), dim=-1), roi_bboxes_txtytwth.float(), rois / div
 
 
+def check_train_extractor(train_extractor, train_rpn_head, train_roi_head):
+    """train_extractor needs a trainable head: the shared map receives a gradient only through the RpnHead's input gradient or the
+    trainable RoI pooling"""
+    if train_extractor and not (train_rpn_head or train_roi_head):
+        raise ValueError('train_extractor=True needs train_rpn_head=True or train_roi_head=True: no gradient reaches the extractor '
+                         'otherwise')
+    return bool(train_extractor)
+
+
 def _features_nhwc(dense):
     """the detector's extractor output as the NHWC map RoiPoolingCropAndResize / RpnHead take"""
     def fn(image):
@@ -262,6 +328,13 @@ class _FrcnnFromDense(BaseFasterRcnn):
         out[1] = feat if feat.is_contiguous() else feat.contiguous()
         return tuple(out)
 
+    def _get_trainable_extractor_results(self, image):
+        return self._dense_ref.extractor_trainable(image)
+
+    def _get_trainable_rpn_head_results(self, shared_features):
+        scores, deltas = self._dense_ref.rpn_trainable(shared_features)
+        return scores.reshape(-1, 2 * self._num_anchors), deltas.reshape(-1, 4)
+
 
 _COMMON = dict(num_classes=21, weight_decay=0.0001, ratios=(0.5, 1.0, 2.0), scales=(8, 16, 32), extractor_stride=16,
                rpn_proposal_means=(0, 0, 0, 0), rpn_proposal_stds=(1.0, 1.0, 1.0, 1.0),
@@ -274,6 +347,7 @@ _COMMON = dict(num_classes=21, weight_decay=0.0001, ratios=(0.5, 1.0, 2.0), scal
                roi_training_max_pos_samples=32, prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3, training_targets='torch',
                training_losses='torch')
+_TRAIN_KEYWORDS = ('train_roi_head', 'train_rpn_head', 'train_extractor', 'dropout_seed')
 
 
 class ResNetFasterRcnn(_FrcnnFromDense):
@@ -283,10 +357,14 @@ class ResNetFasterRcnn(_FrcnnFromDense):
 
     def __init__(self, depth=50, roi_feature_size=(7, 7, 1024), dtype=torch.float32, device='cuda', f32_form='exact', **kwargs):
         from .frcnn_detector import ResNetC4Detector
-        from .fpn_detector import check_caller_f32_form
         check_caller_f32_form(f32_form)
         if depth not in [50, 101, 152]:
             raise ValueError('unknown resnet layers number {}'.format(depth))
+        asked = sorted(k for k in _TRAIN_KEYWORDS if k in kwargs)
+        if asked:
+            raise NotImplementedError('ResNetFasterRcnn: %s: the C4 model has no backward pass (its conv5 stack on the crops and '
+                                      'the global average pooling are not built); Vgg16FasterRcnn and ResnetV1Fpn train'
+                                      % ', '.join(asked))
         kw = dict(_COMMON)
         unknown = set(kwargs) - set(kw)
         if unknown:
@@ -300,14 +378,28 @@ class ResNetFasterRcnn(_FrcnnFromDense):
 
 
 class Vgg16FasterRcnn(_FrcnnFromDense):
-    """reference vgg16_faster_rcnn.py:11-115: Vgg16Extractor (:260-342) + Vgg16RoiHead (:178-257; dropout is identity at
-    inference).  `slim_ckpt_file_path` must be None: no checkpoint exists offline (random initialisation)."""
+    """reference vgg16_faster_rcnn.py:11-115: Vgg16Extractor (:260-342) + Vgg16RoiHead (:178-257).  `slim_ckpt_file_path` must be
+    None: no checkpoint exists offline (random initialisation).  `train_roi_head`, `train_rpn_head`, `train_extractor` (float32,
+    f32_form 'exact'; the module docstring): with all three `sum(losses).backward()` fills the 32 parameters the reference trains
+    -- block3_conv1 .. block5_conv3, the RpnHead, fc1, fc2, score, bbox -- and leaves the eight of blocks 1-2 (trainable=False,
+    :265-288) alone.  `roi_head_keep_dropout_rate` is the keep probability of the head's two dropouts (:250-253): active in a
+    training call with `train_roi_head`, identity everywhere else; their masks come from `dropout_seed` and a per-call image id
+    (ops.dropout)."""
 
     def __init__(self, slim_ckpt_file_path=None, roi_head_keep_dropout_rate=0.5, roi_feature_size=(7, 7, 512),
-                 dtype=torch.float32, device='cuda', f32_form='exact', **kwargs):
+                 dtype=torch.float32, device='cuda', f32_form='exact', train_roi_head=False, train_rpn_head=False,
+                 train_extractor=False, dropout_seed=0, **kwargs):
         from .frcnn_detector import Vgg16Detector
-        from .fpn_detector import check_caller_f32_form
         check_caller_f32_form(f32_form)
+        for on, name, what in ((train_extractor, 'train_extractor', 'the convolution and pooling backward have'),
+                               (train_roi_head, 'train_roi_head', 'the Dense backward has'),
+                               (train_rpn_head, 'train_rpn_head', 'the convolution backward has')):
+            if on and (dtype != torch.float32 or f32_form != 'exact'):
+                raise ValueError("Vgg16FasterRcnn: %s=True needs dtype=torch.float32 and f32_form='exact' (%s no float16 or "
+                                 "split-precision form), got %s, %r" % (name, what, dtype, f32_form))
+        check_train_extractor(train_extractor, train_rpn_head, train_roi_head)
+        if train_roi_head and not 0.0 < float(roi_head_keep_dropout_rate) <= 1.0:
+            raise ValueError('Vgg16FasterRcnn: roi_head_keep_dropout_rate must be in (0, 1], got %r' % (roi_head_keep_dropout_rate,))
         if slim_ckpt_file_path is not None:
             raise ValueError('Vgg16FasterRcnn: checkpoint import is out of scope (SURVEY section 2); weights are random')
         kw = dict(_COMMON)
@@ -315,8 +407,15 @@ class Vgg16FasterRcnn(_FrcnnFromDense):
         if unknown:
             raise TypeError('unexpected keyword argument(s) %s' % sorted(unknown))
         kw.update(kwargs)
+        self._train_roi_head, self._train_rpn_head = bool(train_roi_head), bool(train_rpn_head)
+        self._train_extractor = bool(train_extractor)
         self._roi_head_keep_dropout_rate = roi_head_keep_dropout_rate
+        self._dropout_seed = int(dropout_seed)
         self._roi_feature_size = roi_feature_size
         if len(kw['ratios']) * len(kw['scales']) != 9 or kw['extractor_stride'] != 16:
             raise ValueError('Vgg16FasterRcnn: the dense kernels are built for 9 anchors per cell at stride 16')
         self._init_with_dense(Vgg16Detector(kw['num_classes'], (64, 64), 1, dtype=dtype, f32_form=f32_form), dtype, device, kw)
+
+    def _get_trainable_roi_head(self):
+        keep, seed, image_id = self._roi_head_keep_dropout_rate, self._dropout_seed, self._dropout_image_id
+        return lambda roi_features: self._dense_ref.roi_head_trainable(roi_features, keep, seed, image_id)

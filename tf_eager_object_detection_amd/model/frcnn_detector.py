@@ -163,7 +163,7 @@ class ResNetC4Detector(Detector):
 
 
 class Vgg16Detector(ResNetC4Detector):
-    """Inference-only VGG16 Faster R-CNN -- counterpart of model/faster_rcnn/vgg16_faster_rcnn.py
+    """VGG16 Faster R-CNN (inference pass: detector_base.Detector; trainable parts: model/vgg_trainable.py) -- counterpart of model/faster_rcnn/vgg16_faster_rcnn.py
     (Vgg16Extractor :260-342: 13 3x3 'same' convolutions + ReLU, four 2x2/2 'same' max-pools, stride 16;
     Vgg16RoiHead :178-257: flatten(7,7,512) -> fc 4096 -> fc 4096 -> score / boxes) around FrcnnHotPath
     (14x14 crop + 2x2 max on 512 channels).  BASELINE config "VGG16 Faster R-CNN, 1x3x600x800"."""
@@ -197,9 +197,8 @@ class Vgg16Detector(ResNetC4Detector):
         self._declare_hot_path(512, num_proposals, max_batch, hot_kwargs, pool_size=7, max_pooling_flag=True)
         self._roi_chunk = 0
 
-    @_in_f32_form
-    def features(self, images_nhwc):
-        """[B,H,W,3] -> conv5_3 [B,512,ceil(H/16),ceil(W/16)] channels_last."""
+    def _first_conv(self, images_nhwc):
+        """conv1_1 + ReLU from the image, channels_last"""
         first = self.convs[0]
         if not images_nhwc.is_cuda or not images_nhwc.is_contiguous() or first.out_channels != 64:
             raise _no_kernel('first convolution', first, images_nhwc)
@@ -214,19 +213,55 @@ class Vgg16Detector(ResNetC4Detector):
             x = _patch_gemm(images_nhwc, Hn * Wn * 64 * 4, ops.rgb_patches3x3_f32, w, first.bias, True)
         else:
             raise _no_kernel('first convolution', first, images_nhwc)
-        i = 0
+        return x
+
+    def _layer_plan(self):
+        """(index into convs, pooled) of the convolutions after conv1_1; pooled: a stage's last convolution, with
+        MaxPooling2D((2,2), 2, padding='same') behind it (blocks 1-4)"""
+        plan, i = [], 0
         for bi, (_, n) in enumerate(self._CFG):
             for k in range(n):
-                if i == 0:                                    # (conv1_1: above)
-                    i += 1
-                    continue
-                if k == n - 1 and bi < 4:
-                    # the stage's last convolution: bias + ReLU + MaxPooling2D((2,2), 2, padding='same') in one pass
-                    x = _conv_relu_pool(self.convs[i], x, 2, 2, ceil_mode=True)
-                else:
-                    x = _conv_epi(self.convs[i], x, relu=True)
+                if i:
+                    plan.append((i, k == n - 1 and bi < 4))
                 i += 1
+        return plan
+
+    def _layer(self, i, pooled, x):
+        if pooled:
+            # the stage's last convolution: bias + ReLU + MaxPooling2D((2,2), 2, padding='same') in one pass
+            return _conv_relu_pool(self.convs[i], x, 2, 2, ceil_mode=True)
+        return _conv_epi(self.convs[i], x, relu=True)
+
+    @_in_f32_form
+    def features(self, images_nhwc):
+        """[B,H,W,3] -> conv5_3 [B,512,ceil(H/16),ceil(W/16)] channels_last."""
+        x = self._first_conv(images_nhwc)
+        for i, pooled in self._layer_plan():
+            x = self._layer(i, pooled, x)
         return x
+
+    @_in_f32_form
+    def extractor_trainable(self, images_nhwc):
+        """features with a backward pass into block3_conv1 .. block5_conv3 (float32, f32_form 'exact'; model/vgg_trainable.py):
+        the output bit-equal to features()'s with its shape and strides; blocks 1-2 run under no_grad and stay frozen"""
+        from .vgg_trainable import extractor_trainable
+        return extractor_trainable(self, images_nhwc)
+
+    @_in_f32_form
+    def rpn_trainable(self, c):
+        """rpn with a backward pass into rpn_conv, rpn_score and rpn_bbox (float32, f32_form 'exact'; model/rpn_trainable.py on
+        the one level): outputs bit-equal to rpn()'s with its shapes, and a gradient into ``c`` when it requires one"""
+        from .rpn_trainable import rpn_trainable
+        scores, deltas = rpn_trainable(self, [c])
+        return scores.view(scores.shape[0], -1, 2 * self.A), deltas        # ([B,n,2] and [B,fh*fw,2A] are the same memory)
+
+    @_in_f32_form
+    def roi_head_trainable(self, roi_features, keep_prob=1.0, seed=0, image_id=0):
+        """roi_head with a backward pass into fc1, fc2, score and bbox and the reference's two dropouts (float32, f32_form 'exact';
+        model/vgg_trainable.py): fc1 -> dropout (stream 6) -> fc2 -> dropout (stream 7) -> score / bbox; with keep_prob 1 the
+        outputs are bit-equal to roi_head's"""
+        from .vgg_trainable import roi_head_trainable
+        return roi_head_trainable(self, roi_features, keep_prob, seed, image_id)
 
     def head_activation(self, roi_features):
         x = roi_features.reshape(roi_features.shape[0], -1).to(self.dtype)        # Flatten() of NHWC crops

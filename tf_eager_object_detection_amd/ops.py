@@ -633,6 +633,98 @@ def block_input_grad(d1, dy=None, y=None, d2=None, stride=1, in_hw=None, out=Non
     return out
 
 
+def _vgg_grad_f32(who, what, named):
+    """the checks relu_maxpool2_backward / dropout share (the style of _conv_grad_maps): float32 only, the exact form only,
+    contiguous tensors; the caller checks the shapes, then _conv_grad_on_gpu"""
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError('%s: %s must be a float32 tensor (the %s has no float16 form), got %s'
+                             % (who, name, what, getattr(t, 'dtype', type(t).__name__)))
+    if current_f32_form() != 'exact':
+        raise ValueError("%s: the %s runs only under f32_form 'exact' (no split-precision backward), not %r"
+                         % (who, what, current_f32_form()))
+    for name, t in named:
+        if not t.is_contiguous():
+            raise ValueError('%s: %s must be contiguous' % (who, name))
+
+
+def relu_maxpool2_backward(z, bias, dpool, out=None):
+    """The backward of bias_relu_maxpool(z, bias, 2, 2, 0, ceil_mode=True) in one launch (odet_relu_maxpool2_backward_f32): TF's
+    MaxPoolGrad then ReluGrad of MaxPooling2D((2,2), 2, 'same') after a ReLU convolution (vgg16_faster_rcnn.py:307, 325).  ``z``
+    [B,H,W,C] (the convolution's raw output, without bias), ``bias`` [C], ``dpool`` [B,ceil(H/2),ceil(W/2),C] -> dz [B,H,W,C]:
+    dpool at the first position of each window that holds its maximum of max(z + bias, 0) when that is > 0, +0 elsewhere.
+    Contiguous NHWC float32 GPU tensors, C % 4 == 0.  float32, f32_form 'exact' only."""
+    who = 'relu_maxpool2_backward'
+    named = [('z', z), ('bias', bias), ('dpool', dpool)]
+    _vgg_grad_f32(who, 'max-pooling backward', named)
+    if z.dim() != 4 or int(z.shape[1]) < 1 or int(z.shape[2]) < 1 or int(z.shape[3]) < 4 or int(z.shape[3]) % 4:
+        raise ValueError('%s: z %s must be an NHWC tensor [B,H,W,C] with a positive map size and C a positive multiple of 4'
+                         % (who, tuple(z.shape)))
+    B, H, W, Cc = (int(v) for v in z.shape)
+    if tuple(bias.shape) != (Cc,):
+        raise ValueError('%s: bias %s does not go with z %s' % (who, tuple(bias.shape), tuple(z.shape)))
+    if tuple(dpool.shape) != (B, (H + 1) // 2, (W + 1) // 2, Cc):
+        raise ValueError('%s: dpool %s does not go with z %s (the pooled map is %s)'
+                         % (who, tuple(dpool.shape), tuple(z.shape), (B, (H + 1) // 2, (W + 1) // 2, Cc)))
+    _conv_grad_on_gpu(who, named)
+    out = _out(out, (B, H, W, Cc), torch.float32, z.device)
+    L.call('odet_relu_maxpool2_backward_f32', L.dptr(z), L.dptr(bias), L.dptr(dpool), L.dptr(out), B, H, W, Cc, L.stream())
+    return out
+
+
+DROPOUT_STREAM_FC1, DROPOUT_STREAM_FC2 = 6, 7           # the Philox streams of the RoI head's two dropouts (0-5: include/odet.h)
+
+
+def _dropout(sym, who, x, keep_prob, seed, image_id, stream_id, out):
+    _vgg_grad_f32(who, 'dropout', [('x' if sym == 'odet_dropout_f32' else 'dy', x)])
+    keep_prob = float(keep_prob)
+    if not 0.0 < keep_prob <= 1.0:
+        raise ValueError('%s: keep_prob must be in (0, 1], got %r' % (who, keep_prob))
+    seed, image_id, stream_id = int(seed), int(image_id), int(stream_id)
+    if not 0 <= seed < 1 << 64 or not 0 <= stream_id < 1 << 32:
+        raise ValueError('%s: seed must be in [0, 2^64) and stream_id in [0, 2^32), got %d, %d' % (who, seed, stream_id))
+    _conv_grad_on_gpu(who, [('x', x)])
+    out = _out(out, tuple(x.shape), torch.float32, x.device)
+    L.call(sym, L.dptr(x), L.dptr(out), x.numel(), keep_prob, seed, image_id & 0xFFFFFFFF, stream_id, L.stream())
+    return out
+
+
+def dropout(x, keep_prob, seed, image_id, stream_id, out=None):
+    """tf.nn.dropout(x, keep_prob) of TF r1.13 with the counter-based rule in place of TF's generator (odet_dropout_f32;
+    vgg16_faster_rcnn.py:250-253): y = (x / keep_prob) * keep, keep = floor(keep_prob + u) with u from word e & 3 of
+    philox((e >> 2, image_id, stream_id, 0), seed) for the flat element e.  ``x``: a contiguous float32 GPU tensor of any shape;
+    keep_prob in (0, 1] (1: a copy); stream 6 is the dropout after fc1, 7 the one after fc2.  float32, f32_form 'exact' only."""
+    return _dropout('odet_dropout_f32', 'dropout', x, keep_prob, seed, image_id, stream_id, out)
+
+
+def dropout_backward(dy, keep_prob, seed, image_id, stream_id, out=None):
+    """dropout's backward (odet_dropout_backward_f32): dx = (dy * keep) / keep_prob, the mask recomputed from the same counters"""
+    return _dropout('odet_dropout_backward_f32', 'dropout_backward', dy, keep_prob, seed, image_id, stream_id, out)
+
+
+class _DropoutTrainable(torch.autograd.Function):
+    """ops.dropout forward, ops.dropout_backward backward; nothing is saved but the counters"""
+
+    @staticmethod
+    def forward(ctx, x, keep_prob, seed, image_id, stream_id):
+        ctx.args = (keep_prob, seed, image_id, stream_id)
+        return dropout(x, keep_prob, seed, image_id, stream_id)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        return dropout_backward(dy if dy.is_contiguous() else dy.contiguous(), *ctx.args), None, None, None, None
+
+
+def dropout_trainable(x, keep_prob, seed, image_id, stream_id):
+    """ops.dropout with a backward pass (float32, f32_form 'exact'): the forward is `dropout`, bit for bit.  keep_prob == 1 returns
+    ``x`` itself, as tf.nn.dropout does."""
+    if float(keep_prob) == 1.0:
+        return x
+    return _DropoutTrainable.apply(x if x.is_contiguous() else x.contiguous(), float(keep_prob), int(seed), int(image_id),
+                                   int(stream_id))
+
+
 def bias_act_(x, bias, residual=None, relu=True):
     """In place on an NHWC (or any [..., C] contiguous) activation: x = relu?((x + bias) (+ residual)) -- the
     convolution epilogue of the reference's ResNet blocks / RPN head (resnet_fpn.py:154-205) in one pass."""
@@ -1231,6 +1323,7 @@ class _Conv3x3Trainable(torch.autograd.Function):
     def forward(ctx, weight, bias, relu, *xs):
         ys = conv3x3_f32_levels(list(xs), weight, bias, relu)
         ctx.relu, ctx.has_bias, ctx.n = bool(relu), bias is not None, len(xs)
+        ctx.flipped = None                                   # (conv3x3_trainable_levels hangs a caller's cached one on the node)
         ctx.save_for_backward(weight, *xs, *(ys if relu else ()))
         return tuple(ys)
 
@@ -1248,7 +1341,7 @@ class _Conv3x3Trainable(torch.autograd.Function):
             dw = _conv3x3_weight_grad(dw, weight) if ctx.needs_input_grad[0] else None
         if any(ctx.needs_input_grad[3:]):
             dzs = dys if ys is None else [torch.where(y > 0, d, torch.zeros_like(d)) for y, d in zip(ys, dys)]
-            got = conv3x3_dgrad_f32_levels(dzs, weight)
+            got = conv3x3_dgrad_f32_levels(dzs, weight, flipped=ctx.flipped)
             dxs = [g if need else None for g, need in zip(got, ctx.needs_input_grad[3:])]
         return (dw, db, None) + tuple(dxs)
 
@@ -1274,16 +1367,66 @@ def _conv3x3_weight_grad(dw, weight):
     return g.contiguous()
 
 
-def conv3x3_trainable_levels(xs, weight, bias, relu=False):
+def conv3x3_trainable_levels(xs, weight, bias, relu=False, flipped=None):
     """ops.conv3x3_f32_levels with a backward pass (float32, f32_form 'exact'): the forward is conv3x3_f32_levels, bit for bit;
     `.backward()` leaves weight.grad in the parameter's own shape and memory format and bias.grad [cout], from ONE wgrad launch
-    over all levels (plus its reduce and bias launches), and computes input gradients only when a map requires one."""
+    over all levels (plus its reduce and bias launches), and computes input gradients only when a map requires one (``flipped``: a
+    caller's cached conv3x3_flipped_weight for them; without it the backward pass flips the weight itself)."""
     if current_f32_form() != 'exact':
         raise ValueError("conv3x3_trainable_levels: the convolution backward runs only under f32_form 'exact', not %r"
                          % current_f32_form())
     if weight.dtype != torch.float32 or any(x.dtype != torch.float32 for x in xs):
         raise ValueError('conv3x3_trainable_levels: maps and weight must be float32 (the convolution backward has no float16 form)')
-    return list(_Conv3x3Trainable.apply(weight, bias, bool(relu), *[x if x.is_contiguous() else x.contiguous() for x in xs]))
+    ys = list(_Conv3x3Trainable.apply(weight, bias, bool(relu), *[x if x.is_contiguous() else x.contiguous() for x in xs]))
+    if flipped is not None and ys[0].grad_fn is not None:
+        ys[0].grad_fn.flipped = flipped                      # (the node IS the ctx that backward receives)
+    return ys
+
+
+class _Conv3x3ReluPoolTrainable(torch.autograd.Function):
+    """conv3x3_f32 without its epilogue, then bias_relu_maxpool (2x2 / 2, ceil mode) forward; relu_maxpool2_backward, then one
+    odet_conv3x3_wgrad_f32_levels on the gated gradient (and, only when the input needs a gradient, the forward kernel on the
+    flipped weight) backward"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, flipped):
+        z = conv3x3_f32(x, weight)
+        ctx.save_for_backward(x, z, bias, weight, flipped)
+        return bias_relu_maxpool(z, bias, 2, 2, 0, True)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dpool):
+        x, z, bias, weight, flipped = ctx.saved_tensors
+        dz = relu_maxpool2_backward(z, bias, dpool if dpool.is_contiguous() else dpool.contiguous())
+        dx = dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, db = conv3x3_wgrad_f32_levels([x], [dz], with_bias=ctx.needs_input_grad[2])      # (dz is gated: no y_relus)
+            dw = _conv3x3_weight_grad(dw, weight) if ctx.needs_input_grad[1] else None
+        if ctx.needs_input_grad[0]:
+            dx = conv3x3_dgrad_f32_levels([dz], weight, flipped=flipped)[0]
+        return dx, dw, db, None
+
+
+def conv3x3_relu_pool_trainable(x, weight, bias, flipped=None):
+    """max_pool(relu(conv3x3(x) + bias)) with MaxPooling2D((2,2), 2, 'same') and a backward pass (float32, f32_form 'exact';
+    vgg16_faster_rcnn.py:300-325: a stage's last convolution and its pooling): the forward is conv3x3_f32 without its epilogue, then
+    bias_relu_maxpool -- the detectors' float32 launches, bit for bit; `.backward()` leaves weight.grad in the parameter's own
+    shape and memory format and bias.grad [cout], and computes the input gradient only when ``x`` requires one (``flipped``: a
+    caller's cached conv3x3_flipped_weight).  ``x`` [B,H,W,cin] contiguous NHWC -> [B,ceil(H/2),ceil(W/2),cout]."""
+    who = 'conv3x3_relu_pool_trainable'
+    _vgg_grad_f32(who, 'convolution backward', [('x', x), ('bias', bias)])
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32:       # (channels_last or contiguous: _conv3x3_weight)
+        raise ValueError('%s: weight must be a float32 tensor (the convolution backward has no float16 form), got %s'
+                         % (who, getattr(weight, 'dtype', type(weight).__name__)))
+    if x.dim() != 4 or weight.dim() != 4:
+        raise ValueError('%s: x must be an NHWC tensor [B,H,W,cin] and weight [cout,cin,3,3] or [cout,3,3,cin]' % who)
+    cin, cout = int(x.shape[3]), int(weight.shape[0])
+    if cin % 32 or cout % 64 or weight.numel() != cout * 9 * cin or tuple(bias.shape) != (cout,):
+        raise ValueError('%s: cin %d must be a multiple of 32 and cout %d one of 64, weight %s and bias %s must go with them'
+                         % (who, cin, cout, tuple(weight.shape), tuple(bias.shape)))
+    _conv_grad_on_gpu(who, [('x', x), ('weight', weight), ('bias', bias)])
+    return _Conv3x3ReluPoolTrainable.apply(x, weight, bias, flipped)
 
 
 def rpn_unpack_pair(d_scores, d_deltas, num_anchors, pixels, anchor_offset, out):
