@@ -4,24 +4,33 @@
 // iteration dispatches ~12 TF ops, one single-threaded NMS and one device->host sync
 // (prediction.py:147).  Here the whole function is ONE launch, a workgroup per class:
 //
-//   k_postops (grid = num_classes-1 x images, 1024 threads):
-//     1. score filter (strict >, :136), decode (:138-140), clip + min-edge filter (:141-143): one
-//        RoI per thread, box kept in LDS, 64-bit sort key (score desc, RoI index asc)
-//     2. bitonic sort of the keys: one key per thread, compare-exchange distances < 64 by wave
-//        shuffles, only the 10 stages with distance >= 64 go through LDS (more than 1024 RoIs:
-//        plain LDS bitonic)
-//     3. exact greedy NMS (:146) in rounds of 128 sorted candidates: all 16 waves build the
-//        128 x 128 lower-triangular suppression bit matrix (and test the round against the boxes
-//        kept by earlier rounds), then wave 0 resolves the two 64-blocks with ctz over the alive
-//        ballot; stops at max_per_class or when the candidates are exhausted.
-//     4. the class's list is published (release fence, then a ticket on a wrapping counter in the
+//   k_postops (grid = num_classes-1 x images, PO_THREADS threads).  Greedy NMS (:146) visits the rows that pass the
+//   filters in (score desc, row asc) order and needs nothing past the row at which the max_per_class-th box is
+//   kept; a row that fails the min-edge filter is just skipped in that sequence.  So the rows are ordered by score
+//   FIRST, and decoded, clipped and filtered only a batch of PO_ROUND at a time, as far as the walk gets:
+//     1. the 32-bit order key of every row (score filter, strict >, :136; device-side row count) into LDS.
+//        Nothing else is loaded here.
+//     2. the next PO_ROUND best untaken rows: radix select of the PO_ROUND-th best key among the untaken ones
+//        (po_radix_select, shared with the merge), ties at that key in row order (one block scan), the selected
+//        rows compacted in row order, marked taken, and ranked among themselves by (key, row) -- exactly the next
+//        PO_ROUND positions of the full sort.  Fewer rows left than a batch: all of them, no select.
+//     3. decode (:138-140), clip + min-edge filter (:141-143) of the batch's rows only, each written at its rank;
+//        a row under the min edge stays in the round as a dead candidate.
+//     4. one round of the exact greedy NMS over the batch: all waves build the PO_ROUND x PO_ROUND
+//        lower-triangular suppression bit matrix (and test the round against the boxes kept by earlier rounds),
+//        then wave 0 resolves the 64-blocks with ctz over the alive ballot.
+//     5. back to 2 until max_per_class boxes are kept or no untaken row is left.
+//     6. the class's list is published (release fence, then a ticket on a wrapping counter in the
 //        workspace); the workgroup that draws the LAST ticket of its image merges: concatenation in
 //        class order (:156-158), top-k by (score desc, position asc) (:160), gather (:162), and
-//        optionally the fixed-size detection record of the image-parallel all-gather.  The class
-//        lists are sorted already, so the merge RANKS instead of sorting again: the rank of an entry
-//        is the number of entries before it in (score desc, position asc) order = one binary search
-//        per class list.  (Until round 4 the merge was a second launch with a second 1024-key
-//        sort: 20.4 + 11.6 us per image in the latency arrangement.)
+//        optionally the fixed-size detection record of the image-parallel all-gather.  No second
+//        sort: the merge selects the max_per_image-th key with the same po_radix_select and ranks
+//        only the selected entries (postops_merge).  (Until round 4 the merge was a second launch
+//        with a second 1024-key sort: 20.4 + 11.6 us per image in the latency arrangement.)
+//
+// Until the lazy form every row that passed the score filter was decoded (two float64 exp each), and all of
+// them went through a 1024-key bitonic sort in a 1024-thread workgroup with 36 KB of LDS, although the walk
+// of the benchmark's classes ends after 50-52 candidates (tests/postops_depth.py prints the depths).
 //
 // Output order is the sorted order, one valid instance of tf.nn.top_k(sorted=False)'s
 // unspecified order.
@@ -29,23 +38,28 @@
 
 #include "odet_internal.h"
 
-#define PO_THREADS 1024
-#define PO_ROUND 128          // candidates per NMS round
+// Workgroup size and batch = NMS round size (profiles/postops_lazy.json has the measured alternatives).
+#ifndef PO_THREADS
+#define PO_THREADS 512
+#endif
+#ifndef PO_ROUND
+#define PO_ROUND 64           // candidates per batch = per NMS round
+#endif
+#define PO_SLICES (PO_THREADS / PO_ROUND)   // threads per candidate row in the pair tests
+#define PO_COLS (PO_ROUND / PO_SLICES)      // columns of the round's triangle per thread
+#define PO_WORDS (PO_ROUND / 64)            // 64-bit words of a row's suppression mask
+#define PO_INVALID 0xFFFFFFFFu              // order key of a row that does not take part (no score maps to it: it would be -NaN)
+static_assert((PO_THREADS == 256 || PO_THREADS == 512) && (PO_ROUND == 64 || PO_ROUND == 128), "k_postops: unsupported shape");
+static_assert(PO_COLS == 8 || PO_COLS == 16 || PO_COLS == 32 || PO_COLS == 64, "k_postops: mask pieces are 1, 2, 4 or 8 bytes");
 
 typedef unsigned long long u64;
-
-static int next_pow2_(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
 
 struct PostOpsParams {    // pointer tables: one entry per image of the batch (blockIdx.y)
   PerImg<const float*> scores_t;     // [R, Ccls]
   PerImg<const float*> deltas_t;     // [R, Ccls, 4]
   PerImg<const float4*> rois_t;      // [R]
   PerImg<const int32_t*> count_dev_t;
-  int R, Ccls, P2, K;
+  int R, Ccls, K;
   float means[4], stds[4];
   float wmax, hmax, min_edge, score_thr, nms_thr;
   float roi_div;         // rois are divided by this first (im_detect's rois / img_scale); 1 = as they are
@@ -70,6 +84,47 @@ __device__ __forceinline__ float key_to_score(uint32_t k) {   // inverse of ~d_f
   return __uint_as_float(u);
 }
 
+// The M-th best (smallest) of the keys != PO_INVALID in key[0, n), 1 <= M <= their number, by four 8-bit radix passes from
+// the top.  Each pass has a histogram of its own (hist: [4][256], 16-byte aligned, zeroed here) and ONE barrier: every wave
+// scans the 256 counts for itself, so the running prefix and target stay in registers.  Returns that key T; *ties = how many
+// of the keys == T belong to the best M (the caller takes them in position order).  key[] stores made before the call are
+// covered by the barrier behind the zeroing; between two calls the caller has a barrier (hist is reused).
+__device__ __forceinline__ uint32_t po_radix_select(const uint32_t* key, int n, int M, uint32_t* hist, uint32_t* ties) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (int i = tid; i < 4 * 256; i += PO_THREADS) hist[i] = 0u;
+  __syncthreads();
+  uint32_t prefix = 0u;
+  int tgt = M;
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    uint32_t* h = hist + pass * 256;
+    const uint32_t himask = pass == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
+    for (int i = tid; i < n; i += PO_THREADS) {
+      const uint32_t k = key[i];
+      if (k != PO_INVALID && (k & himask) == prefix) atomicAdd(&h[(k >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    const uint4 hv = reinterpret_cast<const uint4*>(h)[lane];
+    const uint32_t hh[4] = {hv.x, hv.y, hv.z, hv.w};
+    const int sum = (int)(hv.x + hv.y + hv.z + hv.w);
+    const int inc = wave_incl_scan(sum);
+    const bool hit = sum > 0 && inc - sum < tgt && tgt <= inc;     // (exactly one lane)
+    int run = inc - sum, nt = tgt;
+    uint32_t d = 4 * lane;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (run < tgt && tgt <= run + (int)hh[j]) { d = 4 * lane + j; nt = tgt - run; }
+      run += (int)hh[j];
+    }
+    const u64 bal = __ballot(hit);
+    const int src = bal ? __builtin_ctzll(bal) : 0;
+    prefix |= (uint32_t)__shfl((int)d, src) << shift;
+    tgt = __shfl(nt, src);
+  }
+  *ties = (uint32_t)tgt;
+  return prefix;
+}
+
 struct MergeView {        // one image's pointers
   const int32_t* cls_count; const float4* cls_boxes; const float* cls_scores;
   int ncls1, K, max_per_image, mode;
@@ -78,20 +133,19 @@ struct MergeView {        // one image's pointers
 
 // The merge of the class lists of one image by ONE workgroup (the last class workgroup to finish): concatenation in class
 // order, the max_per_image best by (score desc, position asc).  No second sort: the M-th best order key is found by a
-// radix SELECT over the <= 8192 keys (four 8-bit passes on an LDS histogram), ties at that key are taken in position
+// radix SELECT over the <= 8192 keys (po_radix_select: four 8-bit passes on LDS histograms), ties at that key are taken in position
 // order (a block scan: threads hold consecutive slots), and only the <= M selected entries are ranked, among themselves.
 // (Measured on the way, latency arrangement: ranking all entries by one binary search per class list 13.5 us -- a chain of
 // dependent LDS reads --, the second 1024-key bitonic sort of the old merge launch 11.6 us for the whole launch.)
-// LDS: key [nslots] | hist [256] | sel_key [max_per_image] | sel_slot [max_per_image].
+// LDS: key [nslots, rounded up to 4] | hist [4][256] | sel_key | sel_slot [min(max_per_image, nslots)].
 __device__ void postops_merge(const MergeView& p, unsigned char* smem) {
   uint32_t* key = reinterpret_cast<uint32_t*>(smem);            // ~asc key of an entry's score: smaller = better
   const int nslots = p.ncls1 * p.K;
-  uint32_t* hist = key + nslots;
-  uint32_t* sel_key = hist + 256;
-  uint32_t* sel_slot = sel_key + (p.max_per_image > 0 ? p.max_per_image : 1);
-  __shared__ uint32_t s_prefix, s_target, s_total;
+  uint32_t* hist = key + ((nslots + 3) & ~3);
+  uint32_t* sel_key = hist + 4 * 256;
+  uint32_t* sel_slot = sel_key + max(min(p.max_per_image, nslots), 1);   // (M <= min(max_per_image, nslots) entries are selected)
   __shared__ int lds17[17];
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x;
   const int per = (nslots + PO_THREADS - 1) / PO_THREADS;       // consecutive slots per thread (slot order = position order)
   const int lo = tid * per;
   // every entry's key and validity in ONE round trip (the class's count is read beside the score, not before it)
@@ -112,48 +166,10 @@ __device__ void postops_merge(const MergeView& p, unsigned char* smem) {
   // below is `key != 0xFFFFFFFF`
   const int M = (p.mode == 1) ? ((p.max_per_image > 0 && total > p.max_per_image) ? p.max_per_image : total)
                               : min(total, p.max_per_image);                                // prediction.py:160
-  // ---- the M-th best key T (1 <= M <= total), by four 8-bit radix passes from the top
-  uint32_t T = 0xFFFFFFFFu;
-  if (M > 0 && M < total) {
-    if (tid == 0) { s_prefix = 0u; s_target = (uint32_t)M; }
-    for (int pass = 0; pass < 4; ++pass) {
-      const int shift = 24 - 8 * pass;
-      if (tid < 256) hist[tid] = 0u;
-      __syncthreads();
-      const uint32_t prefix = s_prefix;
-      const uint32_t himask = pass == 0 ? 0u : (0xFFFFFFFFu << (shift + 8));
-      for (int q = 0; q < per; ++q) {
-        const int slot = lo + q;
-        if (slot < nslots) {
-          const uint32_t k = key[slot];
-          if (k != 0xFFFFFFFFu && (k & himask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
-        }
-      }
-      __syncthreads();
-      if (tid < 64) {
-        const uint32_t h0 = hist[4 * tid], h1 = hist[4 * tid + 1], h2 = hist[4 * tid + 2], h3 = hist[4 * tid + 3];
-        const int sum = (int)(h0 + h1 + h2 + h3);
-        const int inc = wave_incl_scan(sum);
-        const int tgt = (int)s_target;
-        const bool hit = sum > 0 && inc - sum < tgt && tgt <= inc;
-        const u64 bal = __ballot(hit);
-        if (bal && lane == __builtin_ctzll(bal)) {
-          int run = inc - sum;
-          uint32_t d = 4 * tid;
-          const uint32_t hh[4] = {h0, h1, h2, h3};
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (run < tgt && tgt <= run + (int)hh[j]) { d = 4 * tid + j; s_target = (uint32_t)(tgt - run); }
-            run += (int)hh[j];
-          }
-          s_prefix = prefix | (d << shift);
-        }
-      }
-      __syncthreads();
-    }
-    T = s_prefix;           // s_target = how many of the entries with key == T belong to the best M (in position order)
-  }
-  const uint32_t take_ties = (M > 0 && M < total) ? s_target : 0xFFFFFFFFu;
+  // ---- the M-th best key T (1 <= M < total); take_ties = how many of the entries with key == T belong to the best M (in
+  // position order)
+  uint32_t T = PO_INVALID, take_ties = PO_INVALID;
+  if (M > 0 && M < total) T = po_radix_select(key, nslots, M, hist, &take_ties);
   __syncthreads();
   if (p.mode == 1) {
     // evaluation/pascal_eval_files_utils.py:99-106: when more than max_per_image detections survive,
@@ -248,34 +264,106 @@ __global__ void __launch_bounds__(PO_THREADS) k_postops(PostOpsParams p) {
   int32_t* __restrict__ cls_count = p.cls_count_t.v[img];
   float4* __restrict__ cls_boxes = p.cls_boxes_t.v[img];
   float* __restrict__ cls_scores = p.cls_scores_t.v[img];
-  // layout: keys [max(P2, 2048)] u64 | lbox [R] float4 | sbox [PO_ROUND] float4 | sarea [PO_ROUND] |
-  //         kbox [K] float4 | karea [K] float | mask [PO_ROUND][2] u64 | crossf [PO_ROUND] u32
-  const int nkeys = p.P2 > 2048 ? p.P2 : 2048;
-  u64* keys = reinterpret_cast<u64*>(smem);
-  float4* lbox = reinterpret_cast<float4*>(keys + nkeys);
-  float4* sbox = lbox + p.R;
-  float4* kbox = sbox + PO_ROUND;
+  // layout (po_class_lds_bytes): sbox | obox [PO_ROUND] float4 | kbox [K] float4 | mask [PO_ROUND][PO_WORDS] u64 |
+  //         hist [4][256] u32 | key [R] u32 | bkey | brow | skey | crossf [PO_ROUND] u32 | sarea [PO_ROUND] | karea [K] float
+  float4* sbox = reinterpret_cast<float4*>(smem);     // the round's boxes in rank order, corner-normalised
+  float4* obox = sbox + PO_ROUND;                     // ... and as decoded (what is published)
+  float4* kbox = obox + PO_ROUND;
   u64* mask = reinterpret_cast<u64*>(kbox + p.K);
-  float* sarea = reinterpret_cast<float*>(mask + PO_ROUND * 2);
+  uint32_t* hist = reinterpret_cast<uint32_t*>(mask + PO_ROUND * PO_WORDS);
+  uint32_t* key = hist + 4 * 256;                     // order key per row; PO_INVALID: filtered out, or taken by a batch
+  uint32_t* bkey = key + p.R;                         // the batch in row order: key,
+  uint32_t* brow = bkey + PO_ROUND;                   // row
+  uint32_t* skey = brow + PO_ROUND;                   // the batch's keys in rank order
+  uint32_t* crossf = skey + PO_ROUND;                 // != 0: dead before the round's resolve
+  float* sarea = reinterpret_cast<float*>(crossf + PO_ROUND);
   float* karea = sarea + PO_ROUND;
-  uint32_t* crossf = reinterpret_cast<uint32_t*>(karea + p.K);
   __shared__ int s_nvalid, s_nk, s_last;
+  __shared__ int lds17[17];
 
   const int c = blockIdx.x + 1;   // class id, prediction.py:135
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   if (tid == 0) { s_nvalid = 0; s_nk = 0; s_last = 0; }
+  __syncthreads();
 
-  // 1. filter + decode + clip.  The row count of the image lives on the device: it is requested TOGETHER with the rows'
-  // data (rows up to the static R are always addressable) and only compared afterwards -- one round trip, not two.
+  // 1. the order key of every row, nothing else.  The row count of the image lives on the device: it is requested TOGETHER
+  // with the scores (rows up to the static R are always addressable) and only compared afterwards -- one round trip, not two.
   const int Rdev = in_count ? *in_count : p.R;
-  u64 mykey = ~0ull;
-  for (int r = tid; r < p.P2; r += PO_THREADS) {
-    u64 key = ~0ull;
-    if (r < p.R) {
-      const float s = in_scores[(size_t)r * p.Ccls + c];
-      const float4 t = *reinterpret_cast<const float4*>(in_deltas + ((size_t)r * p.Ccls + c) * 4);
-      float4 roi = in_rois[r];
-      if (r < min(Rdev, p.R) && s > p.score_thr) {                             // :136
+  {
+    int nv = 0;
+    for (int r0 = tid; r0 < p.R; r0 += 4 * PO_THREADS) {     // four rows' scores in flight per thread
+      float s[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int r = r0 + u * PO_THREADS;
+        s[u] = r < p.R ? in_scores[(size_t)r * p.Ccls + c] : 0.0f;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int r = r0 + u * PO_THREADS;
+        const bool ok = r < min(Rdev, p.R) && s[u] > p.score_thr;              // :136
+        if (r < p.R) key[r] = ok ? ~d_float_asc_key(s[u]) : PO_INVALID;
+        nv += ok ? 1 : 0;
+      }
+    }
+    nv = wave_incl_scan(nv);
+    if (lane == 63 && nv) atomicAdd(&s_nvalid, nv);
+  }
+  __syncthreads();
+  const int nvalid = s_nvalid;
+  const int K = p.K;
+  const int per = (p.R + PO_THREADS - 1) / PO_THREADS;     // consecutive rows per thread where the row order counts (ties)
+  const int lo = tid * per;
+  const u64 lt_lane = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+
+  for (int taken = 0; taken < nvalid; taken += PO_ROUND) {
+    const int nk0 = s_nk;                       // kept so far (uniform: read after a barrier)
+    if (nk0 >= K) break;
+    const int left = nvalid - taken;
+    const int mround = min(PO_ROUND, left);
+    // 2. the batch: the mround best untaken rows = those with key < T and the first `ties` rows with key == T; all that are
+    // left when they fit (T = PO_INVALID: every untaken key is below it)
+    uint32_t T = PO_INVALID, ties = 0u;
+    if (mround < left) T = po_radix_select(key, p.R, mround, hist, &ties);
+    int nlt = 0, neq = 0;
+    for (int q = 0; q < per; ++q) {
+      const int row = lo + q;
+      if (row < p.R) {
+        const uint32_t k = key[row];
+        nlt += (k < T) ? 1 : 0;                 // (PO_INVALID is never below T)
+        neq += (k == T && k != PO_INVALID) ? 1 : 0;
+      }
+    }
+    {
+      // one scan for both counts (each total <= R <= ODET_POSTOPS_MAX_ROIS = 4096 < 2^16)
+      int tot;
+      const int before = block_excl_scan(nlt | (neq << 16), lds17, &tot);
+      int e = before >> 16;
+      int o = (before & 0xFFFF) + min(e, (int)ties);
+      for (int q = 0; q < per; ++q) {
+        const int row = lo + q;
+        if (row < p.R) {
+          const uint32_t k = key[row];
+          bool sel = k < T;
+          if (k == T && k != PO_INVALID) { sel = e < (int)ties; ++e; }
+          if (sel && o < PO_ROUND) { bkey[o] = k; brow[o] = (uint32_t)row; key[row] = PO_INVALID; ++o; }
+        }
+      }
+    }
+    __syncthreads();
+    // 3. rank inside the batch by (key, row) -- the batch is in row order, so row order is index order --, decode, clip and
+    // min-edge test of its rows; everything of a row goes to its rank
+    if (tid < PO_ROUND) {
+      if (tid < mround) {
+        const uint32_t ki = bkey[tid];
+        const int r = (int)brow[tid];
+        const float4 t = *reinterpret_cast<const float4*>(in_deltas + ((size_t)r * p.Ccls + c) * 4);
+        float4 roi = in_rois[r];
+        int rank = 0;
+        for (int j = 0; j < mround; ++j) {
+          const uint32_t kj = bkey[j];
+          rank += (kj < ki || (kj == ki && j < tid)) ? 1 : 0;
+        }
         const float d0 = t.x * p.stds[0] + p.means[0];
         const float d1 = t.y * p.stds[1] + p.means[1];
         const float d2 = t.z * p.stds[2] + p.means[2];
@@ -286,71 +374,40 @@ __global__ void __launch_bounds__(PO_THREADS) k_postops(PostOpsParams p) {
         float4 b = d_decode_box(roi, d0, d1, d2, d3);                          // :138-140
         b = d_clip_box(b, 0.0f, p.wmax, p.hmax);                               // :141-143
         const float e0 = b.z - b.x + 1.0f, e1 = b.w - b.y + 1.0f;              // bbox_tf.py:81-83
-        if (e1 >= p.min_edge && e0 >= p.min_edge) {
-          lbox[r] = b;
-          key = ((u64)(~d_float_asc_key(s)) << 32) | (unsigned)r;
-        }
+        const bool ok = e1 >= p.min_edge && e0 >= p.min_edge;
+        const float4 nb = d_norm_box(b);
+        sbox[rank] = nb;
+        obox[rank] = b;
+        sarea[rank] = d_box_area(nb);
+        skey[rank] = ki;
+        crossf[rank] = ok ? 0u : 1u;            // under the min edge: not a candidate (it is never kept, so it suppresses nothing)
+      } else {
+        sbox[tid] = make_float4(0, 0, 0, 0);
+        sarea[tid] = 0.0f;
+        crossf[tid] = 1u;
       }
     }
-    if (p.P2 > 1024) keys[r] = key; else mykey = key;
-  }
-  __syncthreads();                                    // (s_nvalid = 0 is visible)
-  {
-    const u64 bal = __ballot(p.P2 <= 1024 && mykey != ~0ull);
-    if (lane == 0 && bal) atomicAdd(&s_nvalid, (int)__popcll(bal));
-  }
-  __syncthreads();
-
-  // 2. sort: score desc, RoI index asc; rejected rows (key = ~0) go last
-  if (p.P2 <= 1024) {
-    mykey = bitonic_sort_1024_reg(mykey, keys);
     __syncthreads();
-    keys[tid] = mykey;
-    __syncthreads();
-  } else {
-    bitonic_sort_u64(keys, p.P2, PO_THREADS);
-    if (tid == 0) {
-      // count valid keys by bisection (sorted, ~0 last)
-      int lo = 0, hi = p.P2;
-      while (lo < hi) { int mid = (lo + hi) >> 1; if (keys[mid] != ~0ull) lo = mid + 1; else hi = mid; }
-      s_nvalid = lo;
-    }
-    __syncthreads();
-  }
-  const int nvalid = s_nvalid;
-  const int K = p.K;
-
-  // 3. greedy NMS in rounds of PO_ROUND sorted candidates
-  const u64 lt_lane = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  for (int t0 = 0; t0 < nvalid; t0 += PO_ROUND) {
-    const int nk0 = s_nk;                       // kept so far (uniform: read after a barrier)
-    if (nk0 >= K) break;
-    const int mround = min(PO_ROUND, nvalid - t0);
-    // boxes of the round, corner-normalised
-    if (tid < PO_ROUND) {
-      float4 nb = make_float4(0, 0, 0, 0);
-      if (tid < mround) nb = d_norm_box(lbox[(int)(keys[t0 + tid] & 0xFFFFFFFFull)]);
-      sbox[tid] = nb;
-      sarea[tid] = d_box_area(nb);
-      crossf[tid] = 0;
-    }
-    __syncthreads();
+    // 4. one NMS round over the batch
     {
-      // thread = (row, slice): 16 columns of the round's lower triangle + 1/8 of the kept list
-      const int row = tid & (PO_ROUND - 1), cs = tid >> 7;
+      // thread = (row, slice): PO_COLS columns of the round's lower triangle + 1/PO_SLICES of the kept list
+      const int row = tid & (PO_ROUND - 1), cs = tid / PO_ROUND;
       const float4 rb = sbox[row];
       const float ra = sarea[row];
-      uint32_t bits = 0;
+      u64 bits = 0;
 #pragma unroll
-      for (int j = 0; j < 16; ++j) {
-        const int col = cs * 16 + j;
+      for (int j = 0; j < PO_COLS; ++j) {
+        const int col = cs * PO_COLS + j;
         const bool s = (col < row) && d_iou_gt(rb, ra, sbox[col], sarea[col], p.nms_thr);
-        bits |= s ? (1u << j) : 0u;
+        bits |= s ? (1ull << j) : 0ull;
       }
-      // 16-bit pieces of the row's 128-bit mask: 4 pieces per u64 word
-      reinterpret_cast<unsigned short*>(mask)[row * 8 + cs] = (unsigned short)bits;
+      // PO_COLS-bit pieces of the row's PO_ROUND-bit mask, piece cs at its place in the row's words
+      if (PO_COLS == 8) reinterpret_cast<unsigned char*>(mask)[row * PO_SLICES + cs] = (unsigned char)bits;
+      else if (PO_COLS == 16) reinterpret_cast<unsigned short*>(mask)[row * PO_SLICES + cs] = (unsigned short)bits;
+      else if (PO_COLS == 32) reinterpret_cast<uint32_t*>(mask)[row * PO_SLICES + cs] = (uint32_t)bits;
+      else mask[row * PO_SLICES + cs] = bits;
       bool sup = false;
-      for (int k = cs; k < nk0; k += 8) sup = sup || d_iou_gt(rb, ra, kbox[k], karea[k], p.nms_thr);
+      for (int k = cs; k < nk0; k += PO_SLICES) sup = sup || d_iou_gt(rb, ra, kbox[k], karea[k], p.nms_thr);
       if (sup) atomicOr(&crossf[row], 1u);
     }
     __syncthreads();
@@ -358,9 +415,9 @@ __global__ void __launch_bounds__(PO_THREADS) k_postops(PostOpsParams p) {
       int nk = nk0;
       u64 kept0 = 0;
 #pragma unroll
-      for (int blk = 0; blk < 2; ++blk) {
+      for (int blk = 0; blk < PO_WORDS; ++blk) {
         const int row = blk * 64 + lane;
-        const u64 m0 = mask[row * 2 + 0], m1 = mask[row * 2 + 1];
+        const u64 m0 = mask[row * PO_WORDS + 0], m1 = mask[row * PO_WORDS + PO_WORDS - 1];
         bool dead = (row >= mround) || (crossf[row] != 0);
         if (blk == 1) dead = dead || ((m0 & kept0) != 0ull);
         const u64 mm = (blk == 0) ? m0 : m1;      // same-block earlier candidates that suppress me
@@ -376,12 +433,10 @@ __global__ void __launch_bounds__(PO_THREADS) k_postops(PostOpsParams p) {
         if (blk == 0) kept0 = kept;
         if ((kept >> lane) & 1ull) {
           const int slot = nk0 + (blk == 1 ? (int)__popcll(kept0) : 0) + (int)__popcll(kept & lt_lane);
-          const u64 kk = keys[t0 + row];
-          const float4 ob = lbox[(int)(kk & 0xFFFFFFFFull)];
           kbox[slot] = sbox[row];
           karea[slot] = sarea[row];
-          cls_boxes[(size_t)blockIdx.x * K + slot] = ob;
-          cls_scores[(size_t)blockIdx.x * K + slot] = key_to_score((uint32_t)(kk >> 32));
+          cls_boxes[(size_t)blockIdx.x * K + slot] = obox[row];
+          cls_scores[(size_t)blockIdx.x * K + slot] = key_to_score(skey[row]);
         }
       }
       if (lane == 0) s_nk = nk;
@@ -390,7 +445,7 @@ __global__ void __launch_bounds__(PO_THREADS) k_postops(PostOpsParams p) {
   }
   if (tid == 0) cls_count[blockIdx.x] = s_nk;
 
-  // 4. publish this class's list, draw a ticket; the last workgroup of the image merges.  (MI355X guide, "Workgroup
+  // 6. publish this class's list, draw a ticket; the last workgroup of the image merges.  (MI355X guide, "Workgroup
   // dispatch, XCD placement & inter-workgroup visibility": every storing wave drains its stores, workgroup barrier, ONE
   // lane releases at agent scope -- the XCD's L2 writes its dirty lines back -- and only then signals; the consumer
   // acquires at agent scope before any of its loads of the other workgroups' lists.)
@@ -473,15 +528,17 @@ int odet_post_ops_batch(const PostOpsImageIO* io, int B, int R, int Ccls, int nu
     p.out_count_t.v[i] = a.out_count; p.out_record_t.v[i] = a.out_record;
     if (!ws_clean && i < B) ODET_HIP(hipMemsetAsync(tk, 0, sizeof(uint32_t), st));
   }
-  p.R = R; p.Ccls = Ccls; p.P2 = next_pow2_(R < 2 ? 2 : R); p.K = max_per_class;
+  p.R = R; p.Ccls = Ccls; p.K = max_per_class;
   for (int k = 0; k < 4; ++k) { p.means[k] = means[k]; p.stds[k] = stds[k]; }
   p.wmax = ex.wmax; p.hmax = ex.hmax; p.roi_div = ex.roi_div;
   p.min_edge = min_edge; p.score_thr = score_threshold; p.nms_thr = nms_iou_threshold;
   p.ncls1 = ncls1; p.max_per_image = max_per_image; p.mode = ex.mode;
-  const size_t nkeys1 = (size_t)(p.P2 > 2048 ? p.P2 : 2048);
-  const size_t lds_class = nkeys1 * 8 + (size_t)R * 16 + PO_ROUND * 16 + (size_t)max_per_class * 16 + PO_ROUND * 16 +
-                           PO_ROUND * 4 + (size_t)max_per_class * 4 + PO_ROUND * 4;
-  const size_t lds_merge = (size_t)ncls1 * max_per_class * 4 + 256 * 4 + (size_t)(max_per_image > 0 ? max_per_image : 1) * 8 + 64;
+  // (k_postops' layout comment; both stay below what the eager sort needed: 8 B of keys and 16 B of box per row)
+  const size_t lds_class = 2 * PO_ROUND * 16 + (size_t)max_per_class * 16 + PO_ROUND * PO_WORDS * 8 + 4 * 256 * 4 +
+                           (size_t)R * 4 + 5 * PO_ROUND * 4 + (size_t)max_per_class * 4;
+  const size_t nslots = (size_t)ncls1 * max_per_class;
+  const size_t nsel = max_per_image > 0 ? ((size_t)max_per_image < nslots ? (size_t)max_per_image : nslots) : 1;
+  const size_t lds_merge = nslots * 4 + 4 * 256 * 4 + nsel * 8 + 64;
   const size_t lds1 = lds_class > lds_merge ? lds_class : lds_merge;
   if (lds1 > 150 * 1024)
     return odet_set_error(ODET_E_LIMIT, "odet_post_ops: R/max_per_class need %zu B of LDS (> 150 KiB)", lds1);
