@@ -11,16 +11,7 @@
 // HBM-bound streams.  The layout of k_fpn_topdown_backward_f32 (neck.hip): a lane owns four channels (16 bytes), a pixel's lanes
 // are consecutive; the operands are read once (non-temporal loads), the result is stored normally (the next launch reads it).  One
 // float32 add per element, no LDS, no atomics, no workspace; every output element is written exactly once.
-#include "odet_internal.h"
-
-typedef uint32_t blk_u4 __attribute__((ext_vector_type(4)));   // 16 B, the type the non-temporal builtins take
-
-static __device__ __forceinline__ float4 blk_stream(const float4* p) {
-  const blk_u4 t = __builtin_nontemporal_load(reinterpret_cast<const blk_u4*>(p));
-  float4 r;
-  __builtin_memcpy(&r, &t, 16);
-  return r;
-}
+#include "grad_elementwise.h"
 
 struct GatherParams {
   const float4* x; float4* out;
@@ -37,7 +28,7 @@ __global__ void __launch_bounds__(256) k_stride_gather_f32(GatherParams p) {
     px /= p.Wo;
     const int Y = (int)(px % p.Ho);
     const long long b = px / p.Ho;
-    p.out[i] = blk_stream(&p.x[((b * p.H + (long long)Y * p.stride) * p.W + (long long)X * p.stride) * p.vec_per_px + v]);
+    p.out[i] = ge_stream(&p.x[((b * p.H + (long long)Y * p.stride) * p.W + (long long)X * p.stride) * p.vec_per_px + v]);
   }
 }
 
@@ -54,7 +45,7 @@ __global__ void __launch_bounds__(256) k_block_input_grad_f32(JoinParams p) {
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < p.total; i += (long long)gridDim.x * 256) {
     float4 r;
     if (IDENTITY) {
-      const float4 g = blk_stream(&p.dy[i]), y = blk_stream(&p.y[i]), a = blk_stream(&p.d1[i]);
+      const float4 g = ge_stream(&p.dy[i]), y = ge_stream(&p.y[i]), a = ge_stream(&p.d1[i]);
       r = make_float4((y.x > 0.0f ? g.x : 0.0f) + a.x, (y.y > 0.0f ? g.y : 0.0f) + a.y, (y.z > 0.0f ? g.z : 0.0f) + a.z,
                       (y.w > 0.0f ? g.w : 0.0f) + a.w);
     } else {
@@ -68,9 +59,9 @@ __global__ void __launch_bounds__(256) k_block_input_grad_f32(JoinParams p) {
       if (p.stride == 1 || !((Y | X) & 1)) {
         const int sh = p.stride - 1;                         // stride 1 or 2
         const long long src = ((b * p.Ho + (Y >> sh)) * p.Wo + (X >> sh)) * p.vec_per_px + v;
-        r = blk_stream(&p.d1[src]);
+        r = ge_stream(&p.d1[src]);
         if (p.d2) {
-          const float4 t = blk_stream(&p.d2[src]);
+          const float4 t = ge_stream(&p.d2[src]);
           r = make_float4(r.x + t.x, r.y + t.y, r.z + t.z, r.w + t.w);
         }
       }
@@ -79,18 +70,11 @@ __global__ void __launch_bounds__(256) k_block_input_grad_f32(JoinParams p) {
   }
 }
 
-static int blk_grid(long long total) {
-  const long long blocks = (total + 255) / 256;
-  return (int)std::min<long long>(blocks, 256 * 64);           // grid-stride beyond 64 workgroups per CU
-}
-
 extern "C" int odet_stride_gather_f32(const float* x, int B, int H, int W, int C, int stride, float* out, odet_stream_t stream) {
   const char* who = "odet_stride_gather_f32";
   ODET_REQUIRE(x && out, "%s: null pointer", who);
-  ODET_REQUIRE(H > 0 && W > 0 && B >= 0, "%s: bad sizes (B %d, H %d, W %d)", who, B, H, W);
-  ODET_REQUIRE(C > 0 && C % 4 == 0, "%s: C must be a positive multiple of 4 (got %d)", who, C);
+  GE_REQUIRE_NHWC(who, B, H, W, C, (uintptr_t)x | (uintptr_t)out);
   ODET_REQUIRE(stride == 1 || stride == 2, "%s: stride must be 1 or 2 (got %d)", who, stride);
-  ODET_REQUIRE(((uintptr_t)x | (uintptr_t)out) % 16 == 0, "%s: pointers must be 16-byte aligned", who);
   if (B == 0) return ODET_OK;
   GatherParams p;
   p.x = reinterpret_cast<const float4*>(x);
@@ -100,7 +84,7 @@ extern "C" int odet_stride_gather_f32(const float* x, int B, int H, int W, int C
   p.Wo = (W - 1) / stride + 1;
   p.vec_per_px = C / 4;
   p.total = (long long)B * p.Ho * p.Wo * p.vec_per_px;
-  hipLaunchKernelGGL(k_stride_gather_f32, dim3(blk_grid(p.total)), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(k_stride_gather_f32, dim3(ge_grid(p.total)), dim3(256), 0, (hipStream_t)stream, p);
   ODET_LAUNCH_CHECK();
   return ODET_OK;
 }
@@ -113,12 +97,9 @@ extern "C" int odet_block_input_grad_f32(const float* dy, const float* y, const 
   const bool identity = dy && y && !d2, conv = !dy && !y;
   ODET_REQUIRE(identity || conv, "%s: either dy, y and d1 without d2 (identity shortcut) or d1 (and d2) without dy and y "
                "(convolutional shortcut)", who);
-  ODET_REQUIRE(H > 0 && W > 0 && B >= 0, "%s: bad sizes (B %d, H %d, W %d)", who, B, H, W);
-  ODET_REQUIRE(C > 0 && C % 4 == 0, "%s: C must be a positive multiple of 4 (got %d)", who, C);
+  GE_REQUIRE_NHWC(who, B, H, W, C, (uintptr_t)dy | (uintptr_t)y | (uintptr_t)d1 | (uintptr_t)d2 | (uintptr_t)dx);
   ODET_REQUIRE(stride == 1 || stride == 2, "%s: stride must be 1 or 2 (got %d)", who, stride);
   ODET_REQUIRE(!identity || stride == 1, "%s: the identity form takes stride 1 only (got %d)", who, stride);
-  ODET_REQUIRE(((uintptr_t)dy | (uintptr_t)y | (uintptr_t)d1 | (uintptr_t)d2 | (uintptr_t)dx) % 16 == 0,
-               "%s: pointers must be 16-byte aligned", who);
   if (B == 0) return ODET_OK;
   JoinParams p;
   p.dy = reinterpret_cast<const float4*>(dy);
@@ -132,9 +113,9 @@ extern "C" int odet_block_input_grad_f32(const float* dy, const float* y, const 
   p.vec_per_px = C / 4;
   p.total = (long long)B * H * W * p.vec_per_px;
   if (identity)
-    hipLaunchKernelGGL(k_block_input_grad_f32<true>, dim3(blk_grid(p.total)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_block_input_grad_f32<true>, dim3(ge_grid(p.total)), dim3(256), 0, (hipStream_t)stream, p);
   else
-    hipLaunchKernelGGL(k_block_input_grad_f32<false>, dim3(blk_grid(p.total)), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL(k_block_input_grad_f32<false>, dim3(ge_grid(p.total)), dim3(256), 0, (hipStream_t)stream, p);
   ODET_LAUNCH_CHECK();
   return ODET_OK;
 }

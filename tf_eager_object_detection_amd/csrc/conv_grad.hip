@@ -108,55 +108,52 @@ struct ConvGradPlan { int wt, parts, kper; long long tiles, K; };
 // Tile and cut of dw [cout][9 cin] with contraction K = batch * sum H W -- a function of the shapes alone.  128 x 128 tiles
 // when both edges divide (cin, cout multiples of 128), else 64 x 64.  The output never fills the machine at a detector's
 // channel counts, so the contraction is cut: as many parts as bring the launch to 512 workgroups (two of the 128^2 form per
-// CU of 256), at most 16, each of at least 64 k, and none below K = 256; parts are equal runs of whole K-steps
-static ConvGradPlan cg_plan(const int* H, const int* W, int num_levels, int batch, int cin, int cout) {
+// CU of 256), at most 16, each of at least 64 k, and none below K = 256; parts are equal runs of whole K-steps (dg_split)
+static ConvGradPlan cg_plan(long long K, int cin, int cout) {
   ConvGradPlan pl;
-  long long K = 0;
-  for (int l = 0; l < num_levels; ++l) K += (long long)batch * H[l] * W[l];
   pl.K = K;
   pl.wt = (cin % 128 == 0 && cout % 128 == 0) ? 4 : 2;
   const int T = 32 * pl.wt;
   pl.tiles = (long long)((9 * cin + T - 1) / T) * ((cout + T - 1) / T);
   long long parts = 1;
   if (K >= 256) parts = std::max<long long>(1, std::min<long long>(std::min<long long>(512 / pl.tiles, K / 64), 16));
-  const long long kper = ((K + parts - 1) / parts + DG_BK - 1) / DG_BK * DG_BK;
-  pl.kper = (int)kper;
-  pl.parts = (int)std::max<long long>(1, (K + pl.kper - 1) / pl.kper);
+  pl.parts = dg_split(K, parts, &pl.kper);
   return pl;
 }
 
-// the argument rules of both entry points (the forward's, conv_f32_plan_levels, on shapes alone); H / W out for the plan
+// ONE walk of the level list, for the query and the entry point: K = batch * sum H W -> num_levels when every level has a
+// positive size and K stays below CG_MAX_PIXELS; else the first level that fails, *K >= CG_MAX_PIXELS when it is the sum
+static int cg_walk_levels(const odet_conv_grad_level_t* levels, int num_levels, int batch, long long* K) {
+  *K = 0;
+  for (int l = 0; l < num_levels; ++l) {
+    if (levels[l].H < 1 || levels[l].W < 1) return l;
+    *K += (long long)batch * levels[l].H * levels[l].W;
+    if (*K >= CG_MAX_PIXELS) return l;
+  }
+  return num_levels;
+}
+
+// the argument rules of the entry point (the forward's, conv_f32_plan_levels, on shapes alone); K out for the plan
 static int cg_check_shapes(const char* who, const odet_conv_grad_level_t* levels, int num_levels, int batch, int cin, int cout,
-                           int* H, int* W) {
+                           long long* K) {
   ODET_REQUIRE(levels, "%s: null pointer", who);
   ODET_REQUIRE(num_levels >= 1 && num_levels <= ODET_MAX_LEVELS, "%s: num_levels %d out of range", who, num_levels);
   ODET_REQUIRE(batch > 0, "%s: bad batch", who);
   ODET_REQUIRE(cin > 0 && cin % CONV_F32_BK == 0, "%s: cin %d must be a multiple of %d", who, cin, CONV_F32_BK);
   ODET_REQUIRE(cout > 0 && cout % 64 == 0, "%s: cout %d must be a multiple of 64", who, cout);
   ODET_REQUIRE((unsigned long long)cout * 9ull * cin * 4ull < 0x7FFFFFFFull, "%s: weights too large", who);
-  long long K = 0;
-  for (int l = 0; l < num_levels; ++l) {
-    ODET_REQUIRE(levels[l].H > 0 && levels[l].W > 0, "%s: bad level %d", who, l);
-    H[l] = levels[l].H; W[l] = levels[l].W;
-    K += (long long)batch * H[l] * W[l];
-    ODET_REQUIRE(K < CG_MAX_PIXELS, "%s: more than 2^31 - 2^16 pixels", who);
-  }
+  const int l = cg_walk_levels(levels, num_levels, batch, K);
+  ODET_REQUIRE(l == num_levels || *K >= CG_MAX_PIXELS, "%s: bad level %d", who, l);
+  ODET_REQUIRE(l == num_levels, "%s: more than 2^31 - 2^16 pixels", who);
   return ODET_OK;
 }
 
 extern "C" size_t odet_conv3x3_wgrad_workspace_bytes(const odet_conv_grad_level_t* levels, int num_levels, int batch, int cin,
                                                      int cout) {
-  int H[ODET_MAX_LEVELS], W[ODET_MAX_LEVELS];
+  long long K;
   if (!levels || num_levels < 1 || num_levels > ODET_MAX_LEVELS || batch < 1 || cin < 1 || cout < 1) return 0;
-  long long K = 0;
-  for (int l = 0; l < num_levels; ++l) {
-    if (levels[l].H < 1 || levels[l].W < 1) return 0;
-    H[l] = levels[l].H; W[l] = levels[l].W;
-    K += (long long)batch * H[l] * W[l];
-    if (K >= CG_MAX_PIXELS) return 0;
-  }
-  const ConvGradPlan pl = cg_plan(H, W, num_levels, batch, cin, cout);
-  return pl.parts > 1 ? (size_t)pl.parts * (size_t)cout * 9 * (size_t)cin * sizeof(float) : 0;
+  if (cg_walk_levels(levels, num_levels, batch, &K) != num_levels) return 0;
+  return dg_workspace_bytes(cg_plan(K, cin, cout).parts, cout, 9ll * cin);
 }
 
 static hipError_t cg_prepare_kernels() {
@@ -168,9 +165,9 @@ static hipError_t cg_prepare_kernels() {
 extern "C" int odet_conv3x3_wgrad_f32_levels(const odet_conv_grad_level_t* levels, int num_levels, float* dw, float* db, int batch,
                                              int cin, int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
   const char* who = "odet_conv3x3_wgrad_f32_levels";
-  int H[ODET_MAX_LEVELS], W[ODET_MAX_LEVELS];
+  long long K;
   ODET_REQUIRE(dw, "%s: null pointer", who);
-  const int rs = cg_check_shapes(who, levels, num_levels, batch, cin, cout, H, W);
+  const int rs = cg_check_shapes(who, levels, num_levels, batch, cin, cout, &K);
   if (rs != ODET_OK) return rs;
   ODET_REQUIRE((uintptr_t)dw % 16 == 0 && (uintptr_t)db % 4 == 0, "%s: pointers must be 16-byte aligned (db: 4)", who);
   for (int l = 0; l < num_levels; ++l) {
@@ -178,14 +175,10 @@ extern "C" int odet_conv3x3_wgrad_f32_levels(const odet_conv_grad_level_t* level
     ODET_REQUIRE(((uintptr_t)levels[l].x | (uintptr_t)levels[l].dy | (uintptr_t)levels[l].y_relu) % 16 == 0,
                  "%s: maps must be 16-byte aligned", who);
   }
-  const ConvGradPlan pl = cg_plan(H, W, num_levels, batch, cin, cout);
-  const size_t need = pl.parts > 1 ? (size_t)pl.parts * (size_t)cout * 9 * (size_t)cin * sizeof(float) : 0;
-  if (need) {
-    if (!workspace || workspace_bytes < need)
-      return odet_set_error(ODET_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (odet_conv3x3_wgrad_workspace_bytes)", who,
-                            workspace ? workspace_bytes : (size_t)0, need);
-    ODET_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: the workspace must be 16-byte aligned", who);
-  }
+  const ConvGradPlan pl = cg_plan(K, cin, cout);
+  const size_t need = dg_workspace_bytes(pl.parts, cout, 9ll * cin);
+  const int rw = dg_check_workspace(who, "odet_conv3x3_wgrad_workspace_bytes", need, workspace, workspace_bytes);
+  if (rw != ODET_OK) return rw;
   const hipStream_t st = (hipStream_t)stream;
   ODET_HIP(cg_prepare_kernels());
   ConvGradParams p = {};
@@ -196,7 +189,7 @@ extern "C" int odet_conv3x3_wgrad_f32_levels(const odet_conv_grad_level_t* level
     L.start = (int)pl.K;
     if (l >= num_levels) continue;
     L.x = (const float*)levels[l].x; L.dy = (const float*)levels[l].dy; L.y = (const float*)levels[l].y_relu;
-    L.H = H[l]; L.W = W[l]; L.HW = H[l] * W[l]; L.start = k;
+    L.H = levels[l].H; L.W = levels[l].W; L.HW = L.H * L.W; L.start = k;
     rows.dy[l] = L.dy; rows.y[l] = L.y; rows.rows[l] = (long long)batch * L.HW;
     k += batch * L.HW;
   }

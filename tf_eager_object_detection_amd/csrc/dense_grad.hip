@@ -223,9 +223,26 @@ static DenseGradPlan dg_plan(int M, int N, int K) {
   pl.tiles = (long long)((M + T - 1) / T) * ((N + T - 1) / T);
   int ks = 1;
   if (pl.tiles <= 128 && K >= 256) ks = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(256 / pl.tiles, K / 64), 8));
-  pl.kper = ((K + ks - 1) / ks + DG_BK - 1) / DG_BK * DG_BK;
-  pl.ksplit = (K + pl.kper - 1) / pl.kper;
+  pl.ksplit = dg_split(K, ks, &pl.kper);
   return pl;
+}
+
+int dg_split(long long K, long long parts, int* kper) {
+  *kper = (int)(((K + parts - 1) / parts + DG_BK - 1) / DG_BK * DG_BK);
+  return (int)std::max<long long>(1, (K + *kper - 1) / *kper);
+}
+
+size_t dg_workspace_bytes(int parts, long long N, long long M) {
+  return parts > 1 ? (size_t)parts * (size_t)N * (size_t)M * sizeof(float) : 0;
+}
+
+int dg_check_workspace(const char* who, const char* query_name, size_t need, const void* workspace, size_t workspace_bytes) {
+  if (!need) return ODET_OK;
+  if (!workspace || workspace_bytes < need)
+    return odet_set_error(ODET_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (%s)", who,
+                          workspace ? workspace_bytes : (size_t)0, need, query_name);
+  ODET_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: the workspace must be 16-byte aligned", who);
+  return ODET_OK;
 }
 
 static int dg_check_shape(const char* who, int rows, int cin, int cout) {
@@ -238,7 +255,7 @@ static int dg_check_shape(const char* who, int rows, int cin, int cout) {
 extern "C" size_t odet_dense_grad_workspace_bytes(int wgrad, int rows, int cin, int cout) {
   if (rows < 1 || cin < 1 || cout < 1) return 0;
   const DenseGradPlan pl = wgrad ? dg_plan(cin, cout, rows) : dg_plan(cin, rows, cout);
-  return pl.ksplit > 1 ? (size_t)pl.ksplit * (size_t)(wgrad ? cout : rows) * (size_t)cin * sizeof(float) : 0;
+  return dg_workspace_bytes(pl.ksplit, wgrad ? cout : rows, cin);
 }
 
 static hipError_t dg_prepare_kernels() {
@@ -254,13 +271,9 @@ static int dg_launch(const char* who, const float* a, const float* b, const floa
                      int K, void* workspace, size_t workspace_bytes, hipStream_t st) {
   const DenseGradPlan pl = dg_plan(M, N, K);
   ODET_REQUIRE(pl.tiles < (1ll << 31), "%s: too many workgroups", who);
-  const size_t need = pl.ksplit > 1 ? (size_t)pl.ksplit * (size_t)N * (size_t)M * sizeof(float) : 0;
-  if (need) {
-    if (!workspace || workspace_bytes < need)
-      return odet_set_error(ODET_E_WORKSPACE, "%s: workspace of %zu bytes, %zu needed (odet_dense_grad_workspace_bytes)", who,
-                            workspace ? workspace_bytes : (size_t)0, need);
-    ODET_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: the workspace must be 16-byte aligned", who);
-  }
+  const size_t need = dg_workspace_bytes(pl.ksplit, N, M);
+  const int rw = dg_check_workspace(who, "odet_dense_grad_workspace_bytes", need, workspace, workspace_bytes);
+  if (rw != ODET_OK) return rw;
   ODET_HIP(dg_prepare_kernels());
   DenseGradParams p;
   p.a = a; p.b = b; p.bmask = bmask; p.omask = need ? nullptr : omask; p.out = need ? (float*)workspace : out;

@@ -108,6 +108,14 @@ __device__ __forceinline__ void dg_tile(Fetch&& fetch, int kbeg, int kend, int m
 #endif  // __HIPCC__
 
 // ---- host side, defined in dense_grad.hip -----------------------------------------------------------------------------------
+// K cut into at most `parts` equal runs of whole K-steps: the run length in *kper, the number of non-empty runs returned (>= 1);
+// how many parts a launch asks for is each plan's own rule
+int dg_split(long long K, long long parts, int* kper);
+// the workspace a launch cut into `parts` needs for its partial [N][M] outputs (uncut: none), and the caller's checked against
+// it: ODET_E_WORKSPACE naming the query that sizes it when missing or short; 16-byte aligned
+size_t dg_workspace_bytes(int parts, long long N, long long M);
+int dg_check_workspace(const char* who, const char* query_name, size_t need, const void* workspace, size_t workspace_bytes);
+
 // out[i] = ((parts[0][i] + parts[1][i]) + ...) + parts[nparts - 1][i] for the total4 16-byte groups of one part, kept only where
 // omask > 0 when omask is given
 int dg_reduce_parts(const float* parts, int nparts, long long total4, const float* omask, float* out, hipStream_t st);

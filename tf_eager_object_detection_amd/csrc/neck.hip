@@ -7,7 +7,7 @@
 // top = tl + (tr - tl) * xl; bot = bl + (br - bl) * xl; up = top + (bot - top) * yl; out = up*0.5 + lat*0.5.
 #include <hip/hip_fp16.h>
 
-#include "odet_internal.h"
+#include "grad_elementwise.h"
 
 typedef uint32_t neck_u4 __attribute__((ext_vector_type(4)));   // 16 B, the type the non-temporal builtins take
 
@@ -107,8 +107,7 @@ extern "C" int odet_fpn_topdown_merge(const void* top, int h, int w, const void*
   p.total = (long long)B * H * W * p.vec_per_px;
   p.ys = (float)h / (float)H;
   p.xs = (float)w / (float)W;
-  const long long blocks = (p.total + 255) / 256;
-  const int grid = (int)std::min<long long>(blocks, 256 * 64);      // grid-stride beyond 64 workgroups per CU
+  const int grid = ge_grid(p.total);
   if (f16)
     hipLaunchKernelGGL(k_fpn_topdown_merge<__half>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   else
@@ -221,10 +220,8 @@ extern "C" int odet_fpn_topdown_backward_f32(const float* fine, int H, int W, co
   const char* who = "odet_fpn_topdown_backward_f32";
   ODET_REQUIRE(d_top, "%s: null d_top", who);
   ODET_REQUIRE(fine || base || sub, "%s: at least one of fine, base and sub is needed", who);
-  ODET_REQUIRE(h > 0 && w > 0 && H > 0 && W > 0 && B >= 0, "%s: bad sizes (h %d, w %d, H %d, W %d, B %d)", who, h, w, H, W, B);
-  ODET_REQUIRE(C > 0 && C % 4 == 0, "%s: C must be a positive multiple of 4 (got %d)", who, C);
-  ODET_REQUIRE(((uintptr_t)fine | (uintptr_t)base | (uintptr_t)sub | (uintptr_t)d_top) % 16 == 0,
-               "%s: pointers must be 16-byte aligned", who);
+  ODET_REQUIRE(h > 0 && w > 0, "%s: bad sizes (h %d, w %d)", who, h, w);
+  GE_REQUIRE_NHWC(who, B, H, W, C, (uintptr_t)fine | (uintptr_t)base | (uintptr_t)sub | (uintptr_t)d_top);
   if (B == 0) return ODET_OK;
   NeckBwdParams p;
   p.fine = reinterpret_cast<const float4*>(fine);
@@ -238,8 +235,7 @@ extern "C" int odet_fpn_topdown_backward_f32(const float* fine, int H, int W, co
   p.ys = (float)h / (float)H;
   p.xs = (float)w / (float)W;
   p.out_scale = out_scale;
-  const long long blocks = (p.total + 255) / 256;
-  const int grid = (int)std::min<long long>(blocks, 256 * 64);      // grid-stride beyond 64 workgroups per CU
+  const int grid = ge_grid(p.total);
   hipLaunchKernelGGL(k_fpn_topdown_backward_f32, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   ODET_LAUNCH_CHECK();
   return ODET_OK;

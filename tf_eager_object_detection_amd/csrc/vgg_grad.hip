@@ -12,16 +12,7 @@
 // elements (one Philox call); the operands are read once (non-temporal loads), the result is stored normally (the next launch reads
 // it).  The windows do not overlap, so the pooling backward is a gather: no atomics, no LDS, no stored arg-max; every output element
 // is written exactly once.
-#include "odet_internal.h"
-
-typedef uint32_t vg_u4 __attribute__((ext_vector_type(4)));   // 16 B, the type the non-temporal builtins take
-
-static __device__ __forceinline__ float4 vg_stream(const float4* p) {
-  const vg_u4 t = __builtin_nontemporal_load(reinterpret_cast<const vg_u4*>(p));
-  float4 r;
-  __builtin_memcpy(&r, &t, 16);
-  return r;
-}
+#include "grad_elementwise.h"
 
 struct PoolGradParams {
   const float4* z; const float4* bias; const float4* dpool; float4* dz;
@@ -49,12 +40,12 @@ __global__ void __launch_bounds__(256) k_relu_maxpool2_backward_f32(PoolGradPara
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (!in[k]) continue;
-      const float4 zv = vg_stream(&p.z[base + off[k]]);
+      const float4 zv = ge_stream(&p.z[base + off[k]]);
       const float zs[4] = {zv.x, zv.y, zv.z, zv.w};
 #pragma unroll
       for (int c = 0; c < 4; ++c) a[k][c] = zs[c] + bs[c];     // the sum the forward forms
     }
-    const float4 gv = vg_stream(&p.dpool[i]);
+    const float4 gv = ge_stream(&p.dpool[i]);
     const float g[4] = {gv.x, gv.y, gv.z, gv.w};
     int win[4];                                                // the first tap that holds the window's maximum
     float best[4];
@@ -102,7 +93,7 @@ __global__ void __launch_bounds__(256) k_dropout_f32(DropoutParams p) {
     float xs[4], r[4];
     const bool whole = e0 + 4 <= p.n;
     if (whole) {
-      const float4 xv = vg_stream(reinterpret_cast<const float4*>(p.x + e0));
+      const float4 xv = ge_stream(reinterpret_cast<const float4*>(p.x + e0));
       xs[0] = xv.x; xs[1] = xv.y; xs[2] = xv.z; xs[3] = xv.w;
     } else {
 #pragma unroll
@@ -123,19 +114,11 @@ __global__ void __launch_bounds__(256) k_dropout_f32(DropoutParams p) {
   }
 }
 
-static int vg_grid(long long total) {
-  const long long blocks = (total + 255) / 256;
-  return (int)std::min<long long>(blocks, 256 * 64);           // grid-stride beyond 64 workgroups per CU
-}
-
 extern "C" int odet_relu_maxpool2_backward_f32(const float* z, const float* bias, const float* dpool, float* dz, int B, int H, int W,
                                                int C, odet_stream_t stream) {
   const char* who = "odet_relu_maxpool2_backward_f32";
   ODET_REQUIRE(z && bias && dpool && dz, "%s: null pointer", who);
-  ODET_REQUIRE(H > 0 && W > 0 && B >= 0, "%s: bad sizes (B %d, H %d, W %d)", who, B, H, W);
-  ODET_REQUIRE(C > 0 && C % 4 == 0, "%s: C must be a positive multiple of 4 (got %d)", who, C);
-  ODET_REQUIRE(((uintptr_t)z | (uintptr_t)bias | (uintptr_t)dpool | (uintptr_t)dz) % 16 == 0, "%s: pointers must be 16-byte aligned",
-               who);
+  GE_REQUIRE_NHWC(who, B, H, W, C, (uintptr_t)z | (uintptr_t)bias | (uintptr_t)dpool | (uintptr_t)dz);
   if (B == 0) return ODET_OK;
   PoolGradParams p;
   p.z = reinterpret_cast<const float4*>(z);
@@ -147,7 +130,7 @@ extern "C" int odet_relu_maxpool2_backward_f32(const float* z, const float* bias
   p.OW = (W + 1) / 2;
   p.vec_per_px = C / 4;
   p.total = (long long)B * p.OH * p.OW * p.vec_per_px;
-  hipLaunchKernelGGL(k_relu_maxpool2_backward_f32, dim3(vg_grid(p.total)), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(k_relu_maxpool2_backward_f32, dim3(ge_grid(p.total)), dim3(256), 0, (hipStream_t)stream, p);
   ODET_LAUNCH_CHECK();
   return ODET_OK;
 }
@@ -167,7 +150,7 @@ static int vg_dropout(const char* who, bool backward, const float* x, float* y, 
   p.x = x; p.y = y; p.n = n; p.keep_prob = keep_prob;
   p.k0 = (uint32_t)seed; p.k1 = (uint32_t)(seed >> 32);
   p.image_id = image_id; p.stream_id = stream_id;
-  const int grid = vg_grid((n + 3) >> 2);
+  const int grid = ge_grid((n + 3) >> 2);
   if (backward)
     hipLaunchKernelGGL(k_dropout_f32<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, p);
   else

@@ -28,6 +28,7 @@ from .prediction import post_ops_prediction
 from .proposal_target import training_target_layers
 from .region_proposal import RegionProposal
 from .roi_pooling import RoiPoolingCropAndResize
+from .trainable_common import check_train_flags
 
 __all__ = ['BaseFasterRcnn', 'RpnHead', 'ResNetFasterRcnn', 'Vgg16FasterRcnn']
 
@@ -391,12 +392,10 @@ class Vgg16FasterRcnn(_FrcnnFromDense):
                  train_extractor=False, dropout_seed=0, **kwargs):
         from .frcnn_detector import Vgg16Detector
         check_caller_f32_form(f32_form)
-        for on, name, what in ((train_extractor, 'train_extractor', 'the convolution and pooling backward have'),
-                               (train_roi_head, 'train_roi_head', 'the Dense backward has'),
-                               (train_rpn_head, 'train_rpn_head', 'the convolution backward has')):
-            if on and (dtype != torch.float32 or f32_form != 'exact'):
-                raise ValueError("Vgg16FasterRcnn: %s=True needs dtype=torch.float32 and f32_form='exact' (%s no float16 or "
-                                 "split-precision form), got %s, %r" % (name, what, dtype, f32_form))
+        check_train_flags('Vgg16FasterRcnn', dtype, f32_form,
+                          (train_extractor, 'train_extractor', 'the convolution and pooling backward have'),
+                          (train_roi_head, 'train_roi_head', 'the Dense backward has'),
+                          (train_rpn_head, 'train_rpn_head', 'the convolution backward has'))
         check_train_extractor(train_extractor, train_rpn_head, train_roi_head)
         if train_roi_head and not 0.0 < float(roi_head_keep_dropout_rate) <= 1.0:
             raise ValueError('Vgg16FasterRcnn: roi_head_keep_dropout_rate must be in (0, 1], got %r' % (roi_head_keep_dropout_rate,))

@@ -32,6 +32,7 @@ from .prediction import post_ops_prediction
 from .proposal_target import training_target_layers
 from .region_proposal import RegionProposal
 from .roi_pooling import RoiPoolingCropAndResize2
+from .trainable_common import check_train_flags
 
 __all__ = ['BaseFPN', 'RpnHead', 'ResnetV1Fpn']
 
@@ -427,20 +428,13 @@ class ResnetV1Fpn(BaseFPN):
                  train_neck=False, train_extractor=False):
         from .fpn_detector import ResNetFpnDetector, check_caller_f32_form
         check_caller_f32_form(f32_form)
-        if train_extractor and (dtype != torch.float32 or f32_form != 'exact'):
-            raise ValueError("ResnetV1Fpn: train_extractor=True needs dtype=torch.float32 and f32_form='exact' (the bottleneck "
-                             "backward has no float16 or split-precision form), got %s, %r" % (dtype, f32_form))
+        exact = lambda *flags: check_train_flags('ResnetV1Fpn', dtype, f32_form, *flags)
+        exact((train_extractor, 'train_extractor', 'the bottleneck backward has'))
         check_train_extractor(train_extractor, train_neck)
-        if train_neck and (dtype != torch.float32 or f32_form != 'exact'):
-            raise ValueError("ResnetV1Fpn: train_neck=True needs dtype=torch.float32 and f32_form='exact' (the neck's backward "
-                             "has no float16 or split-precision form), got %s, %r" % (dtype, f32_form))
+        exact((train_neck, 'train_neck', "the neck's backward has"))
         check_train_neck(train_neck, train_rpn_head, train_roi_head)
-        if train_roi_head and (dtype != torch.float32 or f32_form != 'exact'):
-            raise ValueError("ResnetV1Fpn: train_roi_head=True needs dtype=torch.float32 and f32_form='exact' (the Dense backward "
-                             "has no float16 or split-precision form), got %s, %r" % (dtype, f32_form))
-        if train_rpn_head and (dtype != torch.float32 or f32_form != 'exact'):
-            raise ValueError("ResnetV1Fpn: train_rpn_head=True needs dtype=torch.float32 and f32_form='exact' (the convolution "
-                             "backward has no float16 or split-precision form), got %s, %r" % (dtype, f32_form))
+        exact((train_roi_head, 'train_roi_head', 'the Dense backward has'),
+              (train_rpn_head, 'train_rpn_head', 'the convolution backward has'))
         if top_down_dims != 256 or tuple(roi_feature_size) != (roi_pool_size, roi_pool_size, top_down_dims):
             raise ValueError('ResnetV1Fpn: the dense kernels are built for 256 top-down channels and %dx%dx256 RoI features'
                              % (roi_pool_size, roi_pool_size))

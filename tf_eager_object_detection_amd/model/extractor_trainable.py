@@ -10,7 +10,7 @@ import torch
 
 from .. import ops
 from .fpn_detector import _conv_epi, _nhwc, _stem
-from .neck_trainable import _rows, neck_conv_flipped
+from .trainable_common import flipped_weight, in_param_layout, param_layouts, pointwise_backward, require_exact_f32
 
 STAGES = ('conv2', 'conv3', 'conv4', 'conv5')
 
@@ -18,11 +18,6 @@ STAGES = ('conv2', 'conv3', 'conv4', 'conv5')
 def block_layers(blk):
     """a bottleneck's convolutions in the order of its parameters: c1, c2, c3 (, short)"""
     return (blk.c1, blk.c2, blk.c3) + ((blk.short,) if blk.short is not None else ())
-
-
-def _weight2d(w):
-    """a [cout, cin, 1, 1] weight as the Dense backward's [cout, cin] (the same floats in either memory format)"""
-    return w.reshape(int(w.shape[0]), -1).contiguous()
 
 
 class _BlockTrainable(torch.autograd.Function):
@@ -34,7 +29,8 @@ class _BlockTrainable(torch.autograd.Function):
         c1     dw, db = dense_wgrad(da, x or xs, y_relu=a);   d1 = dense_dgrad(da, w1, y_relu=a)              (d1, d2, dx only when x
         short  dw, db = dense_wgrad(dy, x or xs, y_relu=y);   d2 = dense_dgrad(dy, ws, y_relu=y)               requires a gradient)
         dx = block_input_grad(d1, dy, y)  (identity shortcut)  or  block_input_grad(d1, d2=d2, stride, in_hw)  (convolutional one)
-    The forward's concatenated [w3 | ws] weight is a forward detail: the backward reads the two parameters themselves."""
+    Each 1x1 line is one trainable_common.pointwise_backward.  The forward's concatenated [w3 | ws] weight is a forward detail:
+    the backward reads the two parameters themselves."""
 
     @staticmethod
     def forward(ctx, blk, wf2, x, *params):
@@ -50,7 +46,7 @@ class _BlockTrainable(torch.autograd.Function):
         if wf2 is not None:                                                       # (None: no graph is being recorded)
             xn = _nhwc(x)
             ctx.stride, ctx.in_hw = stride, (int(xn.shape[1]), int(xn.shape[2]))
-            ctx.layouts = [(tuple(p.shape), tuple(p.stride())) for p in params]
+            ctx.layouts = param_layouts(params)
             ctx.save_for_backward(wf2, xn if stride == 1 else ops.stride_gather(xn, stride), _nhwc(a), _nhwc(b), _nhwc(y), *params)
         return y
 
@@ -65,29 +61,26 @@ class _BlockTrainable(torch.autograd.Function):
         need_dx = ctx.needs_input_grad[2]
         dy = _nhwc(dy)
         # c3, then c2 on the gradient that leaves c3 already gated by c2's ReLU
-        g3 = ops.dense_wgrad(_rows(dy), _rows(b), y_relu=_rows(y))
-        db_gated = ops.dense_dgrad(_rows(dy), _weight2d(weights[2]), y_relu=_rows(y), x_relu=_rows(b)).view(b.shape)
+        dw3, db3, db_gated = pointwise_backward(dy, b, weights[2], y_relu=y, x_relu=b)
         dw2, db2 = ops.conv3x3_wgrad_f32_levels([a], [db_gated])
         da = ops.conv3x3_dgrad_f32_levels([db_gated], weights[1], flipped=wf2)[0]
         # c1 and the shortcut convolution read the block's (subsampled) input
-        g1 = ops.dense_wgrad(_rows(da), _rows(xs), y_relu=_rows(a))
-        d1 = ops.dense_dgrad(_rows(da), _weight2d(weights[0]), y_relu=_rows(a)) if need_dx else None
-        grads = [g1, (ops._conv3x3_weight_grad(dw2, weights[1]), db2), g3]
-        dx = d2 = None
+        dw1, db1, d1 = pointwise_backward(da, xs, weights[0], y_relu=a, need_dx=need_dx)
+        grads = [(dw1, db1), (ops._conv3x3_weight_grad(dw2, weights[1]), db2), (dw3, db3)]
+        dx = None
         if n_params == 8:
-            grads.append(ops.dense_wgrad(_rows(dy), _rows(xs), y_relu=_rows(y)))
+            dws, dbs, d2 = pointwise_backward(dy, xs, weights[3], y_relu=y, need_dx=need_dx)
+            grads.append((dws, dbs))
             if need_dx:
-                d2 = ops.dense_dgrad(_rows(dy), _weight2d(weights[3]), y_relu=_rows(y)).view(xs.shape)
-                dx = ops.block_input_grad(d1.view(xs.shape), d2=d2, stride=ctx.stride, in_hw=ctx.in_hw)
+                dx = ops.block_input_grad(d1, d2=d2, stride=ctx.stride, in_hw=ctx.in_hw)
         elif need_dx:
-            dx = ops.block_input_grad(d1.view(xs.shape), dy=dy, y=y)
+            dx = ops.block_input_grad(d1, dy=dy, y=y)
         # in the order of the parameters, each gradient in its parameter's own shape and memory format (a [cout, cin, 1, 1] weight:
         # the same cout x cin floats in either format)
         d_params = []
         for i, (dw, db) in enumerate(grads):
             if dw.dim() == 2:
-                shape, stride = ctx.layouts[2 * i]
-                dw = torch.as_strided(dw, shape, stride, dw.storage_offset())
+                dw = in_param_layout(dw, ctx.layouts[2 * i])
             d_params += [dw, db]
         return (None, None, None if dx is None else dx.permute(0, 3, 1, 2)) + tuple(d_params)
 
@@ -98,7 +91,7 @@ def block_trainable(blk, x):
     if x.dtype != torch.float32 or ops.current_f32_form() != 'exact':
         raise ValueError("block_trainable needs a float32 map and f32_form='exact' (the bottleneck backward has no float16 or "
                          "split-precision form), got %s, %r" % (x.dtype, ops.current_f32_form()))
-    wf2 = neck_conv_flipped(blk.c2) if torch.is_grad_enabled() else None
+    wf2 = flipped_weight(blk.c2) if torch.is_grad_enabled() else None
     params = [p for conv in block_layers(blk) for p in (conv.weight, conv.bias)]
     return _BlockTrainable.apply(blk, wf2, x, *params)
 
@@ -106,8 +99,7 @@ def block_trainable(blk, x):
 def extractor_trainable(det, images_nhwc):
     """det.extractor(images_nhwc) with a backward pass into conv2..conv5: (C2, C3, C4, C5), bit-equal to extractor()'s.  The stem
     (conv1 + pooling) runs under no_grad as in extractor(): conv1 stays frozen."""
-    if det.dtype != torch.float32 or det.f32_form != 'exact':
-        raise ValueError("extractor_trainable needs dtype=torch.float32 and f32_form='exact' (got %s, %r)" % (det.dtype, det.f32_form))
+    require_exact_f32(det, 'extractor_trainable')
     with torch.no_grad():
         x = _stem(det.conv1, images_nhwc, det.dtype)
     outs = []

@@ -464,9 +464,8 @@ class ResNetFpnDetector(Detector):
         maps without train_neck) cost nothing more: fc1's input gradient -- a read of its 51 MB of weights -- is then never computed.  Features from
         ops.roi_pool_trainable require one: fc1's dense_dgrad produces the [n,P,P,C] gradient that odet_roi_pool_backward
         carries into the feature maps, where neck_trainable consumes it."""
-        if self.dtype != torch.float32 or self.f32_form != 'exact':
-            raise ValueError("roi_head_trainable needs dtype=torch.float32 and f32_form='exact' (got %s, %r)"
-                             % (self.dtype, self.f32_form))
+        from .trainable_common import require_exact_f32
+        require_exact_f32(self, 'roi_head_trainable')
         x = roi_features.reshape(roi_features.shape[0], -1).to(self.dtype)
         x = ops.dense_trainable(x, self.fc1.weight, self.fc1.bias, relu=True)
         x = ops.dense_trainable(x, self.fc2.weight, self.fc2.bias, relu=True)

@@ -6,25 +6,10 @@ with the level's other gradient terms folded in), the four 1x1 convolutions as t
 import torch
 
 from .. import ops
-from ..derived import derived
 from .fpn_detector import _conv_epi, _nhwc
+from .trainable_common import flipped_weight, in_param_layout, param_layouts, pointwise_backward, require_exact_f32
 
 _LAYERS = ('p5', 'l4', 'l3', 'l2', 's4', 's3', 's2')
-
-
-def neck_conv_flipped(conv, half=False):
-    """a 3x3 output convolution's weight flipped and transposed (ops.conv3x3_flipped_weight): the weight whose forward convolution is
-    the layer's input gradient; derived on the layer, rebuilt after an optimiser step.  `half`: times 0.5 -- s2's, so that the
-    convolution's result IS the gradient of l2's output (the merge's 0.5 applied: every product and every partial sum is halved
-    exactly, a power of two) and the finest level takes no elementwise pass of its own."""
-    if half:
-        return derived(conv, 'flip_half', (conv.weight,), lambda w: ops.conv3x3_flipped_weight(w).mul_(0.5))
-    return derived(conv, 'flip', (conv.weight,), ops.conv3x3_flipped_weight)
-
-
-def _rows(x):
-    """an NHWC map [B,H,W,C] as the Dense backward's [rows, C]"""
-    return x.view(-1, int(x.shape[3]))
 
 
 class _NeckTrainable(torch.autograd.Function):
@@ -32,12 +17,12 @@ class _NeckTrainable(torch.autograd.Function):
     s2..s4, which the forward has in memory anyway).  Backward, with dP2..dP6 arriving (any of them may be absent and drops its
     terms): s_k's dw / db and input gradient per level -> the cascade from fine to coarse, h_k = the gradient of level k's
     lateral output = the gradient of the resized map one level up:
-        h2 = s2's input gradient on the HALVED flipped weight (neck_conv_flipped(half=True): no elementwise pass)
+        h2 = s2's input gradient on the HALVED flipped weight (trainable_common.flipped_weight(half=True): no elementwise pass)
         h3 = fpn_topdown_backward(h2, base = s3's input gradient, out_scale = 0.5)
         h4 = fpn_topdown_backward(h3, base = s4's input gradient, out_scale = 0.5)
         g5 = fpn_topdown_backward(h4, base = dP5, sub = dP6, out_scale = 1)
-    -> the 1x1 layers' dw / db as ops.dense_wgrad(h_k, C_k) (p5: g5, C5), and ops.dense_dgrad into a C_k only where that map
-    requires a gradient."""
+    -> the 1x1 layers as Dense layers over pixels (trainable_common.pointwise_backward): dw / db from (h_k, C_k) (p5: g5, C5), and
+    the input gradient into a C_k only where that map requires one."""
 
     @staticmethod
     def forward(ctx, det, wf4, wf3, wf2h, c2, c3, c4, c5, *params):
@@ -48,7 +33,7 @@ class _NeckTrainable(torch.autograd.Function):
         m3 = det._lateral_merge(m4, det.l3, c3)
         m2 = det._lateral_merge(m3, det.l2, c2)
         outs = (_conv_epi(det.s2, m2), _conv_epi(det.s3, m3), _conv_epi(det.s4, m4), p5, p6)
-        ctx.layouts = [(tuple(p.shape), tuple(p.stride())) for p in params]
+        ctx.layouts = param_layouts(params)
         ctx.save_for_backward(wf4, wf3, wf2h, *[_nhwc(t) for t in (c2, c3, c4, c5, m2, m3, m4)], *params)
         return outs
 
@@ -83,20 +68,16 @@ class _NeckTrainable(torch.autograd.Function):
         for i, (name, c) in enumerate((('l2', c2), ('l3', c3), ('l4', c4), ('p5', c5))):
             g, dx = hs[name], None
             if g is not None:
-                grads[name] = ops.dense_wgrad(_rows(g), _rows(c))
-                if ctx.needs_input_grad[4 + i]:
-                    w = weights[name]
-                    dx = ops.dense_dgrad(_rows(g), w.reshape(int(w.shape[0]), -1).contiguous())
-                    dx = dx.view(c.shape).permute(0, 3, 1, 2)
-            d_c.append(dx)
+                dw, db, dx = pointwise_backward(g, c, weights[name], need_dx=ctx.needs_input_grad[4 + i])
+                grads[name] = (dw, db)
+            d_c.append(None if dx is None else dx.permute(0, 3, 1, 2))
         # in the order of the parameters, each gradient in its parameter's own shape and memory format (a [256, cin, 1, 1] weight:
         # the same 256 x cin floats in either format)
         d_params = []
         for i, name in enumerate(_LAYERS):
             dw, db = grads.get(name, (None, None))
             if dw is not None and dw.dim() == 2:
-                shape, stride = ctx.layouts[2 * i]
-                dw = torch.as_strided(dw, shape, stride, dw.storage_offset())
+                dw = in_param_layout(dw, ctx.layouts[2 * i])
             d_params += [dw, db]
         return (None, None, None, None) + tuple(d_c) + tuple(d_params)
 
@@ -105,10 +86,9 @@ def neck_trainable(det, c_list):
     """det.neck(c_list) with a backward pass into p5, l4, l3, l2, s4, s3 and s2: `.backward()` leaves the fourteen parameters'
     gradients in their own shapes and memory formats and carries a gradient into those maps of c_list that require one (the
     models' own maps do with train_extractor: model/extractor_trainable.py)."""
-    if det.dtype != torch.float32 or det.f32_form != 'exact':
-        raise ValueError("neck_trainable needs dtype=torch.float32 and f32_form='exact' (got %s, %r)" % (det.dtype, det.f32_form))
+    require_exact_f32(det, 'neck_trainable')
     flips = (None, None, None)
     if torch.is_grad_enabled():
-        flips = (neck_conv_flipped(det.s4), neck_conv_flipped(det.s3), neck_conv_flipped(det.s2, half=True))
+        flips = (flipped_weight(det.s4), flipped_weight(det.s3), flipped_weight(det.s2, half=True))
     params = [p for name in _LAYERS for p in (getattr(det, name).weight, getattr(det, name).bias)]
     return _NeckTrainable.apply(det, *flips, *c_list, *params)

@@ -5,14 +5,8 @@ ops.conv3x3_wgrad_f32_levels over all levels in one call, its input gradient as 
 import torch
 
 from .. import ops
-from ..derived import derived
 from .fpn_detector import _nhwc, _no_kernel, _own_conv3x3, rpn_pair_padded, rpn_pair_weights
-
-
-def rpn_conv_flipped(m):
-    """rpn_conv's weight flipped and transposed (ops.conv3x3_flipped_weight, 4.7 MB): the weight whose forward convolution is the
-    3x3 layer's input gradient; derived on the module, rebuilt after an optimiser step"""
-    return derived(m, 'rpn_flip', (m.rpn_conv.weight,), ops.conv3x3_flipped_weight)
+from .trainable_common import flipped_weight, in_param_layout, param_layouts, require_exact_f32
 
 
 class _RpnHeadTrainable(torch.autograd.Function):
@@ -43,7 +37,7 @@ class _RpnHeadTrainable(torch.autograd.Function):
             off += r
             aoff += r // B * A
         ctx.A, ctx.rows, ctx.B, ctx.n = A, rows, B, len(xs)
-        ctx.pair_layouts = [(tuple(w.shape), tuple(w.stride())) for w in (score_w, bbox_w)]
+        ctx.pair_layouts = param_layouts((score_w, bbox_w))
         ctx.save_for_backward(hbuf, wpad, wflip, conv_w, *xs)
         return scores, deltas
 
@@ -75,8 +69,7 @@ class _RpnHeadTrainable(torch.autograd.Function):
             dxs = [g if need else None for g, need in zip(got, ctx.needs_input_grad[10:])]
         n2, n6 = 2 * A, 6 * A
         # the pair's rows in the two parameters' own shapes and strides ([n, 512, 1, 1]: the same n x 512 floats in either format)
-        dws = [torch.as_strided(g, shape, stride, g.storage_offset())
-               for g, (shape, stride) in zip((dwp[:n2], dwp[n2:n6]), ctx.pair_layouts)]
+        dws = [in_param_layout(g, layout) for g, layout in zip((dwp[:n2], dwp[n2:n6]), ctx.pair_layouts)]
         return (ops._conv3x3_weight_grad(dw3, conv_w), db3, dws[0], dbp[:n2], dws[1], dbp[n2:n6], None, None, None, None) + tuple(dxs)
 
 
@@ -85,14 +78,13 @@ def rpn_trainable(det, p_list):
     gradients in their own shapes and memory formats -- the pair's from the padded [64, 512] contraction, handed out as row
     slices the way _FinalTrainable does -- and carries a gradient into those maps of p_list that require one (the models' own
     maps do with train_neck=True: neck_trainable consumes it)."""
-    if det.dtype != torch.float32 or det.f32_form != 'exact':
-        raise ValueError("rpn_trainable needs dtype=torch.float32 and f32_form='exact' (got %s, %r)" % (det.dtype, det.f32_form))
+    require_exact_f32(det, 'rpn_trainable')
     p0 = p_list[0]
     if not _own_conv3x3(det.rpn_conv, p0) or det.rpn_conv.out_channels % 256:
         raise _no_kernel('RpnHead', det.rpn_conv, p0)
     w, b = rpn_pair_weights(det)
-    # (the flipped weight only where the backward pass will compute an input gradient)
-    wflip = rpn_conv_flipped(det) if torch.is_grad_enabled() and any(p.requires_grad for p in p_list) else None
+    # (the flipped weight, 4.7 MB, only where the backward pass will compute an input gradient)
+    wflip = flipped_weight(det.rpn_conv) if torch.is_grad_enabled() and any(p.requires_grad for p in p_list) else None
     return _RpnHeadTrainable.apply(det.rpn_conv.weight, det.rpn_conv.bias, det.rpn_score.weight, det.rpn_score.bias,
                                    det.rpn_bbox.weight, det.rpn_bbox.bias, rpn_pair_padded(det, w), b, wflip, det.A,
                                    *[_nhwc(p) for p in p_list])

@@ -9,7 +9,7 @@ import torch
 
 from .. import ops
 from .fpn_detector import _nhwc, _no_kernel, _own_conv3x3
-from .neck_trainable import neck_conv_flipped
+from .trainable_common import flipped_weight, require_exact_f32
 
 FIRST_TRAINED = 4                        # convs[4] = block3_conv1: blocks 1-2 (convs[0..3]) are frozen, :265-288
 
@@ -23,8 +23,7 @@ def extractor_trainable(det, images_nhwc):
     """det.features(images_nhwc) with a backward pass into block3_conv1 .. block5_conv3, bit-equal to it.  Blocks 1-2 run under
     no_grad on features()' launches: the backward stops at block3_conv1's weight gradient (its input requires no gradient, so no
     input gradient is computed there and none through block1_pool / block2_pool)."""
-    if det.dtype != torch.float32 or det.f32_form != 'exact':
-        raise ValueError("extractor_trainable needs dtype=torch.float32 and f32_form='exact' (got %s, %r)" % (det.dtype, det.f32_form))
+    require_exact_f32(det, 'extractor_trainable')
     plan = det._layer_plan()
     with torch.no_grad():
         x = det._first_conv(images_nhwc)
@@ -39,7 +38,7 @@ def extractor_trainable(det, images_nhwc):
         if not _own_conv3x3(conv, x.permute(0, 3, 1, 2)) or conv.bias is None:
             raise _no_kernel('3x3 convolution', conv, x)
         # (the flipped weight only where the backward pass will compute an input gradient)
-        wf = neck_conv_flipped(conv) if torch.is_grad_enabled() and x.requires_grad else None
+        wf = flipped_weight(conv) if torch.is_grad_enabled() and x.requires_grad else None
         if pooled:
             x = ops.conv3x3_relu_pool_trainable(x, conv.weight, conv.bias, flipped=wf)
         else:
@@ -51,8 +50,7 @@ def roi_head_trainable(det, roi_features, keep_prob=1.0, seed=0, image_id=0):
     """det.roi_head(roi_features) with a backward pass into fc1, fc2, score and bbox, and tf.nn.dropout(keep_prob) behind fc1
     (Philox stream 6) and fc2 (stream 7) as the reference trains the head (:250-253); keep_prob 1: bit-equal to roi_head.  Features
     that require a gradient (ops.roi_pool_trainable's, with a trainable extractor) get one: fc1's dense_dgrad."""
-    if det.dtype != torch.float32 or det.f32_form != 'exact':
-        raise ValueError("roi_head_trainable needs dtype=torch.float32 and f32_form='exact' (got %s, %r)" % (det.dtype, det.f32_form))
+    require_exact_f32(det, 'roi_head_trainable')
     x = roi_features.reshape(roi_features.shape[0], -1).to(det.dtype)            # Flatten() of NHWC crops
     x = ops.dense_trainable(x, det.fc1.weight, det.fc1.bias, relu=True)
     x = ops.dropout_trainable(x, keep_prob, seed, image_id, ops.DROPOUT_STREAM_FC1)

@@ -517,6 +517,41 @@ def fpn_topdown_merge(top, lateral, out=None):
     return out
 
 
+def _grad_f32(who, what, named):
+    """the first two rules of every backward front, in this order: the named operands are float32 tensors, the current f32 form is
+    'exact' (``what``: the backward the messages name)"""
+    for name, t in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError('%s: %s must be a float32 tensor (the %s has no float16 form), got %s'
+                             % (who, name, what, getattr(t, 'dtype', type(t).__name__)))
+    if current_f32_form() != 'exact':
+        raise ValueError("%s: the %s runs only under f32_form 'exact' (no split-precision backward), not %r"
+                         % (who, what, current_f32_form()))
+
+
+def _grad_operands(who, what, named, ndim=None):
+    """the ONE front of the backward ops' operands (``named``: (name, tensor) pairs): _grad_f32, then contiguous and of rank
+    ``ndim`` where one is given.  The caller goes on with its own shape rules and ends with _grad_on_gpu: dtype, form, rank and
+    contiguity, shapes, device -- the same precedence in every front."""
+    _grad_f32(who, what, named)
+    how = {None: 'contiguous', 2: 'a contiguous 2-D tensor', 4: 'a contiguous NHWC tensor [B,H,W,C]'}[ndim]
+    for name, t in named:
+        if (ndim is not None and t.dim() != ndim) or not t.is_contiguous():
+            raise ValueError('%s: %s must be %s' % (who, name, how))
+
+
+def _grad_on_gpu(who, named):
+    for name, t in named:
+        if not t.is_cuda:
+            raise ValueError('%s: %s must be a GPU tensor' % (who, name))
+
+
+def _grad_workspace(query_symbol, query_args, device):
+    """the split-K workspace of a gradient GEMM, sized by the library's own query -> (pointer or None, bytes)"""
+    n = int(getattr(L.lib(), query_symbol)(*query_args))
+    return (C.c_void_p(L.workspace(n, device).data_ptr()), n) if n else (None, 0)
+
+
 def fpn_topdown_backward(fine, top_hw, base=None, sub=None, out_scale=1.0, out=None):
     """The backward of the top-down merge's resize with the coarse map's other gradient terms folded in
     (odet_fpn_topdown_backward_f32; resnet_fpn.py:385-398 in reverse): d_top [B,h,w,C] = out_scale * (base + sub placed at the even
@@ -528,16 +563,7 @@ def fpn_topdown_backward(fine, top_hw, base=None, sub=None, out_scale=1.0, out=N
     named = [(n, t) for n, t in (('fine', fine), ('base', base), ('sub', sub)) if t is not None]
     if not named:
         raise ValueError('%s: at least one of fine, base and sub is needed' % who)
-    for name, t in named:
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise ValueError('%s: %s must be a float32 tensor (the neck backward has no float16 form), got %s'
-                             % (who, name, getattr(t, 'dtype', type(t).__name__)))
-    if current_f32_form() != 'exact':
-        raise ValueError("%s: the neck backward runs only under f32_form 'exact' (no split-precision backward), not %r"
-                         % (who, current_f32_form()))
-    for name, t in named:
-        if t.dim() != 4 or not t.is_contiguous():
-            raise ValueError('%s: %s must be a contiguous NHWC tensor [B,H,W,C]' % (who, name))
+    _grad_operands(who, 'neck backward', named, ndim=4)
     h, w = int(top_hw[0]), int(top_hw[1])
     B, Cc = int(named[0][1].shape[0]), int(named[0][1].shape[3])
     if h < 1 or w < 1 or Cc < 4 or Cc % 4:
@@ -550,9 +576,7 @@ def fpn_topdown_backward(fine, top_hw, base=None, sub=None, out_scale=1.0, out=N
         elif tuple(t.shape) != want[name]:
             raise ValueError('%s: %s %s does not go with top_hw %s and %s %s (expected %s)'
                              % (who, name, tuple(t.shape), (h, w), named[0][0], tuple(named[0][1].shape), want[name]))
-    for name, t in named:
-        if not t.is_cuda:
-            raise ValueError('%s: %s must be a GPU tensor' % (who, name))
+    _grad_on_gpu(who, named)
     out = _out(out, (B, h, w, Cc), torch.float32, named[0][1].device)
     H, W = (int(fine.shape[1]), int(fine.shape[2])) if fine is not None else (h, w)
     L.call('odet_fpn_topdown_backward_f32', L.dptr(fine), H, W, L.dptr(base), L.dptr(sub), float(out_scale), L.dptr(out), h, w, B,
@@ -560,20 +584,8 @@ def fpn_topdown_backward(fine, top_hw, base=None, sub=None, out_scale=1.0, out=N
     return out
 
 
-def _block_grad_maps(who, named):
-    """the checks stride_gather / block_input_grad share (the style of _conv_grad_maps): float32 only, the exact form only,
-    contiguous NHWC tensors with a positive map and C a positive multiple of 4; the caller checks the shapes against each other,
-    then _conv_grad_on_gpu"""
-    for name, t in named:
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise ValueError('%s: %s must be a float32 tensor (the bottleneck backward has no float16 form), got %s'
-                             % (who, name, getattr(t, 'dtype', type(t).__name__)))
-    if current_f32_form() != 'exact':
-        raise ValueError("%s: the bottleneck backward runs only under f32_form 'exact' (no split-precision backward), not %r"
-                         % (who, current_f32_form()))
-    for name, t in named:
-        if t.dim() != 4 or not t.is_contiguous():
-            raise ValueError('%s: %s must be a contiguous NHWC tensor [B,H,W,C]' % (who, name))
+def _positive_maps(who, named):
+    """the first shape rule of stride_gather / block_input_grad: a positive map size and C a positive multiple of 4"""
     for name, t in named:
         if int(t.shape[1]) < 1 or int(t.shape[2]) < 1 or int(t.shape[3]) < 4 or int(t.shape[3]) % 4:
             raise ValueError('%s: %s %s must have a positive map size and C a positive multiple of 4' % (who, name, tuple(t.shape)))
@@ -590,9 +602,10 @@ def stride_gather(x, stride, out=None):
     strided 1x1 convolution (resnet_fpn.py:154-205: the first block of conv3..conv5).  ``x`` [B,H,W,C] contiguous NHWC float32 on
     the GPU, C % 4 == 0, stride 1 or 2 -> [B, ceil(H/stride), ceil(W/stride), C].  float32, f32_form 'exact' only."""
     who = 'stride_gather'
-    _block_grad_maps(who, [('x', x)])
+    _grad_operands(who, 'bottleneck backward', [('x', x)], ndim=4)
+    _positive_maps(who, [('x', x)])
     stride = _stride_1_or_2(who, stride)
-    _conv_grad_on_gpu(who, [('x', x)])
+    _grad_on_gpu(who, [('x', x)])
     B, H, W, Cc = (int(v) for v in x.shape)
     out = _out(out, (B, (H - 1) // stride + 1, (W - 1) // stride + 1, Cc), torch.float32, x.device)
     L.call('odet_stride_gather_f32', L.dptr(x), B, H, W, Cc, stride, L.dptr(out), L.stream())
@@ -612,7 +625,8 @@ def block_input_grad(d1, dy=None, y=None, d2=None, stride=1, in_hw=None, out=Non
         raise ValueError('%s: dy and y come together (the identity form) or not at all (the convolutional-shortcut form)' % who)
     identity = dy is not None
     named = [(n, t) for n, t in (('d1', d1), ('dy', dy), ('y', y), ('d2', d2)) if t is not None or n == 'd1']
-    _block_grad_maps(who, named)
+    _grad_operands(who, 'bottleneck backward', named, ndim=4)
+    _positive_maps(who, named)
     stride = _stride_1_or_2(who, stride)
     if identity and (d2 is not None or stride != 1):
         raise ValueError('%s: the identity form (dy, y, d1) takes no d2 and stride 1 only' % who)
@@ -627,25 +641,10 @@ def block_input_grad(d1, dy=None, y=None, d2=None, stride=1, in_hw=None, out=Non
     H, W = int(in_hw[0]), int(in_hw[1])
     if H < 1 or W < 1 or ((H - 1) // stride + 1, (W - 1) // stride + 1) != (Ho, Wo):
         raise ValueError('%s: in_hw %s at stride %d does not go with d1 %s' % (who, (H, W), stride, (B, Ho, Wo, Cc)))
-    _conv_grad_on_gpu(who, named)
+    _grad_on_gpu(who, named)
     out = _out(out, (B, H, W, Cc), torch.float32, d1.device)
     L.call('odet_block_input_grad_f32', L.dptr(dy), L.dptr(y), L.dptr(d1), L.dptr(d2), L.dptr(out), B, H, W, Cc, stride, L.stream())
     return out
-
-
-def _vgg_grad_f32(who, what, named):
-    """the checks relu_maxpool2_backward / dropout share (the style of _conv_grad_maps): float32 only, the exact form only,
-    contiguous tensors; the caller checks the shapes, then _conv_grad_on_gpu"""
-    for name, t in named:
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise ValueError('%s: %s must be a float32 tensor (the %s has no float16 form), got %s'
-                             % (who, name, what, getattr(t, 'dtype', type(t).__name__)))
-    if current_f32_form() != 'exact':
-        raise ValueError("%s: the %s runs only under f32_form 'exact' (no split-precision backward), not %r"
-                         % (who, what, current_f32_form()))
-    for name, t in named:
-        if not t.is_contiguous():
-            raise ValueError('%s: %s must be contiguous' % (who, name))
 
 
 def relu_maxpool2_backward(z, bias, dpool, out=None):
@@ -656,7 +655,7 @@ def relu_maxpool2_backward(z, bias, dpool, out=None):
     Contiguous NHWC float32 GPU tensors, C % 4 == 0.  float32, f32_form 'exact' only."""
     who = 'relu_maxpool2_backward'
     named = [('z', z), ('bias', bias), ('dpool', dpool)]
-    _vgg_grad_f32(who, 'max-pooling backward', named)
+    _grad_operands(who, 'max-pooling backward', named)
     if z.dim() != 4 or int(z.shape[1]) < 1 or int(z.shape[2]) < 1 or int(z.shape[3]) < 4 or int(z.shape[3]) % 4:
         raise ValueError('%s: z %s must be an NHWC tensor [B,H,W,C] with a positive map size and C a positive multiple of 4'
                          % (who, tuple(z.shape)))
@@ -666,7 +665,7 @@ def relu_maxpool2_backward(z, bias, dpool, out=None):
     if tuple(dpool.shape) != (B, (H + 1) // 2, (W + 1) // 2, Cc):
         raise ValueError('%s: dpool %s does not go with z %s (the pooled map is %s)'
                          % (who, tuple(dpool.shape), tuple(z.shape), (B, (H + 1) // 2, (W + 1) // 2, Cc)))
-    _conv_grad_on_gpu(who, named)
+    _grad_on_gpu(who, named)
     out = _out(out, (B, H, W, Cc), torch.float32, z.device)
     L.call('odet_relu_maxpool2_backward_f32', L.dptr(z), L.dptr(bias), L.dptr(dpool), L.dptr(out), B, H, W, Cc, L.stream())
     return out
@@ -676,14 +675,14 @@ DROPOUT_STREAM_FC1, DROPOUT_STREAM_FC2 = 6, 7           # the Philox streams of 
 
 
 def _dropout(sym, who, x, keep_prob, seed, image_id, stream_id, out):
-    _vgg_grad_f32(who, 'dropout', [('x' if sym == 'odet_dropout_f32' else 'dy', x)])
+    _grad_operands(who, 'dropout', [('x' if sym == 'odet_dropout_f32' else 'dy', x)])
     keep_prob = float(keep_prob)
     if not 0.0 < keep_prob <= 1.0:
         raise ValueError('%s: keep_prob must be in (0, 1], got %r' % (who, keep_prob))
     seed, image_id, stream_id = int(seed), int(image_id), int(stream_id)
     if not 0 <= seed < 1 << 64 or not 0 <= stream_id < 1 << 32:
         raise ValueError('%s: seed must be in [0, 2^64) and stream_id in [0, 2^32), got %d, %d' % (who, seed, stream_id))
-    _conv_grad_on_gpu(who, [('x', x)])
+    _grad_on_gpu(who, [('x', x)])
     out = _out(out, tuple(x.shape), torch.float32, x.device)
     L.call(sym, L.dptr(x), L.dptr(out), x.numel(), keep_prob, seed, image_id & 0xFFFFFFFF, stream_id, L.stream())
     return out
@@ -713,7 +712,7 @@ class _DropoutTrainable(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        return dropout_backward(dy if dy.is_contiguous() else dy.contiguous(), *ctx.args), None, None, None, None
+        return dropout_backward(dy.contiguous(), *ctx.args), None, None, None, None
 
 
 def dropout_trainable(x, keep_prob, seed, image_id, stream_id):
@@ -721,7 +720,7 @@ def dropout_trainable(x, keep_prob, seed, image_id, stream_id):
     ``x`` itself, as tf.nn.dropout does."""
     if float(keep_prob) == 1.0:
         return x
-    return _DropoutTrainable.apply(x if x.is_contiguous() else x.contiguous(), float(keep_prob), int(seed), int(image_id),
+    return _DropoutTrainable.apply(x.contiguous(), float(keep_prob), int(seed), int(image_id),
                                    int(stream_id))
 
 
@@ -1119,22 +1118,10 @@ def dense(x, weight, bias=None, relu=False, out=None):
 
 
 def _dense_grad_args(who, dy, other, other_name, other_cols, y_relu):
-    """the checks dense_dgrad / dense_wgrad share (the style of _pw_args): float32 only, the exact form only, contiguous 2-D GPU
-    tensors, the kernels' shape rules -> (rows, cout)"""
+    """the front dense_dgrad / dense_wgrad share: _grad_operands on 2-D tensors, the kernels' shape rules, _grad_on_gpu ->
+    (rows, cin, cout)"""
     named = [('dy', dy), (other_name, other)] + ([('y_relu', y_relu)] if y_relu is not None else [])
-    for name, t in named:
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise ValueError('%s: %s must be a float32 tensor (the Dense backward has no float16 form), got %s'
-                             % (who, name, getattr(t, 'dtype', type(t).__name__)))
-    if current_f32_form() != 'exact':
-        raise ValueError("%s: the Dense backward runs only under f32_form 'exact' (no split-precision backward), not %r"
-                         % (who, current_f32_form()))
-    for name, t in named:
-        if t.dim() != 2 or not t.is_contiguous():
-            raise ValueError('%s: %s must be a contiguous 2-D tensor' % (who, name))
-    for name, t in named:
-        if not t.is_cuda:
-            raise ValueError('%s: %s must be a GPU tensor' % (who, name))
+    _grad_operands(who, 'Dense backward', named, ndim=2)
     rows, cout = int(dy.shape[0]), int(dy.shape[1])
     if y_relu is not None and tuple(y_relu.shape) != (rows, cout):
         raise ValueError('%s: y_relu must have the shape of dy %s, got %s' % (who, (rows, cout), tuple(y_relu.shape)))
@@ -1144,15 +1131,8 @@ def _dense_grad_args(who, dy, other, other_name, other_cols, y_relu):
     if rows < 1 or cin % 32 or cin < 64 or cout % 64 or cout < 64:
         raise ValueError('%s: rows %d must be positive, cin %d a multiple of 32 (>= 64), cout %d a multiple of 64'
                          % (who, rows, cin, cout))
+    _grad_on_gpu(who, named)
     return rows, cin, cout
-
-
-def _dense_grad_workspace(wgrad, rows, cin, cout, device):
-    n = int(L.lib().odet_dense_grad_workspace_bytes(wgrad, rows, cin, cout))
-    if n == 0:
-        return None, 0
-    ws = L.workspace(n, device)
-    return C.c_void_p(ws.data_ptr()), n
 
 
 def dense_dgrad(dy, weight, y_relu=None, x_relu=None, out=None):
@@ -1164,7 +1144,7 @@ def dense_dgrad(dy, weight, y_relu=None, x_relu=None, out=None):
                                or tuple(x_relu.shape) != (rows, cin) or not x_relu.is_contiguous()):
         raise ValueError('dense_dgrad: x_relu must be a contiguous float32 GPU tensor of shape %s' % ((rows, cin),))
     out = _out(out, (rows, cin), torch.float32, dy.device)
-    wsp, wsn = _dense_grad_workspace(0, rows, cin, cout, dy.device)
+    wsp, wsn = _grad_workspace('odet_dense_grad_workspace_bytes', (0, rows, cin, cout), dy.device)
     L.call('odet_dense_dgrad_f32', L.dptr(dy), L.dptr(weight), L.dptr(y_relu), L.dptr(x_relu), L.dptr(out), rows, cin, cout,
            wsp, wsn, L.stream())
     return out
@@ -1176,7 +1156,7 @@ def dense_wgrad(dy, x, y_relu=None, with_bias=True, out=None):
     rows, cin, cout = _dense_grad_args('dense_wgrad', dy, x, 'x', lambda r, c: r, y_relu)
     dw = _out(out, (cout, cin), torch.float32, dy.device)
     db = torch.empty((cout,), dtype=torch.float32, device=dy.device) if with_bias else None
-    wsp, wsn = _dense_grad_workspace(1, rows, cin, cout, dy.device)
+    wsp, wsn = _grad_workspace('odet_dense_grad_workspace_bytes', (1, rows, cin, cout), dy.device)
     L.call('odet_dense_wgrad_f32', L.dptr(dy), L.dptr(x), L.dptr(y_relu), L.dptr(dw), L.dptr(db), rows, cin, cout, wsp, wsn,
            L.stream())
     return dw, db
@@ -1197,7 +1177,7 @@ class _DenseTrainable(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         x, weight, y = ctx.saved_tensors
-        dy = dy if dy.is_contiguous() else dy.contiguous()
+        dy = dy.contiguous()
         dx = dw = db = None
         if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
             dw, db = dense_wgrad(dy, x, y, with_bias=ctx.has_bias and ctx.needs_input_grad[2])
@@ -1211,32 +1191,22 @@ def dense_trainable(x, weight, bias, relu=False):
     """ops.dense with a backward pass (float32, f32_form 'exact'): the forward is `dense`, bit for bit; `.backward()` leaves
     weight.grad [cout, cin] and bias.grad [cout] contiguous in the variables' shapes (what training.train_step takes), and
     computes the input gradient only when x requires one."""
-    if x.dim() != 2 or x.dtype != torch.float32 or weight.dtype != torch.float32 or weight.dim() != 2 or not weight.is_contiguous():
-        raise ValueError('dense_trainable: x [rows, cin] and weight [cout, cin] must be float32, weight contiguous')
-    if current_f32_form() != 'exact':
-        raise ValueError("dense_trainable: the Dense backward runs only under f32_form 'exact', not %r" % current_f32_form())
-    return _DenseTrainable.apply(x if x.is_contiguous() else x.contiguous(), weight, bias, bool(relu))
+    _grad_f32('dense_trainable', 'Dense backward', [('x', x), ('weight', weight)])
+    if x.dim() != 2 or weight.dim() != 2 or not weight.is_contiguous():
+        raise ValueError('dense_trainable: x must be [rows, cin] and weight a contiguous [cout, cin]')
+    return _DenseTrainable.apply(x.contiguous(), weight, bias, bool(relu))
 
 
 def _conv_grad_maps(who, named_lists):
-    """the checks the 3x3 convolution's backward fronts share (the style of _dense_grad_args): float32 only, the exact form only,
-    contiguous NHWC GPU tensors of one batch size, 1..MAX_LEVELS of them, the lists equally long and shaped level by level ->
-    (levels, batch, the named tensors for _conv_grad_on_gpu, which the caller runs after its shape rules)"""
+    """the front the 3x3 convolution's backward ops share: 1..MAX_LEVELS maps, the lists equally long, _grad_operands on every map,
+    one batch size and the lists shaped level by level -> (levels, batch, the named tensors for _grad_on_gpu, which the caller
+    runs after its shape rules)"""
     lists = [(name, ts) for name, ts in named_lists if ts is not None]
     n = len(lists[0][1])
     if not 1 <= n <= MAX_LEVELS or any(len(ts) != n for _, ts in lists):
         raise ValueError('%s: between 1 and %d maps expected, as many in every list' % (who, MAX_LEVELS))
     every = [('%s[%d]' % (name, i), t) for name, ts in lists for i, t in enumerate(ts) if t is not None]
-    for name, t in every:
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise ValueError('%s: %s must be a float32 tensor (the convolution backward has no float16 form), got %s'
-                             % (who, name, getattr(t, 'dtype', type(t).__name__)))
-    if current_f32_form() != 'exact':
-        raise ValueError("%s: the convolution backward runs only under f32_form 'exact' (no split-precision backward), not %r"
-                         % (who, current_f32_form()))
-    for name, t in every:
-        if t.dim() != 4 or not t.is_contiguous():
-            raise ValueError('%s: %s must be a contiguous NHWC tensor [B,H,W,C]' % (who, name))
+    _grad_operands(who, 'convolution backward', every, ndim=4)
     B = int(lists[0][1][0].shape[0])
     for i in range(n):
         hw = tuple(lists[0][1][i].shape[:3])
@@ -1246,12 +1216,6 @@ def _conv_grad_maps(who, named_lists):
                 raise ValueError('%s: %s[%d] %s does not go with %s[%d] %s (one batch size, one channel count per list)'
                                  % (who, name, i, tuple(ts[i].shape), lists[0][0], i, tuple(lists[0][1][i].shape)))
     return n, B, every
-
-
-def _conv_grad_on_gpu(who, every):
-    for name, t in every:
-        if not t.is_cuda:
-            raise ValueError('%s: %s must be a GPU tensor' % (who, name))
 
 
 def conv3x3_wgrad_f32_levels(xs, dys, y_relus=None, with_bias=True, out=None):
@@ -1268,7 +1232,7 @@ def conv3x3_wgrad_f32_levels(xs, dys, y_relus=None, with_bias=True, out=None):
         raise ValueError('%s: y_relus must have the shapes of dys' % who)
     if cin % 32 or cout % 64:
         raise ValueError('%s: cin %d must be a multiple of 32, cout %d a multiple of 64' % (who, cin, cout))
-    _conv_grad_on_gpu(who, every)
+    _grad_on_gpu(who, every)
     lv = (L.OdetConvGradLevel * n)()
     for i in range(n):
         y = y_relus[i] if y_relus is not None else None
@@ -1277,10 +1241,8 @@ def conv3x3_wgrad_f32_levels(xs, dys, y_relus=None, with_bias=True, out=None):
     dev = xs[0].device
     dw = _out(out, (cout, 3, 3, cin), torch.float32, dev)
     db = torch.empty((cout,), dtype=torch.float32, device=dev) if with_bias else None
-    nbytes = int(L.lib().odet_conv3x3_wgrad_workspace_bytes(lv, n, B, cin, cout))
-    ws = L.workspace(nbytes, dev) if nbytes else None
-    L.call('odet_conv3x3_wgrad_f32_levels', lv, n, L.dptr(dw), L.dptr(db), B, cin, cout,
-           C.c_void_p(ws.data_ptr()) if nbytes else None, nbytes, L.stream())
+    wsp, wsn = _grad_workspace('odet_conv3x3_wgrad_workspace_bytes', (lv, n, B, cin, cout), dev)
+    L.call('odet_conv3x3_wgrad_f32_levels', lv, n, L.dptr(dw), L.dptr(db), B, cin, cout, wsp, wsn, L.stream())
     return dw, db
 
 
@@ -1308,7 +1270,7 @@ def conv3x3_dgrad_f32_levels(dzs, weight, outs=None, flipped=None):
     if int(weight.shape[0]) != cout or cout % 32 or cin % 64 or cin < 64:
         raise ValueError('%s: cout %d must be a multiple of 32 (the weight has %d output channels), cin %d a multiple of 64'
                          % (who, cout, int(weight.shape[0]), cin))
-    _conv_grad_on_gpu(who, every + [('weight', weight)])
+    _grad_on_gpu(who, every + [('weight', weight)])
     wf = conv3x3_flipped_weight(weight) if flipped is None else flipped
     if tuple(wf.shape) != (cin, 3, 3, cout) or not wf.is_contiguous():
         raise ValueError('%s: flipped must be a contiguous [cin,3,3,cout] tensor' % who)
@@ -1332,7 +1294,7 @@ class _Conv3x3Trainable(torch.autograd.Function):
     def backward(ctx, *dys):
         weight, xs = ctx.saved_tensors[0], list(ctx.saved_tensors[1:1 + ctx.n])
         ys = list(ctx.saved_tensors[1 + ctx.n:]) if ctx.relu else None
-        dys = [d if d.is_contiguous() else d.contiguous() for d in dys]
+        dys = [d.contiguous() for d in dys]
         dw = db = None
         dxs = [None] * ctx.n
         need_b = ctx.has_bias and ctx.needs_input_grad[1]
@@ -1372,12 +1334,9 @@ def conv3x3_trainable_levels(xs, weight, bias, relu=False, flipped=None):
     `.backward()` leaves weight.grad in the parameter's own shape and memory format and bias.grad [cout], from ONE wgrad launch
     over all levels (plus its reduce and bias launches), and computes input gradients only when a map requires one (``flipped``: a
     caller's cached conv3x3_flipped_weight for them; without it the backward pass flips the weight itself)."""
-    if current_f32_form() != 'exact':
-        raise ValueError("conv3x3_trainable_levels: the convolution backward runs only under f32_form 'exact', not %r"
-                         % current_f32_form())
-    if weight.dtype != torch.float32 or any(x.dtype != torch.float32 for x in xs):
-        raise ValueError('conv3x3_trainable_levels: maps and weight must be float32 (the convolution backward has no float16 form)')
-    ys = list(_Conv3x3Trainable.apply(weight, bias, bool(relu), *[x if x.is_contiguous() else x.contiguous() for x in xs]))
+    _grad_f32('conv3x3_trainable_levels', 'convolution backward',
+              [('weight', weight)] + [('xs[%d]' % i, x) for i, x in enumerate(xs)])
+    ys = list(_Conv3x3Trainable.apply(weight, bias, bool(relu), *[x.contiguous() for x in xs]))
     if flipped is not None and ys[0].grad_fn is not None:
         ys[0].grad_fn.flipped = flipped                      # (the node IS the ctx that backward receives)
     return ys
@@ -1398,7 +1357,7 @@ class _Conv3x3ReluPoolTrainable(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dpool):
         x, z, bias, weight, flipped = ctx.saved_tensors
-        dz = relu_maxpool2_backward(z, bias, dpool if dpool.is_contiguous() else dpool.contiguous())
+        dz = relu_maxpool2_backward(z, bias, dpool.contiguous())
         dx = dw = db = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             dw, db = conv3x3_wgrad_f32_levels([x], [dz], with_bias=ctx.needs_input_grad[2])      # (dz is gated: no y_relus)
@@ -1415,17 +1374,15 @@ def conv3x3_relu_pool_trainable(x, weight, bias, flipped=None):
     shape and memory format and bias.grad [cout], and computes the input gradient only when ``x`` requires one (``flipped``: a
     caller's cached conv3x3_flipped_weight).  ``x`` [B,H,W,cin] contiguous NHWC -> [B,ceil(H/2),ceil(W/2),cout]."""
     who = 'conv3x3_relu_pool_trainable'
-    _vgg_grad_f32(who, 'convolution backward', [('x', x), ('bias', bias)])
-    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.float32:       # (channels_last or contiguous: _conv3x3_weight)
-        raise ValueError('%s: weight must be a float32 tensor (the convolution backward has no float16 form), got %s'
-                         % (who, getattr(weight, 'dtype', type(weight).__name__)))
+    _grad_operands(who, 'convolution backward', [('x', x), ('bias', bias)])
+    _grad_f32(who, 'convolution backward', [('weight', weight)])                    # (channels_last or contiguous: _conv3x3_weight)
     if x.dim() != 4 or weight.dim() != 4:
         raise ValueError('%s: x must be an NHWC tensor [B,H,W,cin] and weight [cout,cin,3,3] or [cout,3,3,cin]' % who)
     cin, cout = int(x.shape[3]), int(weight.shape[0])
     if cin % 32 or cout % 64 or weight.numel() != cout * 9 * cin or tuple(bias.shape) != (cout,):
         raise ValueError('%s: cin %d must be a multiple of 32 and cout %d one of 64, weight %s and bias %s must go with them'
                          % (who, cin, cout, tuple(weight.shape), tuple(bias.shape)))
-    _conv_grad_on_gpu(who, [('x', x), ('weight', weight), ('bias', bias)])
+    _grad_on_gpu(who, [('x', x), ('weight', weight), ('bias', bias)])
     return _Conv3x3ReluPoolTrainable.apply(x, weight, bias, flipped)
 
 
