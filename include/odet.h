@@ -44,7 +44,8 @@ extern "C" {
  * (odet_conv3x3_wgrad_f32_levels, odet_conv3x3_wgrad_workspace_bytes, odet_rpn_unpack_pair) and the RoI pooling backward
  * (odet_roi_pool_argmax, odet_roi_pool_backward) and the FPN top-down merge's backward (odet_fpn_topdown_backward_f32) and the
  * two elementwise launches of the ResNet bottleneck's backward (odet_stride_gather_f32, odet_block_input_grad_f32) and the VGG16
- * training graph's max-pooling and dropout backward (odet_relu_maxpool2_backward_f32, odet_dropout_f32, odet_dropout_backward_f32); no
+ * training graph's max-pooling and dropout backward (odet_relu_maxpool2_backward_f32, odet_dropout_f32, odet_dropout_backward_f32) and
+ * the ResNet-C4 head's global average pooling (odet_global_avg_pool_f32, odet_global_avg_pool_backward_f32); no
  * existing struct or signature changed.  One documented order did: from
  * 4096 rows on, odet_dense_wgrad_f32 adds db in 256 running sums per column, not 4 (its own comment; below 4096 rows every bit is
  * as before). */
@@ -665,6 +666,27 @@ int odet_dropout_f32(const float* x, float* y, long long n, float keep_prob, uin
                      odet_stream_t stream);
 int odet_dropout_backward_f32(const float* dy, float* dx, long long n, float keep_prob, uint64_t seed, uint32_t image_id,
                               uint32_t stream_id, odet_stream_t stream);
+
+/* ---- ResNet-C4 training graph: global average pooling, forward and backward (added within 103) ------------------------------ */
+
+/* GlobalAveragePooling2D between the conv5 stack and the two Dense layers of the C4 RoI head,
+ * model/faster_rcnn/resnet_faster_rcnn.py:167-168 (get_resnet_v1_roi_head: stack1(..., name='conv5'), then
+ * layers.GlobalAveragePooling2D()), with a stated summation order.  x [rows, hw, channels] contiguous float32 -- an NHWC map [R,H,W,C] with hw = H * W --, out [rows, channels]:
+ *   s = x[r,0,c];  s = s + x[r,p,c] for p = 1 .. hw-1 in that order      every add rounded to float32, started from the first pixel
+ *   out[r,c] = s / (float)hw                                              itself (all pixels -0 give -0); one IEEE division
+ * One lane per (row, 4 channels), the pixels walked serially with 16 loads in flight.  Algorithmic bytes: 4 * rows * (hw + 1) *
+ * channels.  No atomics, no workspace, no host read (graph-capturable); every element of out is written exactly once; the result
+ * is the NumPy statement's, bit for bit (tests/c4_grad_np.py).
+ * Errors, all before any HIP call: ODET_E_INVALID (a null pointer; rows < 1; hw < 1; channels no positive multiple of 4; a pointer
+ * not 16-byte aligned). */
+int odet_global_avg_pool_f32(const float* x, int rows, int hw, int channels, float* out, odet_stream_t stream);
+
+/* Its backward, TF's _MeanGrad (python/ops/math_grad.py: the gradient broadcast to the input's shape, then a true division by
+ * the number of pooled elements): g [rows, channels], dx [rows, hw, channels],
+ *   dx[r,p,c] = g[r,c] / (float)hw        for every p; one IEEE division per element
+ * the transpose of the forward wherever the division is exact.  One lane per (row, 8 consecutive pixels, 4 channels): one
+ * division of g per eight stores.  Same rules and errors as the forward; every element of dx is written exactly once. */
+int odet_global_avg_pool_backward_f32(const float* g, int rows, int hw, int channels, float* dx, odet_stream_t stream);
 
 /* Convolution epilogue of the dense path, in place on an NHWC activation x [npix, C]:
  * x = relu?((x + bias[C]) (+ residual[npix, C])) -- the frozen-BatchNormalization bias, the

@@ -168,6 +168,8 @@ SIGNATURES = {
     'odet_relu_maxpool2_backward_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'odet_dropout_f32': (_i, [_vp, _vp, C.c_longlong, _f, C.c_uint64, C.c_uint32, C.c_uint32, _vp]),
     'odet_dropout_backward_f32': (_i, [_vp, _vp, C.c_longlong, _f, C.c_uint64, C.c_uint32, C.c_uint32, _vp]),
+    'odet_global_avg_pool_f32': (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    'odet_global_avg_pool_backward_f32': (_i, [_vp, _i, _i, _i, _vp, _vp]),
     'odet_bias_act': (_i, [_vp, _vp, _vp, C.c_longlong, _i, _i, _i, _vp]),
     'odet_rpn_pack': (_i, [_vp, _vp, C.c_longlong, _i, _i, _vp, C.c_longlong, C.c_longlong, _i, _vp]),
     'odet_bias_relu_maxpool': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

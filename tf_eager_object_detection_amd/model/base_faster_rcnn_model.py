@@ -1,5 +1,5 @@
-"""BaseFasterRcnn / RpnHead / ResNetFasterRcnn / Vgg16FasterRcnn -- counterparts of the reference's
-model/faster_rcnn/base_faster_rcnn_model.py (BaseFasterRcnn :16-306, RpnHead :309-350), resnet_faster_rcnn.py
+"""BaseFasterRcnn / RpnHead / ResNetFasterRcnn (TrainableResNetFasterRcnn) / Vgg16FasterRcnn -- counterparts of the
+reference's model/faster_rcnn/base_faster_rcnn_model.py (BaseFasterRcnn :16-306, RpnHead :309-350), resnet_faster_rcnn.py
 (ResNetFasterRcnn :188-293) and vgg16_faster_rcnn.py (Vgg16FasterRcnn :11-115): the CALLER objects of the single-level hot
 path, with the reference's constructor arguments, `call(inputs, training=None, mask=None)` and `im_detect`.
 
@@ -8,11 +8,12 @@ path, with the reference's constructor arguments, `call(inputs, training=None, m
 `_roi_pooling` (RoiPoolingCropAndResize) -> `_roi_head` -> softmax -> post_ops_prediction, with dynamic shapes and one image
 per call as in the reference.  The static-shape, sync-free arrangement for throughput is model/frcnn_detector.py.
 
-The training branches run every dense part under no_grad unless a keyword switches its backward pass on (Vgg16FasterRcnn; float32,
-f32_form 'exact'): `train_roi_head` runs the RoI head's trainable form with the reference's two dropouts (the two RoI losses carry a
-graph into fc1, fc2, score and bbox), `train_rpn_head` the RpnHead's (the two RPN losses carry a graph into rpn_conv, rpn_score and
-rpn_bbox), `train_extractor` (with at least one of the two) the extractor's: the shared map requires a gradient, which the RpnHead's
-input gradient and the trainable RoI pooling deliver, and the losses carry a graph into block3_conv1 .. block5_conv3."""
+The training branches run every dense part under no_grad unless a keyword switches its backward pass on (Vgg16FasterRcnn,
+TrainableResNetFasterRcnn; float32, f32_form 'exact'): `train_roi_head` runs the RoI head's trainable form -- VGG16's with the
+reference's two dropouts -- (the two RoI losses carry a graph into fc1, fc2, score and bbox / into the conv5 stack, score and
+bbox), `train_rpn_head` the RpnHead's (the two RPN losses carry a graph into rpn_conv, rpn_score and rpn_bbox), `train_extractor`
+(with at least one of the two) the extractor's: the shared map requires a gradient, which the RpnHead's input gradient and the
+trainable RoI pooling deliver, and the losses carry a graph into block3_conv1 .. block5_conv3 / into conv3 and conv4."""
 import contextlib
 import math
 
@@ -30,7 +31,7 @@ from .region_proposal import RegionProposal
 from .roi_pooling import RoiPoolingCropAndResize
 from .trainable_common import check_train_flags
 
-__all__ = ['BaseFasterRcnn', 'RpnHead', 'ResNetFasterRcnn', 'Vgg16FasterRcnn']
+__all__ = ['BaseFasterRcnn', 'RpnHead', 'ResNetFasterRcnn', 'TrainableResNetFasterRcnn', 'Vgg16FasterRcnn']
 
 
 class RpnHead(torch.nn.Module):
@@ -354,18 +355,24 @@ _TRAIN_KEYWORDS = ('train_roi_head', 'train_rpn_head', 'train_extractor', 'dropo
 class ResNetFasterRcnn(_FrcnnFromDense):
     """reference resnet_faster_rcnn.py:188-293: ResNet-{50,101,152} C4 extractor, RoI head = conv5 stack + global average
     pooling + score / box layers.  Keyword arguments and defaults as there (`_COMMON`; model_factory.py:117 passes
-    roi_pooling_max_pooling_flag=False from the config)."""
+    roi_pooling_max_pooling_flag=False from the config).  This class refuses the train_* keywords; TrainableResNetFasterRcnn,
+    the same constructor body, takes them."""
+
+    _accepts_train_keywords = False
 
     def __init__(self, depth=50, roi_feature_size=(7, 7, 1024), dtype=torch.float32, device='cuda', f32_form='exact', **kwargs):
         from .frcnn_detector import ResNetC4Detector
         check_caller_f32_form(f32_form)
         if depth not in [50, 101, 152]:
             raise ValueError('unknown resnet layers number {}'.format(depth))
-        asked = sorted(k for k in _TRAIN_KEYWORDS if k in kwargs)
-        if asked:
-            raise NotImplementedError('ResNetFasterRcnn: %s: the C4 model has no backward pass (its conv5 stack on the crops and '
-                                      'the global average pooling are not built); Vgg16FasterRcnn and ResnetV1Fpn train'
-                                      % ', '.join(asked))
+        if self._accepts_train_keywords:
+            self._take_train_keywords(kwargs, dtype, f32_form)
+        else:
+            asked = sorted(k for k in _TRAIN_KEYWORDS if k in kwargs)
+            if asked:
+                raise NotImplementedError('ResNetFasterRcnn: %s: this class takes no training keywords (existing callers rely on '
+                                          'the refusal); TrainableResNetFasterRcnn, the same model, takes train_roi_head, '
+                                          'train_rpn_head and train_extractor' % ', '.join(asked))
         kw = dict(_COMMON)
         unknown = set(kwargs) - set(kw)
         if unknown:
@@ -376,6 +383,38 @@ class ResNetFasterRcnn(_FrcnnFromDense):
         if len(kw['ratios']) * len(kw['scales']) != 9 or kw['extractor_stride'] != 16:
             raise ValueError('ResNetFasterRcnn: the dense kernels are built for 9 anchors per cell at stride 16')
         self._init_with_dense(ResNetC4Detector(depth, kw['num_classes'], (64, 64), 1, dtype=dtype, f32_form=f32_form), dtype, device, kw)
+
+
+class TrainableResNetFasterRcnn(ResNetFasterRcnn):
+    """ResNetFasterRcnn with the three training keywords (float32, f32_form 'exact'; the module docstring), under Vgg16FasterRcnn's
+    rules: `train_roi_head` (the conv5 stack on the crops, the global average pooling in ops.global_avg_pool's order, score and
+    bbox), `train_rpn_head`, `train_extractor` (conv3 and conv4, with at least one of the two heads).  With all three
+    `sum(losses).backward()` fills every parameter the reference trains -- conv3, conv4, conv5, the RpnHead, score, bbox: 94 of
+    116 at depth 50, 196 of 218 at depth 101 -- and leaves the 22 of conv1 and the conv2 stack (trainable=False,
+    resnet_faster_rcnn.py:109, 139-141) alone.  There is no dropout in this head, so no `dropout_seed`.  With the keywords off,
+    and in every inference call, the model is ResNetFasterRcnn bit for bit; a training call's RoI scores go through the trainable
+    head's pooling and differ from it by that pooling's rounding."""
+
+    _accepts_train_keywords = True
+
+    def __init__(self, depth=50, roi_feature_size=(7, 7, 1024), dtype=torch.float32, device='cuda', f32_form='exact',
+                 train_roi_head=False, train_rpn_head=False, train_extractor=False, **kwargs):
+        super().__init__(depth, roi_feature_size, dtype, device, f32_form, train_roi_head=train_roi_head,
+                         train_rpn_head=train_rpn_head, train_extractor=train_extractor, **kwargs)
+
+    def _take_train_keywords(self, kwargs, dtype, f32_form):
+        """checks the three keywords, sets the _train_* attributes (before the base constructor reads them) and removes them from
+        ``kwargs``"""
+        roi, rpn, ext = (kwargs.pop(k) for k in ('train_roi_head', 'train_rpn_head', 'train_extractor'))
+        check_train_flags('TrainableResNetFasterRcnn', dtype, f32_form,
+                          (ext, 'train_extractor', 'the bottleneck backward has'),
+                          (roi, 'train_roi_head', 'the bottleneck backward has'),
+                          (rpn, 'train_rpn_head', 'the convolution backward has'))
+        check_train_extractor(ext, rpn, roi)
+        self._train_roi_head, self._train_rpn_head, self._train_extractor = bool(roi), bool(rpn), bool(ext)
+
+    def _get_trainable_roi_head(self):
+        return self._dense_ref.roi_head_trainable
 
 
 class Vgg16FasterRcnn(_FrcnnFromDense):

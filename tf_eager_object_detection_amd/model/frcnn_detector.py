@@ -17,6 +17,7 @@ import torch.nn as nn
 from .. import ops
 from ..derived import derived
 from ..pipeline import FrcnnHotPath, FrcnnStepBatch
+from .c4_trainable import C4TrainableParts
 from .detector_base import Detector, _in_f32_form
 from .fpn_detector import _BLOCKS, _conv, _conv_epi, _conv_relu_pool, _fold_frozen_bn, _nhwc, _no_kernel, _patch_gemm, \
     _patch_weight, _stack, _stem, rpn_pair_padded, rpn_pair_weights
@@ -24,10 +25,10 @@ from .fpn_detector import _BLOCKS, _conv, _conv_epi, _conv_relu_pool, _fold_froz
 __all__ = ['ResNetC4Detector', 'Vgg16Detector']
 
 
-class ResNetC4Detector(Detector):
-    """Inference-only ResNet-{50,101,152} C4 Faster R-CNN (the pass itself: detector_base.Detector).  Batched arrangement:
-    FrcnnStepBatch (odet_fpn_step_t.single_level); per image (`batched=False`): one FrcnnHotPath per image on a stream of its
-    own, then ONE RoI-head call for the whole batch."""
+class ResNetC4Detector(C4TrainableParts, Detector):
+    """ResNet-{50,101,152} C4 Faster R-CNN (inference pass: detector_base.Detector; trainable parts: model/c4_trainable.py).
+    Batched arrangement: FrcnnStepBatch (odet_fpn_step_t.single_level); per image (`batched=False`): one FrcnnHotPath per
+    image on a stream of its own, then ONE RoI-head call for the whole batch."""
 
     _step_batch_class, _hot_path_class = FrcnnStepBatch, FrcnnHotPath
 

@@ -724,6 +724,70 @@ def dropout_trainable(x, keep_prob, seed, image_id, stream_id):
                                    int(stream_id))
 
 
+def _gap_out(who, out, shape, name, operand):
+    """the last two rules of the pooling fronts: a given ``out`` is one more shape rule (checked before the device, like every
+    shape), then operand and ``out`` on the GPU -> the result tensor"""
+    if out is not None:
+        try:
+            _out(out, shape, torch.float32, None)
+        except ValueError as e:
+            raise ValueError('%s: %s' % (who, e)) from None
+    _grad_on_gpu(who, [(name, operand)] + ([('out', out)] if out is not None else []))
+    return _out(out, shape, torch.float32, operand.device)
+
+
+def global_avg_pool(x, out=None):
+    """GlobalAveragePooling2D with a stated order (odet_global_avg_pool_f32; resnet_faster_rcnn.py:167-168, between the conv5 stack
+    and the two Dense layers): out[r,c] = (x[r,0,0,c] + x[r,0,1,c] + ... ) / (float)(H W), the float32 sum over the pixels in
+    row-major order, every add rounded, started from the first pixel itself; then one IEEE division.  ``x`` [R,H,W,C] contiguous
+    NHWC float32 on the GPU, R, H, W >= 1, C % 4 == 0 -> [R,C].  float32, f32_form 'exact' only."""
+    who = 'global_avg_pool'
+    _grad_operands(who, 'pooling backward', [('x', x)], ndim=4)
+    if min(int(v) for v in x.shape[:3]) < 1 or int(x.shape[3]) < 4 or int(x.shape[3]) % 4:
+        raise ValueError('%s: x %s must have at least one row and one pixel and C a positive multiple of 4' % (who, tuple(x.shape)))
+    R, H, W, Cc = (int(v) for v in x.shape)
+    out = _gap_out(who, out, (R, Cc), 'x', x)
+    L.call('odet_global_avg_pool_f32', L.dptr(x), R, H * W, Cc, L.dptr(out), L.stream())
+    return out
+
+
+def global_avg_pool_backward(g, hw, out=None):
+    """global_avg_pool's backward (odet_global_avg_pool_backward_f32), TF's _MeanGrad: dx[r,y,x,c] = g[r,c] / (float)(H W) at every
+    pixel.  ``g`` [R,C] contiguous float32 on the GPU, R >= 1, C % 4 == 0; ``hw`` = (H, W) of the pooled map, both >= 1
+    -> [R,H,W,C].  float32, f32_form 'exact' only."""
+    who = 'global_avg_pool_backward'
+    _grad_operands(who, 'pooling backward', [('g', g)], ndim=2)
+    if int(g.shape[0]) < 1 or int(g.shape[1]) < 4 or int(g.shape[1]) % 4:
+        raise ValueError('%s: g %s must have at least one row and C a positive multiple of 4' % (who, tuple(g.shape)))
+    H, W = int(hw[0]), int(hw[1])
+    if H < 1 or W < 1:
+        raise ValueError('%s: hw %s must be positive' % (who, (H, W)))
+    R, Cc = int(g.shape[0]), int(g.shape[1])
+    out = _gap_out(who, out, (R, H, W, Cc), 'g', g)
+    L.call('odet_global_avg_pool_backward_f32', L.dptr(g), R, H * W, Cc, L.dptr(out), L.stream())
+    return out
+
+
+class _GlobalAvgPoolTrainable(torch.autograd.Function):
+    """ops.global_avg_pool forward, ops.global_avg_pool_backward backward; nothing is saved but the map's size"""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.hw = (int(x.shape[1]), int(x.shape[2]))
+        return global_avg_pool(x)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        return global_avg_pool_backward(g.contiguous(), ctx.hw) if ctx.needs_input_grad[0] else None
+
+
+def global_avg_pool_trainable(x):
+    """ops.global_avg_pool with a backward pass (float32, f32_form 'exact'): the forward is `global_avg_pool`, bit for bit; the
+    backward is one global_avg_pool_backward, computed only when ``x`` requires a gradient."""
+    return _GlobalAvgPoolTrainable.apply(x)
+
+
 def bias_act_(x, bias, residual=None, relu=True):
     """In place on an NHWC (or any [..., C] contiguous) activation: x = relu?((x + bias) (+ residual)) -- the
     convolution epilogue of the reference's ResNet blocks / RPN head (resnet_fpn.py:154-205) in one pass."""
