@@ -45,7 +45,8 @@ extern "C" {
  * (odet_roi_pool_argmax, odet_roi_pool_backward) and the FPN top-down merge's backward (odet_fpn_topdown_backward_f32) and the
  * two elementwise launches of the ResNet bottleneck's backward (odet_stride_gather_f32, odet_block_input_grad_f32) and the VGG16
  * training graph's max-pooling and dropout backward (odet_relu_maxpool2_backward_f32, odet_dropout_f32, odet_dropout_backward_f32) and
- * the ResNet-C4 head's global average pooling (odet_global_avg_pool_f32, odet_global_avg_pool_backward_f32); no
+ * the ResNet-C4 head's global average pooling (odet_global_avg_pool_f32, odet_global_avg_pool_backward_f32) and the
+ * data-parallel gradient exchange (odet_bucket_pack_f32, odet_bucket_unpack_f32, odet_rank_mean_f32); no
  * existing struct or signature changed.  One documented order did: from
  * 4096 rows on, odet_dense_wgrad_f32 adds db in 256 running sums per column, not 4 (its own comment; below 4096 rows every bit is
  * as before). */
@@ -1254,6 +1255,42 @@ int odet_opt_step(const odet_opt_config_t* cfg, const odet_opt_tensor_t* tensors
 /* The same L2 reduction with no update (the forward value of l2_loss): nothing but the two outputs and partials is written. */
 int odet_l2_loss(const odet_opt_config_t* cfg, const odet_opt_tensor_t* tensors, const odet_opt_chunk_t* chunks, void* partials,
                  size_t partials_bytes, float* tensor_losses, float* total_loss, odet_stream_t stream);
+
+/* ---- gradient exchange (added within 103) --------------------------------------------------------------------------
+ * The byte moves and the arithmetic of data-parallel training, one image per rank (parallel.GradientExchange): the gradient
+ * list goes into one contiguous float32 BUCKET in one launch, collectives that only move bytes hand rank r shard r of every
+ * rank, and the sum over the ranks is formed here in ASCENDING RANK order -- so the exchanged gradient is a function of the data
+ * alone, whatever the collective library's algorithm, channel count or topology.  All three: no allocation, no host read
+ * (graph-capturable), no atomics, every output element written exactly once; errors are found on the host before any HIP call.
+ *
+ * Bucket layout.  The chunk table of the training step (odet_opt_chunk_t, ODET_OPT_CHUNK elements per chunk) built over the
+ * PRESENT tensors in list order: chunk c of the table is elements c * ODET_OPT_CHUNK .. of the bucket and covers elements offset ..
+ * min(offset + ODET_OPT_CHUNK, numel) of tensor `tensor`; a tensor of 0 elements, or an absent one (NULL in the pointer column),
+ * has no chunk and no place.  bucket_chunks >= num_chunks is the bucket's size (a whole number of shards: world * shard_chunks).
+ *   tensors   void* [num_tensors] (DEVICE): the pointer column, a table of its own so that tensors that moved cost an 8-byte
+ *             re-upload each; float32, dense, 4-byte aligned;
+ *   numels    int64 [num_tensors] (DEVICE);
+ *   chunks    odet_opt_chunk_t [num_chunks] (DEVICE); a record that does not fit (tensor index or offset out of range, a NULL
+ *             tensor) is treated as absent: pack writes +0.0f for it, unpack skips it.
+ * odet_bucket_pack_f32 writes EVERY element of the bucket: the tensors' elements, +0.0f in the tail of a tensor's last chunk and
+ * in the chunks num_chunks .. bucket_chunks - 1.  odet_bucket_unpack_f32 writes each present tensor's numel elements and
+ * nothing else.  A chunk goes through 16-byte loads and stores when its tensor is 16-byte aligned, else element by element,
+ * with the same bits; the bucket itself must be 16-byte aligned.
+ * Errors: ODET_E_INVALID (a negative count, num_chunks > bucket_chunks, a null table that is needed, a null or misaligned
+ * bucket), ODET_E_LIMIT (num_tensors > ODET_OPT_MAX_TENSORS, bucket_chunks > ODET_OPT_MAX_CHUNKS).
+ *
+ * odet_rank_mean_f32: parts float32 [world, n] -> out float32 [n].  s = parts[0][i]; s = s + parts[r][i] for r = 1 .. world - 1,
+ * each ONE float32 add, in ascending r; average (0 / 1): out[i] = s / float32(world), one correctly rounded division (not a
+ * multiplication by a reciprocal), else out[i] = s.  world == 1 returns the input's bits.  16-byte accesses where a row (and
+ * out) is 16-byte aligned, else element by element, with the same bits; out must not overlap parts.
+ * Errors: ODET_E_INVALID (world < 1, n < 0, average outside {0, 1}, a null pointer with n > 0, a pointer not 4-byte aligned),
+ * ODET_E_LIMIT (world > ODET_RANK_MEAN_MAX_WORLD, n > ODET_OPT_MAX_CHUNKS * ODET_OPT_CHUNK).  n == 0 is a no-op. */
+#define ODET_RANK_MEAN_MAX_WORLD 64
+int odet_bucket_pack_f32(const void* const* tensors, const int64_t* numels, int num_tensors, const odet_opt_chunk_t* chunks,
+                         int num_chunks, float* bucket, int64_t bucket_chunks, odet_stream_t stream);
+int odet_bucket_unpack_f32(const float* bucket, int64_t bucket_chunks, void* const* tensors, const int64_t* numels,
+                           int num_tensors, const odet_opt_chunk_t* chunks, int num_chunks, odet_stream_t stream);
+int odet_rank_mean_f32(const float* parts, int world, int64_t n, int average, float* out, odet_stream_t stream);
 
 /* ---- Dense backward, float32 (added within 103) --------------------------------------------------------------------
  * The gradients of a keras Dense layer y = relu?(x . w^T + b) (resnet_fpn.py:292-336, the FPN RoI head) on the exact-float32

@@ -73,6 +73,7 @@ OPT_MAX_CHUNKS = 1 << 24
 OPT_MAX_BOUNDARIES = 16
 OPT_MOMENTUM, OPT_ADAM = 1, 2
 OPT_VAR_F16, OPT_GRAD_F16 = 1, 2
+RANK_MEAN_MAX_WORLD = 64
 
 
 class OdetOptTensor(C.Structure):
@@ -235,6 +236,9 @@ SIGNATURES = {
     'odet_opt_partials_bytes': (_sz, [_i]),
     'odet_opt_step': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     'odet_l2_loss': (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    'odet_bucket_pack_f32': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i64, _vp]),
+    'odet_bucket_unpack_f32': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _i, _vp]),
+    'odet_rank_mean_f32': (_i, [_vp, _i, _i64, _i, _vp, _vp]),
     'odet_dense_grad_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'odet_dense_dgrad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     'odet_dense_wgrad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),

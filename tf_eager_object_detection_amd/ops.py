@@ -2044,6 +2044,38 @@ def _bytes_tensor(obj, device):
     return torch.frombuffer(bytearray(bytes(obj)), dtype=torch.uint8).to(device)
 
 
+class _PointerColumn:
+    """A device column of tensor pointers (int64, 0 = absent) with its pinned staging copy: a table of its own, so that tensors
+    that moved cost an 8-byte re-upload each and unchanged pointers cost nothing."""
+
+    def __init__(self, n, device):
+        self.n = int(n)
+        self.device_column = torch.zeros(max(self.n, 1), dtype=torch.int64, device=device)
+        self._host = torch.zeros(max(self.n, 1), dtype=torch.int64).pin_memory()
+        self._now = None
+        self._copied = None
+
+    def set(self, pointers, in_capture):
+        """Unchanged -> nothing happens, returns False.  Changed -> re-uploaded from pinned memory on the current stream (nothing
+        is read back), returns True; inside a graph capture that raises OdetError(in_capture)."""
+        pointers = tuple(int(p) for p in pointers)
+        if len(pointers) != self.n:
+            raise ValueError('%d pointers for a column of %d' % (len(pointers), self.n))
+        if pointers == self._now:
+            return False
+        if torch.cuda.is_current_stream_capturing():
+            raise L.OdetError(in_capture)
+        if self._copied is not None:
+            self._copied.synchronize()                         # (the previous upload has left the pinned buffer)
+        if pointers:
+            self._host[:len(pointers)] = torch.tensor(pointers, dtype=torch.int64)
+        self.device_column.copy_(self._host, non_blocking=True)
+        self._copied = torch.cuda.Event()
+        self._copied.record()
+        self._now = pointers
+        return True
+
+
 class OptimizerTables:
     """The device tables of one variable list (include/odet.h "training step"), built once: the tensor records, the chunk
     table, the gradient pointer column with its pinned staging copy, the partials buffer and the two L2 outputs.
@@ -2066,10 +2098,8 @@ class OptimizerTables:
         self.chunks = _bytes_tensor(ctab, self.device)
         self.tensors = torch.empty(max(T, 1) * C.sizeof(L.OdetOptTensor), dtype=torch.uint8, device=self.device)
         self.write_tensors()
-        self.grads = torch.zeros(max(T, 1), dtype=torch.int64, device=self.device)
-        self._grads_host = torch.zeros(max(T, 1), dtype=torch.int64).pin_memory()
-        self._grads_now = None
-        self._copied = None
+        self._column = _PointerColumn(T, self.device)
+        self.grads = self._column.device_column
         self.partials = L.workspace(L.lib().odet_opt_partials_bytes(self.num_chunks), self.device)
         self.tensor_l2_losses = torch.zeros(max(T, 1), dtype=torch.float32, device=self.device)[:T]
         self.l2_loss = torch.zeros((), dtype=torch.float32, device=self.device)
@@ -2110,23 +2140,11 @@ class OptimizerTables:
     def set_gradients(self, pointers):
         """pointers: one int per variable (0 = None this step).  Unchanged -> nothing happens.  Changed -> the pointer column is
         re-uploaded from pinned memory on the current stream (nothing is read back); inside a graph capture that is an error."""
-        pointers = tuple(int(p) for p in pointers)
+        pointers = tuple(pointers)
         if len(pointers) != self.num_tensors:
             raise ValueError('%d gradient pointers for %d variables' % (len(pointers), self.num_tensors))
-        if pointers == self._grads_now:
-            return False
-        if torch.cuda.is_current_stream_capturing():
-            raise L.OdetError('the gradient pointers changed inside a graph capture: bind the gradients the graph will use '
-                              '(set_gradients / Optimizer.prepare) before capturing, and write new gradients into them')
-        if self._copied is not None:
-            self._copied.synchronize()                         # (the previous upload has left the pinned buffer)
-        if pointers:
-            self._grads_host[:len(pointers)] = torch.tensor(pointers, dtype=torch.int64)
-        self.grads.copy_(self._grads_host, non_blocking=True)
-        self._copied = torch.cuda.Event()
-        self._copied.record()
-        self._grads_now = pointers
-        return True
+        return self._column.set(pointers, 'the gradient pointers changed inside a graph capture: bind the gradients the graph will '
+                                'use (set_gradients / Optimizer.prepare) before capturing, and write new gradients into them')
 
 
 def _opt_config(tables, kind=0, num_boundaries=0, momentum=0.0, beta1=0.0, beta2=0.0, epsilon=0.0):
@@ -2153,3 +2171,130 @@ def l2_loss(tables):
     L.call('odet_l2_loss', C.byref(cfg), L.dptr(tables.tensors), L.dptr(tables.chunks), L.dptr(tables.partials),
            tables.partials.numel(), L.dptr(tables.tensor_l2_losses), L.dptr(tables.l2_loss), L.stream())
     return OptimizerOutputs(tables.l2_loss, tables.tensor_l2_losses)
+
+
+# ---- the gradient exchange (csrc/grad_exchange.hip) -----------------------------------------------------------------------------
+RANK_MEAN_MAX_WORLD = L.RANK_MEAN_MAX_WORLD
+
+
+def memory_dense(t):
+    """True when the tensor's elements fill numel consecutive places (contiguous in the default or the channels-last sense)"""
+    if t.numel() == 0 or t.is_contiguous():
+        return True
+    if t.dim() == 4:
+        return t.is_contiguous(memory_format=torch.channels_last)
+    if t.dim() == 5:
+        return t.is_contiguous(memory_format=torch.channels_last_3d)
+    return False
+
+
+class BucketTables:
+    """The layout of one tensor list in a float32 bucket (include/odet.h "gradient exchange") and, on a GPU, its device tables.
+    numels: one int per tensor, None = absent (no place in the bucket).  The chunk table is the optimizer's (opt_chunk_table)
+    over the present tensors, so table chunk c is bucket chunk c; the bucket is world * shard_chunks chunks, the chunks past
+    the table being padding.  device None / cpu: host arithmetic only (the layout; nothing is uploaded)."""
+
+    def __init__(self, numels, world=1, device=None):
+        self.world = int(world)
+        if self.world < 1:
+            raise ValueError('world must be at least 1, got %d' % self.world)
+        self.numels = [None if n is None else int(n) for n in numels]
+        T = len(self.numels)
+        if T > OPT_MAX_TENSORS:
+            raise ValueError('%d tensors exceed the limit of %d' % (T, OPT_MAX_TENSORS))
+        first, self.chunk_list = opt_chunk_table([0 if n is None else n for n in self.numels])
+        self.first_chunk = [None if n is None else f for n, f in zip(self.numels, first)]
+        self.num_tensors, self.num_chunks = T, len(self.chunk_list)
+        self.shard_chunks = -(-self.num_chunks // self.world)
+        self.bucket_chunks = self.world * self.shard_chunks
+        if self.bucket_chunks > OPT_MAX_CHUNKS:
+            raise ValueError('%d chunks exceed the limit of %d' % (self.bucket_chunks, OPT_MAX_CHUNKS))
+        self.shard_numel, self.bucket_numel = self.shard_chunks * OPT_CHUNK, self.bucket_chunks * OPT_CHUNK
+        self.device = torch.device(device) if device is not None else torch.device('cpu')
+        if self.device.type == 'cuda':
+            ctab = (L.OdetOptChunk * max(self.num_chunks, 1))()
+            for i, (t, o) in enumerate(self.chunk_list):
+                ctab[i].offset, ctab[i].tensor = o, t
+            self.chunks = _bytes_tensor(ctab, self.device)
+            self.numels_dev = torch.tensor([0 if n is None else n for n in self.numels] or [0], dtype=torch.int64).to(self.device)
+            self._column = _PointerColumn(T, self.device)
+            self.pointers = self._column.device_column
+
+    def offset(self, t):
+        """first bucket element of tensor t (a multiple of OPT_CHUNK), None for an absent one"""
+        f = self.first_chunk[t]
+        return None if f is None else f * OPT_CHUNK
+
+    def new_bucket(self, device=None):
+        return torch.empty(self.bucket_numel, dtype=torch.float32, device=device if device is not None else self.device)
+
+    def check(self, tensors):
+        """the tensors this layout was built for: float32, dense, present exactly where the layout has a place"""
+        tensors = list(tensors)
+        if len(tensors) != self.num_tensors:
+            raise ValueError('%d tensors for a layout of %d' % (len(tensors), self.num_tensors))
+        for i, (t, n) in enumerate(zip(tensors, self.numels)):
+            if (t is None) != (n is None):
+                raise ValueError('tensor %d is %s, the layout has it %s' % (i, 'absent' if t is None else 'present',
+                                                                            'absent' if n is None else 'present'))
+            if t is None:
+                continue
+            if t.dtype != torch.float32:
+                raise TypeError('tensor %d must be float32, got %s' % (i, t.dtype))
+            if t.numel() != n:
+                raise ValueError('tensor %d has %d elements, the layout %d' % (i, t.numel(), n))
+            if not memory_dense(t):
+                raise ValueError('tensor %d is not dense in memory (shape %s, strides %s)' % (i, tuple(t.shape), t.stride()))
+            if t.device != self.device:
+                raise L.OdetError('tensor %d lives on %s, the tables on %s' % (i, t.device, self.device))
+        return tensors
+
+    def set_pointers(self, tensors):
+        """binds the tensor list (None = absent).  Unchanged pointers -> nothing happens, returns False.  Changed -> the pointer
+        column is re-uploaded from pinned memory on the current stream; inside a graph capture that is an error."""
+        return self._column.set([0 if t is None else t.data_ptr() for t in self.check(tensors)],
+                                'the bucket pointers changed inside a graph capture: bind the tensors before capturing')
+
+    def _bucket(self, bucket):
+        if bucket.dtype != torch.float32 or bucket.numel() != self.bucket_numel or not bucket.is_contiguous() or bucket.dim() != 1:
+            raise ValueError('the bucket must be a contiguous float32 vector of %d elements' % self.bucket_numel)
+        if bucket.device != self.device:
+            raise L.OdetError('the bucket lives on %s, the tables on %s' % (bucket.device, self.device))
+        return bucket
+
+
+def bucket_pack(tables, tensors, bucket=None):
+    """odet_bucket_pack_f32: the list of float32 tensors (None where the layout has none) -> the whole bucket, one launch"""
+    bucket = tables._bucket(bucket if bucket is not None else tables.new_bucket())
+    tables.set_pointers(tensors)
+    L.call('odet_bucket_pack_f32', L.dptr(tables.pointers), L.dptr(tables.numels_dev), tables.num_tensors, L.dptr(tables.chunks),
+           tables.num_chunks, L.dptr(bucket), tables.bucket_chunks, L.stream())
+    return bucket
+
+
+def bucket_unpack(tables, bucket, tensors):
+    """odet_bucket_unpack_f32: the bucket -> the tensors' own elements, one launch; nothing else is written"""
+    tables._bucket(bucket)
+    tables.set_pointers(tensors)
+    L.call('odet_bucket_unpack_f32', L.dptr(bucket), tables.bucket_chunks, L.dptr(tables.pointers), L.dptr(tables.numels_dev),
+           tables.num_tensors, L.dptr(tables.chunks), tables.num_chunks, L.stream())
+    return tensors
+
+
+def rank_mean(parts, average=True, out=None):
+    """odet_rank_mean_f32: parts float32 [world, n] -> [n], the float32 sum over the ranks in ascending rank order, divided by
+    float32(world) with `average`"""
+    if parts.dim() != 2:
+        raise ValueError('parts must have shape [world, n], got %s' % (tuple(parts.shape),))
+    world, n = parts.shape
+    if world < 1:
+        raise ValueError('world must be at least 1')
+    if world > RANK_MEAN_MAX_WORLD:
+        raise ValueError('world %d exceeds the limit of %d' % (world, RANK_MEAN_MAX_WORLD))
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=parts.device)
+    elif tuple(out.shape) != (n,) or out.device != parts.device:
+        raise ValueError('out must have shape [%d] on %s' % (n, parts.device))
+    L.call('odet_rank_mean_f32', L.dptr(parts, torch.float32, 'parts'), int(world), int(n), 1 if average else 0,
+           L.dptr(out, torch.float32, 'out'), L.stream())
+    return out

@@ -51,14 +51,7 @@ def learning_rate_at(schedule, step):
     return schedule.values[sum(1 for b in schedule.boundaries if b < int(step))]
 
 
-def _dense(t):
-    if t.numel() == 0 or t.is_contiguous():
-        return True
-    if t.dim() == 4:
-        return t.is_contiguous(memory_format=torch.channels_last)
-    if t.dim() == 5:
-        return t.is_contiguous(memory_format=torch.channels_last_3d)
-    return False
+_dense = ops.memory_dense
 
 
 class _Optimizer:
