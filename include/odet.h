@@ -87,7 +87,9 @@ int odet_anchors_fpn(int num_levels, int A, const int* fh, const int* fw, const 
 /* utils/bbox_transform.py:32-55 decode_bbox_with_mean_and_std.  means/stds: host [4].
  * If clip_h > 0 the result is also clipped to [0, clip_w-1] x [0, clip_h-1] as
  * utils/bbox_tf.py:70-74 does with min_value 0 (fusion used by region_proposal.py:59-63).
- * delta_stride: floats between consecutive delta rows (4 for a dense [n,4] array). */
+ * delta_stride: floats between consecutive delta rows (4 for a dense [n,4] array), >= 4.
+ * deltas needs float alignment only: a row is read as one 16-byte load where the stride is
+ * a multiple of 4 and the pointer is 16-byte aligned, as four floats otherwise. */
 int odet_decode(const float* anchors, const float* deltas, int64_t delta_stride, int n,
                 const float* means, const float* stds, int clip_h, int clip_w, float* out,
                 odet_stream_t stream);

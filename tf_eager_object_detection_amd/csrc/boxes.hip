@@ -82,14 +82,15 @@ extern "C" int odet_anchors_fpn(int num_levels, int A, const int* fh, const int*
 
 // ---------------------------------------------------------------------- decode / encode --
 
+// vec4: every row of deltas starts on a 16-byte boundary (decided by the host from the stride AND the pointer).
 __global__ void __launch_bounds__(256) k_decode(const float4* __restrict__ anchors, const float* __restrict__ deltas,
-                                                int64_t delta_stride, int n, Vec4 means, Vec4 stds, int clip,
+                                                int64_t delta_stride, int vec4, int n, Vec4 means, Vec4 stds, int clip,
                                                 float wmax, float hmax, float4* __restrict__ out) {
   int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float* t = deltas + (int64_t)i * delta_stride;
   float4 d;
-  if ((delta_stride & 3) == 0) {
+  if (vec4) {
     d = *reinterpret_cast<const float4*>(t);
   } else {
     d = make_float4(t[0], t[1], t[2], t[3]);
@@ -112,8 +113,10 @@ extern "C" int odet_decode(const float* anchors, const float* deltas, int64_t de
   ODET_REQUIRE(delta_stride >= 4, "odet_decode: delta_stride must be >= 4");
   Vec4 m, s;
   for (int k = 0; k < 4; ++k) { m.v[k] = means[k]; s.v[k] = stds[k]; }
+  // the C ABI takes any float pointer: one float4 load per row only where every row is 16-byte aligned
+  const int vec4 = ((delta_stride & 3) == 0 && ((uintptr_t)deltas & 15) == 0) ? 1 : 0;
   hipLaunchKernelGGL(k_decode, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const float4*)anchors, deltas, delta_stride, n, m, s, clip_h > 0 ? 1 : 0,
+                     (const float4*)anchors, deltas, delta_stride, vec4, n, m, s, clip_h > 0 ? 1 : 0,
                      (float)(clip_w - 1), (float)(clip_h - 1), (float4*)out);
   ODET_LAUNCH_CHECK();
   return ODET_OK;
