@@ -244,3 +244,45 @@ def test_faster_rcnn_models_call_agrees_with_the_static_shape_detectors(kind):
     np.testing.assert_array_equal(labels.cpu().numpy()[o1], dl[:n].cpu().numpy()[o2])
     np.testing.assert_allclose(scores.cpu().numpy()[o1], ds[:n].cpu().numpy()[o2], rtol=0, atol=1e-5)
     np.testing.assert_allclose(boxes.cpu().numpy()[o1], db[:n].cpu().numpy()[o2], rtol=0, atol=1e-2)
+
+
+@pytest.mark.gpu
+def test_resnet_v1_fpn_helpers_equal_the_front_composed_by_hand():
+    """predict_rois, predict_rpns and im_detect of ResnetV1Fpn against the same stages called one by one on the model's dense part
+    and layers: the training-mode proposals through ProposalTarget (the same image id), the anchors AnchorTarget labels positive,
+    and the test-mode proposals in level order divided by the scale (a true float32 division: exact against NumPy's)."""
+    from tf_eager_object_detection_amd import ops
+    from tf_eager_object_detection_amd.model.base_fpn_model import ResnetV1Fpn
+    torch.manual_seed(1)
+    shape = (256, 352)
+    m = ResnetV1Fpn(depth=50, rpn_proposal_num_post_nms_test=300, training_targets='hip')
+    img = _image(shape, 1)
+    gt = torch.tensor([[30., 40., 200., 180.], [100., 60., 330., 250.]], device='cuda')
+    gl = torch.tensor([3, 7], device='cuda')
+    with torch.no_grad():
+        p_list = m.dense.features(img)
+        scores, deltas = m.dense.rpn(list(p_list))
+        anchors = m._get_anchors(list(shape))
+        fg = ops.rpn_fg_softmax(scores.reshape(-1, 2), 1, ops.RPN_LAYOUT_FPN)
+        rois = {t: m._rpn_proposal((deltas.reshape(-1, 4), anchors, fg, list(shape)), training=t) for t in (True, False)}
+    assert rois[True].shape[0] > 0 and rois[False].shape[0] > 0
+    # predict_rois: ProposalTarget's sampled RoIs of the training-mode proposals, drawn with the same image id
+    first = m._proposal_target._next_image_id
+    got = m.predict_rois(img, gt, gl)
+    m._proposal_target._next_image_id = first
+    want = m._proposal_target((rois[True], gt, gl), True)[0]
+    assert got.shape[0] > 0 and torch.equal(got, want)
+    # predict_rpns: the anchors labelled positive
+    first = m._anchor_target._next_image_id
+    got = m.predict_rpns(list(shape), gt)
+    m._anchor_target._next_image_id = first
+    labels = m._anchor_target((gt, list(shape), anchors), True)[0]
+    want = anchors[torch.nonzero(labels > 0)[:, 0]]
+    assert got.shape[0] > 0 and torch.equal(got, want)
+    # im_detect: the test-mode proposals in level order, divided by the scale
+    k = int(rois[False].shape[0])
+    perm = ops.assign_levels(rois[False], 2, 5)[2][:k].long()
+    assert np.array_equal(np.sort(perm.cpu().numpy()), np.arange(k))
+    s, d, r = m.im_detect(img, 1.25)
+    assert s.shape == (k, 21) and d.shape == (k, 84)
+    np.testing.assert_array_equal(r.cpu().numpy(), rois[False][perm].cpu().numpy() / np.float32(1.25))

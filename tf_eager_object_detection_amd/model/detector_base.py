@@ -25,6 +25,12 @@ def _pad_rows64(t):
     return out
 
 
+def _nhwc(x):
+    """the NHWC memory of a channels_last [B,C,H,W] tensor as a contiguous [B,H,W,C] view"""
+    y = x.permute(0, 2, 3, 1)
+    return y if y.is_contiguous() else y.contiguous()
+
+
 def check_caller_f32_form(form):
     """the reference-surface caller objects (base_fpn_model.py, base_faster_rcnn_model.py) take every float32 form; with 'x2'
     their call / im_detect / predict_rois read the dense part's range status word after the pass and repeat an out-of-range

@@ -36,7 +36,7 @@ from ..derived import derived
 from ..pipeline import FpnHotPath, FpnStepBatch
 # (the detectors' shared pass lives in detector_base.py; its names stay importable from here)
 from .detector_base import DEFAULT_BLIND_CHUNKS, Detector, _FinalLayer, _FinalTrainable, _NmsCompleteness, _in_f32_form, \
-    _pad_rows64, _x3_workspace_of, caller_range_checked, check_caller_f32_form  # noqa: F401
+    _nhwc, _pad_rows64, _x3_workspace_of, caller_range_checked, check_caller_f32_form  # noqa: F401
 
 __all__ = ['ResNetFpnDetector', 'tf_legacy_resize_bilinear']
 
@@ -69,12 +69,6 @@ def _no_kernel(what, conv, x):
                         '%s); the detectors run float16 / float32 NHWC maps on the GPU and have no library or CPU route'
                         % (what, tuple(conv.kernel_size), tuple(conv.stride), conv.in_channels, conv.out_channels,
                            tuple(x.shape), x.dtype, x.device))
-
-
-def _nhwc(x):
-    """the NHWC memory of a channels_last [B,C,H,W] tensor as a contiguous [B,H,W,C] view"""
-    y = x.permute(0, 2, 3, 1)
-    return y if y.is_contiguous() else y.contiguous()
 
 
 def _mfma_ok(conv, x):

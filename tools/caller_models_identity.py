@@ -1,0 +1,178 @@
+#!/usr/bin/env python
+"""The caller models of two source trees against each other, through their public surface only: the same file runs on a checkout of
+an earlier commit and on the present tree (profiles/caller_models_refactor.json).
+
+  python tools/caller_models_identity.py --parent DIR [--new DIR] --out FILE.json
+
+DIR is a source tree with its library built.  Every leg runs parent / new / parent, each in a fresh process under its own time
+limit; the first failure ends the chain (nothing more is started) and the file says where.  A leg's process does, in this order:
+one inference call, one im_detect, predict_rois / predict_roi, two training calls each followed by sum(losses).backward() -- and
+keeps, per step, the ordered names of the native entry points (_lib.recording), SHA-256 of every output, of the four losses and of
+every parameter gradient in named_parameters() order, and the three image-id counters; then it times one call (training: forward +
+backward; the plain models: inference), eager, synchronised on both sides, 3 warm-ups, 20 samples.
+
+Identity: what differs between the two parent runs is listed and left out of the claim; everything else must be equal between
+parent and new.  Time: new <= max(parent runs) + |parent_1 - parent_2| on the medians."""
+import argparse
+import hashlib
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+GT = {'fpn': ([[30., 40., 200., 180.], [100., 60., 330., 250.]], [3, 7]),                    # tests/test_caller_models.py
+      'single': ([[40.0, 30.0, 170.0, 160.0], [60.0, 50.0, 240.0, 150.0]], [3, 12])}       # tests/test_c4_grad_gpu.py, test_vgg_grad_gpu.py
+# leg -> (module, class, keywords, image shape, image seed, model seed, ground truth, what is timed)
+LEGS = {
+    'fpn_4flags': ('base_fpn_model', 'ResnetV1Fpn', dict(depth=50, train_roi_head=True, train_rpn_head=True, train_neck=True,
+                                                          train_extractor=True), (256, 352), 1, 1, 'fpn', 'training'),
+    'c4_3flags': ('base_faster_rcnn_model', 'TrainableResNetFasterRcnn',
+                  dict(depth=50, roi_pooling_max_pooling_flag=False, train_roi_head=True, train_rpn_head=True, train_extractor=True),
+                  (208, 256), 6, 3, 'single', 'training'),
+    'vgg16_3flags': ('base_faster_rcnn_model', 'Vgg16FasterRcnn',
+                     dict(train_roi_head=True, train_rpn_head=True, train_extractor=True, dropout_seed=3), (208, 256), 6, 3, 'single',
+                     'training'),
+    'fpn_plain': ('base_fpn_model', 'ResnetV1Fpn', dict(depth=50), (256, 352), 1, 1, 'fpn', 'inference'),
+    'c4_plain': ('base_faster_rcnn_model', 'ResNetFasterRcnn', dict(depth=50, roi_pooling_max_pooling_flag=False), (208, 256), 6, 3,
+                 'single', 'inference'),
+}
+RUNS = [(leg, losses) for leg in ('fpn_4flags', 'c4_3flags', 'vgg16_3flags') for losses in ('hip', 'torch')] + \
+       [('fpn_plain', 'hip'), ('c4_plain', 'hip')]
+CHILD_LIMIT_S = 240
+
+
+def _sha(t):
+    import torch
+    if t is None:
+        return 'none'
+    if isinstance(t, torch.Tensor):
+        t = t.detach().contiguous().cpu()
+        return hashlib.sha256(str((t.dtype, tuple(t.shape))).encode() + t.numpy().tobytes()).hexdigest()
+    return hashlib.sha256(repr(t).encode()).hexdigest()
+
+
+def child(root, leg, losses, out):
+    sys.path.insert(0, root)
+    import importlib
+    import numpy as np
+    import torch
+    from tf_eager_object_detection_amd import _lib
+    module, cls, kw, shape, image_seed, model_seed, gt_key, timed = LEGS[leg]
+    ctor = getattr(importlib.import_module('tf_eager_object_detection_amd.model.' + module), cls)
+    torch.manual_seed(model_seed)
+    m = ctor(training_targets=losses, training_losses=losses, **kw)
+    rng = np.random.default_rng(image_seed)
+    img = torch.from_numpy((rng.uniform(0, 255, (1,) + shape + (3,)) - 110).astype(np.float32)).cuda()
+    gt, gl = torch.tensor(GT[gt_key][0], device='cuda'), torch.tensor(GT[gt_key][1], device='cuda')
+    params = list(m.named_parameters())
+    torch.manual_seed(11)                                       # (the 'torch' target layers draw their samples from this generator)
+
+    def counters():
+        return [getattr(m._anchor_target, '_next_image_id', None), getattr(m._proposal_target, '_next_image_id', None),
+                getattr(m, '_next_dropout_image_id', None)]
+
+    def train():
+        m.zero_grad(set_to_none=True)
+        step = m((img, gt, gl), training=True)
+        if any(x.requires_grad for x in step):
+            sum(step).backward()
+        return list(step) + [p.grad for _, p in params]
+
+    steps = [('inference', lambda: list(m(img, training=False))), ('im_detect', lambda: list(m.im_detect(img, 1.25))),
+             ('predict', lambda: [m.predict_rois(img, gt, gl)] if gt_key == 'fpn' else list(m.predict_roi(img, gt, gl))),
+             ('training_1', train), ('training_2', train)]
+    record = {}
+    for name, fn in steps:
+        with _lib.recording() as calls:
+            result = fn()
+            torch.cuda.synchronize()
+        names = [getattr(c[0], '__name__', str(c[0])) for c in calls]
+        record[name] = dict(native_calls=len(names), call_list_sha256=hashlib.sha256('\n'.join(names).encode()).hexdigest(),
+                            call_list=names, hashes=[_sha(x) for x in result], counters=counters())
+    record['training_1']['trained_parameters'] = sum(1 for _, p in params if p.grad is not None)
+    call = train if timed == 'training' else (lambda: m(img, training=False))
+    ms = []
+    for i in range(23):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call()
+        torch.cuda.synchronize()
+        if i >= 3:
+            ms.append((time.perf_counter() - t0) * 1e3)
+    record['timing'] = dict(what=timed, median_ms=round(statistics.median(ms), 3), min_max_ms=[round(min(ms), 3), round(max(ms), 3)])
+    with open(out, 'w') as f:
+        json.dump(record, f)
+
+
+def _compare(a, b):
+    """-> the (step, quantity) pairs on which two records of one leg differ"""
+    diff = []
+    for step in a:
+        if step == 'timing':
+            continue
+        for key in ('call_list', 'hashes', 'counters'):
+            if a[step][key] != b[step][key]:
+                diff.append('%s: %s' % (step, key))
+    return diff
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--child', nargs=4, metavar=('ROOT', 'LEG', 'LOSSES', 'OUT'))
+    ap.add_argument('--parent')
+    ap.add_argument('--new', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument('--out')
+    ap.add_argument('--only', nargs='*', help='legs to run (default: all)')
+    args = ap.parse_args()
+    if args.child:
+        return child(*args.child)
+    work = os.path.dirname(os.path.abspath(args.out))
+    result = {'acceptance_identity': 'call lists equal as lists, every hash and counter equal, but for what two parent runs differ on',
+              'acceptance_time': 'new <= max(parent runs) + |parent_1 - parent_2| (medians of 20, ms)', 'legs': {}}
+    status = 0
+    for leg, losses in RUNS:
+        if args.only and leg not in args.only:
+            continue
+        key = '%s, training_losses=%s' % (leg, losses) if LEGS[leg][7] == 'training' else leg
+        recs = {}
+        for run, root in (('parent_1', args.parent), ('new', args.new), ('parent_2', args.parent)):
+            tmp = os.path.join(work, 'leg_%s_%s_%s.json' % (leg, losses, run))
+            cmd = [sys.executable, os.path.abspath(__file__), '--child', os.path.abspath(root), leg, losses, tmp]
+            try:
+                rc = subprocess.run(cmd, timeout=CHILD_LIMIT_S).returncode
+            except subprocess.TimeoutExpired:
+                rc = 124
+            if rc != 0:
+                result['stopped_at'] = dict(leg=key, run=run, exit_status=rc)
+                status = 1
+                break
+            recs[run] = json.load(open(tmp))
+            print(key, run, recs[run]['timing'], flush=True)
+        if status:
+            break
+        noise = _compare(recs['parent_1'], recs['parent_2'])
+        diff = [d for d in _compare(recs['parent_1'], recs['new']) if d not in noise]
+        t = {r: recs[r]['timing'] for r in recs}
+        med = {r: t[r]['median_ms'] for r in t}
+        spread = abs(med['parent_1'] - med['parent_2'])
+        ok_time = med['new'] <= max(med['parent_1'], med['parent_2']) + spread
+        result['legs'][key] = dict(
+            steps={s: dict(native_calls=v['native_calls'], call_list_sha256=v['call_list_sha256'], tensors_hashed=len(v['hashes']),
+                           counters_after=v['counters']) for s, v in recs['new'].items() if s != 'timing'},
+            trained_parameters=recs['new']['training_1']['trained_parameters'],
+            differs_between_the_two_parent_runs=noise, differs_between_parent_and_new=diff,
+            identical=not diff, timed=t['new']['what'], median_ms=med, min_max_ms={r: t[r]['min_max_ms'] for r in t},
+            parent_runs_differ_by_ms=round(spread, 3),
+            verdict_time='ACCEPTED' if ok_time else 'NOT ACCEPTED: new is slower than the slower parent run by more than the parent runs differ')
+        if diff:
+            status = 1
+    with open(args.out, 'w') as f:
+        json.dump(result, f, indent=1)
+    print('identical legs: %d of %d' % (sum(1 for v in result['legs'].values() if v['identical']), len(result['legs'])))
+    return status
+
+
+if __name__ == '__main__':
+    sys.exit(main())
