@@ -1347,6 +1347,30 @@ typedef struct {
 size_t odet_conv3x3_wgrad_workspace_bytes(const odet_conv_grad_level_t* levels, int num_levels, int batch, int cin, int cout);
 int odet_conv3x3_wgrad_f32_levels(const odet_conv_grad_level_t* levels, int num_levels, float* dw, float* db, int batch, int cin,
                                   int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream);
+/* ---- Split-precision backward (added within 103) ---------------------------------------------------------------------
+ * The three gradient contractions above on the bfloat16 matrix instruction, in the arithmetic of odet_conv3x3_x3_levels: every
+ * float32 operand (dz after its ReLU gate included) is split in the kernel into three bfloat16 limbs whose sum is the
+ * operand exactly, a product is six limb products, each exact in float32, added in float32 accumulators (dropped: three limb
+ * products below 2^-23 of the product).  Same tensors, layouts, argument rules, error codes and error texts (under the entry
+ * point's own name) as odet_dense_dgrad_f32 / odet_dense_wgrad_f32 / odet_conv3x3_wgrad_f32_levels; the workspace is sized by
+ * the form's OWN queries (its split rule differs: K / parts >= 128).  db is not part of the form: it is the same
+ * ordered float32 sum, bit-equal to the exact entry points'.  Order of sums: a function of the shapes alone, no atomics --
+ * bit-equal from call to call; a K-step's 32 k are added inside one matrix instruction per limb product (inner order
+ * undocumented), K-steps ascending, parts in ascending order.  Exact on data whose limb products and partial sums are
+ * representable (integers below 2^8 in magnitude with sums below 2^24, among others).
+ * odet_*_x3_plan: the launch a shape gets -- the workgroup tile's edge (64 or 128) and the number of parts -- from the same
+ * shape rules as the entry points (ODET_E_INVALID on a shape they refuse), without any device call. */
+size_t odet_dense_grad_x3_workspace_bytes(int wgrad, int rows, int cin, int cout);
+int odet_dense_grad_x3_plan(int wgrad, int rows, int cin, int cout, int* tile_edge, int* parts);
+int odet_dense_dgrad_x3(const float* dy, const float* w, const float* y_relu, const float* x_relu, float* dx, int rows, int cin,
+                        int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream);
+int odet_dense_wgrad_x3(const float* dy, const float* x, const float* y_relu, float* dw, float* db, int rows, int cin, int cout,
+                        void* workspace, size_t workspace_bytes, odet_stream_t stream);
+size_t odet_conv3x3_wgrad_x3_workspace_bytes(const odet_conv_grad_level_t* levels, int num_levels, int batch, int cin, int cout);
+int odet_conv3x3_wgrad_x3_plan(const odet_conv_grad_level_t* levels, int num_levels, int batch, int cin, int cout, int* tile_edge,
+                               int* parts);
+int odet_conv3x3_wgrad_x3_levels(const odet_conv_grad_level_t* levels, int num_levels, float* dw, float* db, int batch, int cin,
+                                 int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream);
 /* The inverse of odet_rpn_pack_pair's index map, for the backward pass of the RpnHead's two 1x1 convolutions run as one
  * contraction: from d_scores [B,N,2] and d_deltas [B,N,4] (float32; image strides and the level's offsets in VALUES, as in
  * odet_rpn_pack_pair) the level's gradient level_grad [B * pixels, channels] of the PADDED pair output -- columns 0 .. 2A - 1

@@ -244,6 +244,13 @@ SIGNATURES = {
     'odet_dense_wgrad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     'odet_conv3x3_wgrad_workspace_bytes': (_sz, [_vp, _i, _i, _i, _i]),
     'odet_conv3x3_wgrad_f32_levels': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    'odet_dense_grad_x3_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'odet_dense_grad_x3_plan': (_i, [_i, _i, _i, _i, _vp, _vp]),
+    'odet_dense_dgrad_x3': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    'odet_dense_wgrad_x3': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
+    'odet_conv3x3_wgrad_x3_workspace_bytes': (_sz, [_vp, _i, _i, _i, _i]),
+    'odet_conv3x3_wgrad_x3_plan': (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    'odet_conv3x3_wgrad_x3_levels': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     'odet_rpn_unpack_pair': (_i, [_vp, C.c_longlong, C.c_longlong, _vp, C.c_longlong, C.c_longlong, C.c_longlong, _i, _i, _i, _vp,
                                   _vp]),
     'odet_roi_pool_argmax': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),

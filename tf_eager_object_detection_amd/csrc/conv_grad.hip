@@ -41,8 +41,12 @@ struct ConvGradParams {
   int num_levels, cin, cout, K, kper;
 };
 
-template <int WT>
-__global__ void __launch_bounds__(256) k_conv3x3_wgrad_f32(ConvGradParams p) {
+// ONE kernel for both forms (X3: grad_gemm.h's split-precision tile routine).  s_lv lies in front of the dynamic region, whose
+// start the split-precision routine's transposed LDS reads need 16-byte aligned: the table's size is a multiple of 16 and the
+// region is declared 16-byte aligned
+static_assert(sizeof(ConvGradLevel) * ODET_MAX_LEVELS % 16 == 0, "the level table must keep the dynamic LDS 16-byte aligned");
+template <int WT, bool X3>
+__global__ void __launch_bounds__(256) k_conv3x3_wgrad(ConvGradParams p) {
   constexpr int T = 32 * WT;
   constexpr int PER = T / 32;
   __shared__ ConvGradLevel s_lv[ODET_MAX_LEVELS];
@@ -96,7 +100,8 @@ __global__ void __launch_bounds__(256) k_conv3x3_wgrad_f32(ConvGradParams p) {
       }
     }
   };
-  dg_tile<WT, true>(fetch, kbeg, kend, m0, n0, M, N, M, nullptr, p.out + (long long)blockIdx.z * N * M);
+  if constexpr (X3) dg_tile_x3<WT, true>(fetch, kbeg, kend, m0, n0, M, N, M, nullptr, p.out + (long long)blockIdx.z * N * M);
+  else dg_tile<WT, true>(fetch, kbeg, kend, m0, n0, M, N, M, nullptr, p.out + (long long)blockIdx.z * N * M);
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
@@ -117,6 +122,20 @@ static ConvGradPlan cg_plan(long long K, int cin, int cout) {
   pl.tiles = (long long)((9 * cin + T - 1) / T) * ((cout + T - 1) / T);
   long long parts = 1;
   if (K >= 256) parts = std::max<long long>(1, std::min<long long>(std::min<long long>(512 / pl.tiles, K / 64), 16));
+  pl.parts = dg_split(K, parts, &pl.kper);
+  return pl;
+}
+
+// The split-precision form's (X3 = true): the same tile rule and target of 512 workgroups, cut so that K / parts >= 128, not
+// 64 (dense_grad.hip's dgx_plan: an assumption about a K-step's cost that the measured launches do not bear out; a shape rule)
+static ConvGradPlan cgx_plan(long long K, int cin, int cout) {
+  ConvGradPlan pl;
+  pl.K = K;
+  pl.wt = (cin % 128 == 0 && cout % 128 == 0) ? 4 : 2;
+  const int T = 32 * pl.wt;
+  pl.tiles = (long long)((9 * cin + T - 1) / T) * ((cout + T - 1) / T);
+  long long parts = 1;
+  if (K >= 256) parts = std::max<long long>(1, std::min<long long>(std::min<long long>(512 / pl.tiles, K / 128), 16));
   pl.parts = dg_split(K, parts, &pl.kper);
   return pl;
 }
@@ -148,23 +167,50 @@ static int cg_check_shapes(const char* who, const odet_conv_grad_level_t* levels
   return ODET_OK;
 }
 
-extern "C" size_t odet_conv3x3_wgrad_workspace_bytes(const odet_conv_grad_level_t* levels, int num_levels, int batch, int cin,
-                                                     int cout) {
+static size_t cg_workspace_bytes(bool x3, const odet_conv_grad_level_t* levels, int num_levels, int batch, int cin, int cout) {
   long long K;
   if (!levels || num_levels < 1 || num_levels > ODET_MAX_LEVELS || batch < 1 || cin < 1 || cout < 1) return 0;
   if (cg_walk_levels(levels, num_levels, batch, &K) != num_levels) return 0;
-  return dg_workspace_bytes(cg_plan(K, cin, cout).parts, cout, 9ll * cin);
+  return dg_workspace_bytes((x3 ? cgx_plan(K, cin, cout) : cg_plan(K, cin, cout)).parts, cout, 9ll * cin);
+}
+
+extern "C" size_t odet_conv3x3_wgrad_workspace_bytes(const odet_conv_grad_level_t* levels, int num_levels, int batch, int cin,
+                                                     int cout) {
+  return cg_workspace_bytes(false, levels, num_levels, batch, cin, cout);
+}
+
+extern "C" size_t odet_conv3x3_wgrad_x3_workspace_bytes(const odet_conv_grad_level_t* levels, int num_levels, int batch, int cin,
+                                                        int cout) {
+  return cg_workspace_bytes(true, levels, num_levels, batch, cin, cout);
+}
+
+extern "C" int odet_conv3x3_wgrad_x3_plan(const odet_conv_grad_level_t* levels, int num_levels, int batch, int cin, int cout,
+                                          int* tile_edge, int* parts) {
+  const char* who = "odet_conv3x3_wgrad_x3_plan";
+  long long K;
+  ODET_REQUIRE(tile_edge && parts, "%s: null pointer", who);
+  const int rs = cg_check_shapes(who, levels, num_levels, batch, cin, cout, &K);
+  if (rs != ODET_OK) return rs;
+  const ConvGradPlan pl = cgx_plan(K, cin, cout);
+  *tile_edge = 32 * pl.wt; *parts = pl.parts;
+  return ODET_OK;
 }
 
 static hipError_t cg_prepare_kernels() {
-  static const void* const kernels[] = {(const void*)k_conv3x3_wgrad_f32<4>, (const void*)k_conv3x3_wgrad_f32<2>};
+  static const void* const kernels[] = {(const void*)k_conv3x3_wgrad<4, false>, (const void*)k_conv3x3_wgrad<2, false>};
   static OdetPerDeviceOnce once;
   return conv_f32_raise_lds_limit(&once, kernels, sizeof(kernels) / sizeof(kernels[0]), DG_LDS_MAX);
 }
 
-extern "C" int odet_conv3x3_wgrad_f32_levels(const odet_conv_grad_level_t* levels, int num_levels, float* dw, float* db, int batch,
-                                             int cin, int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
-  const char* who = "odet_conv3x3_wgrad_f32_levels";
+static hipError_t cgx_prepare_kernels() {
+  static const void* const kernels[] = {(const void*)k_conv3x3_wgrad<4, true>, (const void*)k_conv3x3_wgrad<2, true>};
+  static OdetPerDeviceOnce once;
+  return conv_f32_raise_lds_limit(&once, kernels, sizeof(kernels) / sizeof(kernels[0]), DG_X3_LDS_MAX);
+}
+
+// (db is not part of the split-precision form: the same ordered float32 sums, the same bits, in either)
+static int cg_wgrad(const char* who, bool x3, const odet_conv_grad_level_t* levels, int num_levels, float* dw, float* db, int batch,
+                    int cin, int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
   long long K;
   ODET_REQUIRE(dw, "%s: null pointer", who);
   const int rs = cg_check_shapes(who, levels, num_levels, batch, cin, cout, &K);
@@ -175,12 +221,13 @@ extern "C" int odet_conv3x3_wgrad_f32_levels(const odet_conv_grad_level_t* level
     ODET_REQUIRE(((uintptr_t)levels[l].x | (uintptr_t)levels[l].dy | (uintptr_t)levels[l].y_relu) % 16 == 0,
                  "%s: maps must be 16-byte aligned", who);
   }
-  const ConvGradPlan pl = cg_plan(K, cin, cout);
+  const ConvGradPlan pl = x3 ? cgx_plan(K, cin, cout) : cg_plan(K, cin, cout);
   const size_t need = dg_workspace_bytes(pl.parts, cout, 9ll * cin);
-  const int rw = dg_check_workspace(who, "odet_conv3x3_wgrad_workspace_bytes", need, workspace, workspace_bytes);
+  const int rw = dg_check_workspace(who, x3 ? "odet_conv3x3_wgrad_x3_workspace_bytes" : "odet_conv3x3_wgrad_workspace_bytes", need,
+                                    workspace, workspace_bytes);
   if (rw != ODET_OK) return rw;
   const hipStream_t st = (hipStream_t)stream;
-  ODET_HIP(cg_prepare_kernels());
+  ODET_HIP(x3 ? cgx_prepare_kernels() : cg_prepare_kernels());
   ConvGradParams p = {};
   DgBiasRows rows = {};
   int k = 0;
@@ -197,12 +244,30 @@ extern "C" int odet_conv3x3_wgrad_f32_levels(const odet_conv_grad_level_t* level
   p.out = need ? (float*)workspace : dw;
   p.num_levels = num_levels; p.cin = cin; p.cout = cout; p.K = (int)pl.K; p.kper = pl.kper;
   const dim3 grid((unsigned)pl.tiles, 1, (unsigned)pl.parts);
-  if (pl.wt == 4) hipLaunchKernelGGL(k_conv3x3_wgrad_f32<4>, grid, dim3(256), dg_lds_bytes(4), st, p);
-  else hipLaunchKernelGGL(k_conv3x3_wgrad_f32<2>, grid, dim3(256), dg_lds_bytes(2), st, p);
+  if (x3) {
+    const unsigned lds = dg_x3_lds_bytes(pl.wt, true);
+    if (pl.wt == 4) hipLaunchKernelGGL((k_conv3x3_wgrad<4, true>), grid, dim3(256), lds, st, p);
+    else hipLaunchKernelGGL((k_conv3x3_wgrad<2, true>), grid, dim3(256), lds, st, p);
+  } else {
+    if (pl.wt == 4) hipLaunchKernelGGL((k_conv3x3_wgrad<4, false>), grid, dim3(256), dg_lds_bytes(4), st, p);
+    else hipLaunchKernelGGL((k_conv3x3_wgrad<2, false>), grid, dim3(256), dg_lds_bytes(2), st, p);
+  }
   ODET_LAUNCH_CHECK();
   if (need) {
     const int rr = dg_reduce_parts((const float*)workspace, pl.parts, (long long)cout * 9 * cin / 4, nullptr, dw, st);
     if (rr != ODET_OK) return rr;
   }
   return db ? dg_bias_grad(rows, db, cout, st) : ODET_OK;
+}
+
+extern "C" int odet_conv3x3_wgrad_f32_levels(const odet_conv_grad_level_t* levels, int num_levels, float* dw, float* db, int batch,
+                                             int cin, int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
+  return cg_wgrad("odet_conv3x3_wgrad_f32_levels", false, levels, num_levels, dw, db, batch, cin, cout, workspace, workspace_bytes,
+                  stream);
+}
+
+extern "C" int odet_conv3x3_wgrad_x3_levels(const odet_conv_grad_level_t* levels, int num_levels, float* dw, float* db, int batch,
+                                            int cin, int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
+  return cg_wgrad("odet_conv3x3_wgrad_x3_levels", true, levels, num_levels, dw, db, batch, cin, cout, workspace, workspace_bytes,
+                  stream);
 }

@@ -41,12 +41,10 @@
 
 #include "conv_f32_common.h"
 #include "conv_diag.h"
+#include "x3_split.h"
 
-typedef __bf16 x3b8 __attribute__((ext_vector_type(8)));
-typedef __bf16 x3b2 __attribute__((ext_vector_type(2)));
 typedef _Float16 x2h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 x2h2 __attribute__((ext_vector_type(2)));
-typedef float x3f2 __attribute__((ext_vector_type(2)));
 typedef unsigned int x3u4 __attribute__((ext_vector_type(4)));
 typedef unsigned int x3u2 __attribute__((ext_vector_type(2)));
 typedef __amdgpu_buffer_rsrc_t x3_rsrc_t;
@@ -59,20 +57,6 @@ typedef __attribute__((address_space(3))) void* x3_lds_ptr;
 #ifndef X3_NA
 #define X3_NA(NS) (NS)
 #endif
-
-// two float32 -> their three bfloat16 limbs, packed (low half = first value)
-__device__ __forceinline__ void x3_split2(const x3f2 a, unsigned& h, unsigned& m, unsigned& l) {
-  const x3b2 hb = __builtin_convertvector(a, x3b2);
-  h = __builtin_bit_cast(unsigned, hb);
-  const x3f2 hf = {__builtin_bit_cast(float, h << 16), __builtin_bit_cast(float, h & 0xFFFF0000u)};
-  const x3f2 r1 = a - hf;                                 // exact (the difference has at most 16 significant bits)
-  const x3b2 mb = __builtin_convertvector(r1, x3b2);
-  m = __builtin_bit_cast(unsigned, mb);
-  const x3f2 mf = {__builtin_bit_cast(float, m << 16), __builtin_bit_cast(float, m & 0xFFFF0000u)};
-  const x3f2 r2 = r1 - mf;                                // exact (at most 8 significant bits are left)
-  const x3b2 lb = __builtin_convertvector(r2, x3b2);
-  l = __builtin_bit_cast(unsigned, lb);
-}
 
 // two float32 -> their two float16 limbs, packed: a ~ h + l * 2^-11, h = f16(a), l = f16((a - h) * 2^11) (the low limb scaled
 // into float16's normal range; |a| > 65504 gives infinities -- and a NaN result -- never a wrong finite number)

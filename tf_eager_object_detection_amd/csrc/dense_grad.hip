@@ -43,9 +43,10 @@ struct DenseGradParams {
   int M, N, K, kper;              // part z of a launch takes k in [z * kper, min(K, (z + 1) * kper)); kper % DG_BK == 0
 };
 
-// the tile routine of grad_gemm.h on operands that are plain row-major matrices
-template <int WT, bool BKMAJOR>
-__global__ void __launch_bounds__(256) k_dense_grad_f32(DenseGradParams p) {
+// the tile routines of grad_gemm.h (X3: the split-precision one) on operands that are plain row-major matrices: ONE operand
+// fetch for both forms
+template <int WT, bool BKMAJOR, bool X3>
+__global__ void __launch_bounds__(256) k_dense_grad(DenseGradParams p) {
   constexpr int T = 32 * WT;
   constexpr int PER = T / 32;
   const int tid = threadIdx.x;
@@ -85,7 +86,8 @@ __global__ void __launch_bounds__(256) k_dense_grad_f32(DenseGradParams p) {
       }
     }
   };
-  dg_tile<WT, BKMAJOR>(fetch, kbeg, kend, m0, n0, M, N, M, p.omask, p.out + (long long)blockIdx.z * N * M);
+  if constexpr (X3) dg_tile_x3<WT, BKMAJOR>(fetch, kbeg, kend, m0, n0, M, N, M, p.omask, p.out + (long long)blockIdx.z * N * M);
+  else dg_tile<WT, BKMAJOR>(fetch, kbeg, kend, m0, n0, M, N, M, p.omask, p.out + (long long)blockIdx.z * N * M);
 }
 
 // the parts of a split launch, added in the order 0 .. ksplit - 1, and the epilogue mask
@@ -252,36 +254,85 @@ static int dg_check_shape(const char* who, int rows, int cin, int cout) {
   return ODET_OK;
 }
 
+// the split-precision form's tile and split (grad_gemm.h: dg_tile_x3) -- again a function of the shape alone.  The same tile
+// rule (128 x 128, one workgroup per CU at that form's LDS size, where every CU still gets one); the contraction is cut so
+// that K / parts >= 128, not 64 -- chosen on the ASSUMPTION that a K-step would cost about a third of the exact form's, which the
+// measured launches do not bear out (tools/grad_x3_bench.py: the step is bound by the in-kernel split); kept as a shape rule
+static DenseGradPlan dgx_plan(int M, int N, int K) {
+  DenseGradPlan pl;
+  const long long t128 = (long long)((M + 127) / 128) * ((N + 127) / 128);
+  pl.wt = t128 >= 256 ? 4 : 2;
+  const int T = 32 * pl.wt;
+  pl.tiles = (long long)((M + T - 1) / T) * ((N + T - 1) / T);
+  int ks = 1;
+  if (pl.tiles <= 128 && K >= 256) ks = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(256 / pl.tiles, K / 128), 8));
+  pl.ksplit = dg_split(K, ks, &pl.kper);
+  return pl;
+}
+
+static DenseGradPlan dg_plan_of(bool x3, int wgrad, int rows, int cin, int cout) {
+  const int N = wgrad ? cout : rows, K = wgrad ? rows : cout;
+  return x3 ? dgx_plan(cin, N, K) : dg_plan(cin, N, K);
+}
+
 extern "C" size_t odet_dense_grad_workspace_bytes(int wgrad, int rows, int cin, int cout) {
   if (rows < 1 || cin < 1 || cout < 1) return 0;
-  const DenseGradPlan pl = wgrad ? dg_plan(cin, cout, rows) : dg_plan(cin, rows, cout);
-  return dg_workspace_bytes(pl.ksplit, wgrad ? cout : rows, cin);
+  return dg_workspace_bytes(dg_plan_of(false, wgrad, rows, cin, cout).ksplit, wgrad ? cout : rows, cin);
+}
+
+extern "C" size_t odet_dense_grad_x3_workspace_bytes(int wgrad, int rows, int cin, int cout) {
+  if (rows < 1 || cin < 1 || cout < 1) return 0;
+  return dg_workspace_bytes(dg_plan_of(true, wgrad, rows, cin, cout).ksplit, wgrad ? cout : rows, cin);
+}
+
+extern "C" int odet_dense_grad_x3_plan(int wgrad, int rows, int cin, int cout, int* tile_edge, int* parts) {
+  const char* who = "odet_dense_grad_x3_plan";
+  ODET_REQUIRE(tile_edge && parts, "%s: null pointer", who);
+  const int rs = dg_check_shape(who, rows, cin, cout);
+  if (rs != ODET_OK) return rs;
+  const DenseGradPlan pl = dg_plan_of(true, wgrad, rows, cin, cout);
+  *tile_edge = 32 * pl.wt; *parts = pl.ksplit;
+  return ODET_OK;
 }
 
 static hipError_t dg_prepare_kernels() {
-  static const void* const kernels[] = {(const void*)k_dense_grad_f32<4, true>, (const void*)k_dense_grad_f32<4, false>,
-                                        (const void*)k_dense_grad_f32<2, true>, (const void*)k_dense_grad_f32<2, false>};
+  static const void* const kernels[] = {(const void*)k_dense_grad<4, true, false>, (const void*)k_dense_grad<4, false, false>,
+                                        (const void*)k_dense_grad<2, true, false>, (const void*)k_dense_grad<2, false, false>};
   static OdetPerDeviceOnce once;
   return conv_f32_raise_lds_limit(&once, kernels, sizeof(kernels) / sizeof(kernels[0]), DG_LDS_MAX);
 }
 
+static hipError_t dgx_prepare_kernels() {
+  static const void* const kernels[] = {(const void*)k_dense_grad<4, true, true>, (const void*)k_dense_grad<4, false, true>,
+                                        (const void*)k_dense_grad<2, true, true>, (const void*)k_dense_grad<2, false, true>};
+  static OdetPerDeviceOnce once;
+  return conv_f32_raise_lds_limit(&once, kernels, sizeof(kernels) / sizeof(kernels[0]), DG_X3_LDS_MAX);
+}
+
 // C [N][M] = A^T-free contraction of the file comment; every argument already checked
 template <bool BKMAJOR>
-static int dg_launch(const char* who, const float* a, const float* b, const float* bmask, const float* omask, float* out, int M, int N,
-                     int K, void* workspace, size_t workspace_bytes, hipStream_t st) {
-  const DenseGradPlan pl = dg_plan(M, N, K);
+static int dg_launch(const char* who, bool x3, const float* a, const float* b, const float* bmask, const float* omask, float* out,
+                     int M, int N, int K, void* workspace, size_t workspace_bytes, hipStream_t st) {
+  const DenseGradPlan pl = x3 ? dgx_plan(M, N, K) : dg_plan(M, N, K);
   ODET_REQUIRE(pl.tiles < (1ll << 31), "%s: too many workgroups", who);
   const size_t need = dg_workspace_bytes(pl.ksplit, N, M);
-  const int rw = dg_check_workspace(who, "odet_dense_grad_workspace_bytes", need, workspace, workspace_bytes);
+  const int rw = dg_check_workspace(who, x3 ? "odet_dense_grad_x3_workspace_bytes" : "odet_dense_grad_workspace_bytes", need,
+                                    workspace, workspace_bytes);
   if (rw != ODET_OK) return rw;
-  ODET_HIP(dg_prepare_kernels());
+  ODET_HIP(x3 ? dgx_prepare_kernels() : dg_prepare_kernels());
   DenseGradParams p;
   p.a = a; p.b = b; p.bmask = bmask; p.omask = need ? nullptr : omask; p.out = need ? (float*)workspace : out;
   p.M = M; p.N = N; p.K = K; p.kper = pl.kper;
-  const unsigned lds = dg_lds_bytes(pl.wt);
   const dim3 grid((unsigned)pl.tiles, 1, (unsigned)pl.ksplit);
-  if (pl.wt == 4) hipLaunchKernelGGL((k_dense_grad_f32<4, BKMAJOR>), grid, dim3(256), lds, st, p);
-  else hipLaunchKernelGGL((k_dense_grad_f32<2, BKMAJOR>), grid, dim3(256), lds, st, p);
+  if (x3) {
+    const unsigned lds = dg_x3_lds_bytes(pl.wt, BKMAJOR);
+    if (pl.wt == 4) hipLaunchKernelGGL((k_dense_grad<4, BKMAJOR, true>), grid, dim3(256), lds, st, p);
+    else hipLaunchKernelGGL((k_dense_grad<2, BKMAJOR, true>), grid, dim3(256), lds, st, p);
+  } else {
+    const unsigned lds = dg_lds_bytes(pl.wt);
+    if (pl.wt == 4) hipLaunchKernelGGL((k_dense_grad<4, BKMAJOR, false>), grid, dim3(256), lds, st, p);
+    else hipLaunchKernelGGL((k_dense_grad<2, BKMAJOR, false>), grid, dim3(256), lds, st, p);
+  }
   ODET_LAUNCH_CHECK();
   if (need) {
     return dg_reduce_parts((const float*)workspace, pl.ksplit, (long long)N * M / 4, omask, out, st);
@@ -289,26 +340,25 @@ static int dg_launch(const char* who, const float* a, const float* b, const floa
   return ODET_OK;
 }
 
-extern "C" int odet_dense_dgrad_f32(const float* dy, const float* w, const float* y_relu, const float* x_relu, float* dx, int rows,
-                                    int cin, int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
-  const char* who = "odet_dense_dgrad_f32";
+static int dg_dgrad(const char* who, bool x3, const float* dy, const float* w, const float* y_relu, const float* x_relu, float* dx,
+                    int rows, int cin, int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
   ODET_REQUIRE(dy && w && dx, "%s: null pointer", who);
   const int rs = dg_check_shape(who, rows, cin, cout);
   if (rs != ODET_OK) return rs;
   ODET_REQUIRE(((uintptr_t)dy | (uintptr_t)w | (uintptr_t)y_relu | (uintptr_t)x_relu | (uintptr_t)dx) % 16 == 0,
                "%s: pointers must be 16-byte aligned", who);
-  return dg_launch<false>(who, w, dy, y_relu, x_relu, dx, cin, rows, cout, workspace, workspace_bytes, (hipStream_t)stream);
+  return dg_launch<false>(who, x3, w, dy, y_relu, x_relu, dx, cin, rows, cout, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-extern "C" int odet_dense_wgrad_f32(const float* dy, const float* x, const float* y_relu, float* dw, float* db, int rows, int cin,
-                                    int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
-  const char* who = "odet_dense_wgrad_f32";
+// (db is not part of the split-precision form: the same ordered float32 sums, the same bits, in either)
+static int dg_wgrad(const char* who, bool x3, const float* dy, const float* x, const float* y_relu, float* dw, float* db, int rows,
+                    int cin, int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
   ODET_REQUIRE(dy && x && dw, "%s: null pointer", who);
   const int rs = dg_check_shape(who, rows, cin, cout);
   if (rs != ODET_OK) return rs;
   ODET_REQUIRE(((uintptr_t)dy | (uintptr_t)x | (uintptr_t)y_relu | (uintptr_t)dw) % 16 == 0 && (uintptr_t)db % 4 == 0,
                "%s: pointers must be 16-byte aligned (db: 4)", who);
-  const int rl = dg_launch<true>(who, x, dy, y_relu, nullptr, dw, cin, cout, rows, workspace, workspace_bytes, (hipStream_t)stream);
+  const int rl = dg_launch<true>(who, x3, x, dy, y_relu, nullptr, dw, cin, cout, rows, workspace, workspace_bytes, (hipStream_t)stream);
   if (rl != ODET_OK) return rl;
   if (db) {
     DgBiasRows q = {};
@@ -316,4 +366,24 @@ extern "C" int odet_dense_wgrad_f32(const float* dy, const float* x, const float
     return dg_bias_grad(q, db, cout, (hipStream_t)stream);
   }
   return ODET_OK;
+}
+
+extern "C" int odet_dense_dgrad_f32(const float* dy, const float* w, const float* y_relu, const float* x_relu, float* dx, int rows,
+                                    int cin, int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
+  return dg_dgrad("odet_dense_dgrad_f32", false, dy, w, y_relu, x_relu, dx, rows, cin, cout, workspace, workspace_bytes, stream);
+}
+
+extern "C" int odet_dense_dgrad_x3(const float* dy, const float* w, const float* y_relu, const float* x_relu, float* dx, int rows,
+                                   int cin, int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
+  return dg_dgrad("odet_dense_dgrad_x3", true, dy, w, y_relu, x_relu, dx, rows, cin, cout, workspace, workspace_bytes, stream);
+}
+
+extern "C" int odet_dense_wgrad_f32(const float* dy, const float* x, const float* y_relu, float* dw, float* db, int rows, int cin,
+                                    int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
+  return dg_wgrad("odet_dense_wgrad_f32", false, dy, x, y_relu, dw, db, rows, cin, cout, workspace, workspace_bytes, stream);
+}
+
+extern "C" int odet_dense_wgrad_x3(const float* dy, const float* x, const float* y_relu, float* dw, float* db, int rows, int cin,
+                                   int cout, void* workspace, size_t workspace_bytes, odet_stream_t stream) {
+  return dg_wgrad("odet_dense_wgrad_x3", true, dy, x, y_relu, dw, db, rows, cin, cout, workspace, workspace_bytes, stream);
 }

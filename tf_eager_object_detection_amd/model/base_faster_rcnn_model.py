@@ -185,7 +185,8 @@ class ResNetFasterRcnn(_FrcnnFromDense):
         kw = self._common_keywords('ResNetFasterRcnn', kwargs)
         self._depth = depth
         self._roi_feature_size = roi_feature_size
-        self._init_with_dense(ResNetC4Detector(depth, kw['num_classes'], (64, 64), 1, dtype=dtype, f32_form=f32_form), dtype, device,
+        self._init_with_dense(ResNetC4Detector(depth, kw['num_classes'], (64, 64), 1, dtype=dtype, f32_form=f32_form,
+                                               grad_form=self.grad_form), dtype, device,
                               BaseFasterRcnn.__init__, kw)
 
 
@@ -202,7 +203,8 @@ class TrainableResNetFasterRcnn(ResNetFasterRcnn):
     _accepts_train_keywords = True
 
     def __init__(self, depth=50, roi_feature_size=(7, 7, 1024), dtype=torch.float32, device='cuda', f32_form='exact',
-                 train_roi_head=False, train_rpn_head=False, train_extractor=False, **kwargs):
+                 train_roi_head=False, train_rpn_head=False, train_extractor=False, grad_form='exact', **kwargs):
+        self.grad_form = ops.check_grad_form(grad_form)
         super().__init__(depth, roi_feature_size, dtype, device, f32_form, train_roi_head=train_roi_head,
                          train_rpn_head=train_rpn_head, train_extractor=train_extractor, **kwargs)
 
@@ -229,8 +231,9 @@ class Vgg16FasterRcnn(_FrcnnFromDense):
 
     def __init__(self, slim_ckpt_file_path=None, roi_head_keep_dropout_rate=0.5, roi_feature_size=(7, 7, 512),
                  dtype=torch.float32, device='cuda', f32_form='exact', train_roi_head=False, train_rpn_head=False,
-                 train_extractor=False, dropout_seed=0, **kwargs):
+                 train_extractor=False, dropout_seed=0, grad_form='exact', **kwargs):
         from .frcnn_detector import Vgg16Detector
+        self.grad_form = ops.check_grad_form(grad_form)
         check_caller_f32_form(f32_form)
         check_train_flags('Vgg16FasterRcnn', dtype, f32_form,
                           (train_extractor, 'train_extractor', 'the convolution and pooling backward have'),
@@ -247,7 +250,8 @@ class Vgg16FasterRcnn(_FrcnnFromDense):
         self._roi_head_keep_dropout_rate = roi_head_keep_dropout_rate
         self._dropout_seed = int(dropout_seed)
         self._roi_feature_size = roi_feature_size
-        self._init_with_dense(Vgg16Detector(kw['num_classes'], (64, 64), 1, dtype=dtype, f32_form=f32_form), dtype, device,
+        self._init_with_dense(Vgg16Detector(kw['num_classes'], (64, 64), 1, dtype=dtype, f32_form=f32_form,
+                                            grad_form=grad_form), dtype, device,
                               BaseFasterRcnn.__init__, kw)
 
     def _get_trainable_roi_head(self):

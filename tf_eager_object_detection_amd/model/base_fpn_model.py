@@ -72,8 +72,10 @@ class BaseFPN(CallerModel):
                  roi_training_total_num_samples=128, roi_training_max_pos_samples=32,
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0., training_targets='torch',
-                 training_losses='torch', train_roi_head=False, train_rpn_head=False, train_neck=False, train_extractor=False):
+                 training_losses='torch', train_roi_head=False, train_rpn_head=False, train_neck=False, train_extractor=False,
+                 grad_form='exact'):
         super().__init__()
+        self.grad_form = ops.check_grad_form(grad_form)
         self._training_losses = check_training_losses(training_losses, training_targets)
         check_train_dependencies(train_extractor, train_neck, train_rpn_head, train_roi_head, has_neck=True)
         # True: the training branches run that part with a backward pass (caller_base.CallerModel)
@@ -207,8 +209,9 @@ class ResnetV1Fpn(DenseParts, BaseFPN):
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3, dtype=torch.float32, device='cuda',
                  f32_form='exact', training_targets='torch', training_losses='torch', train_roi_head=False, train_rpn_head=False,
-                 train_neck=False, train_extractor=False):
+                 train_neck=False, train_extractor=False, grad_form='exact'):
         from .fpn_detector import ResNetFpnDetector
+        ops.check_grad_form(grad_form)
         check_caller_f32_form(f32_form)
         exact = lambda *flags: check_train_flags('ResnetV1Fpn', dtype, f32_form, *flags)
         exact((train_extractor, 'train_extractor', 'the bottleneck backward has'),
@@ -224,7 +227,8 @@ class ResnetV1Fpn(DenseParts, BaseFPN):
         self._depth = depth
         self._roi_head_keep_dropout_rate = roi_head_keep_dropout_rate
         self._top_down_dims = top_down_dims
-        self._init_with_dense(ResNetFpnDetector(depth, num_classes, (64, 64), 1, dtype=dtype, f32_form=f32_form), dtype, device,
+        self._init_with_dense(ResNetFpnDetector(depth, num_classes, (64, 64), 1, dtype=dtype, f32_form=f32_form,
+                                                grad_form=grad_form), dtype, device,
                               BaseFPN.__init__, dict(
             roi_feature_size=roi_feature_size, num_classes=num_classes, weight_decay=weight_decay,
             level_name_list=level_name_list, min_level=min_level, max_level=max_level, anchor_stride_list=anchor_stride_list,
@@ -248,7 +252,7 @@ class ResnetV1Fpn(DenseParts, BaseFPN):
             prediction_max_objects_per_class=prediction_max_objects_per_class,
             prediction_nms_iou_threshold=prediction_nms_iou_threshold, prediction_score_threshold=prediction_score_threshold,
             training_targets=training_targets, training_losses=training_losses, train_roi_head=train_roi_head,
-            train_rpn_head=train_rpn_head, train_neck=train_neck, train_extractor=train_extractor))
+            train_rpn_head=train_rpn_head, train_neck=train_neck, train_extractor=train_extractor, grad_form=grad_form))
 
     def _get_extractor(self):
         return _Part(self._dense_ref.extractor)

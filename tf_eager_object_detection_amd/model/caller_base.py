@@ -121,6 +121,7 @@ class CallerModel(torch.nn.Module):
     _train_neck = False        # the neck: P2..P6 require a gradient (needs a trainable head)
     _train_rpn_head = False    # the RpnHead: the two RPN losses carry a graph into its layers
     _train_roi_head = False    # the RoI head: the two RoI losses carry a graph into its layers
+    grad_form = 'exact'        # the arithmetic of the trainable parts' gradient GEMMs: 'exact' | 'x3' (ops.grad_form)
     _rpn_layout = None
     _rpn_head_type = None
 
@@ -189,6 +190,11 @@ class CallerModel(torch.nn.Module):
     # ---- base_fpn_model.py:202-276, base_faster_rcnn_model.py:126-198 ----------------------------------------------------------
     @caller_range_checked
     def forward(self, inputs, training=None, mask=None):
+        # (the trainable parts record the form on their graph nodes: `.backward()` may run anywhere, ops.keep_grad_form)
+        with ops.grad_form(self.grad_form):
+            return self._forward(inputs, training)
+
+    def _forward(self, inputs, training):
         if training:
             image, gt_bboxes, gt_labels = inputs
         else:

@@ -52,11 +52,11 @@ def caller_range_checked(method):
 
 
 def _in_f32_form(method):
-    """runs a detector's dense method with the float32 layers in the detector's `f32_form` ('exact' | 'x3' | 'x2': ops.f32_form)"""
+    """runs a detector's dense method in the detector's `f32_form` (ops.f32_form) and, for the backward of a trainable part, `grad_form`"""
     @functools.wraps(method)
     def run(self, *args, **kw):
-        form = getattr(self, 'f32_form', 'exact')
-        with ops.f32_form(form, workspace=_x3_workspace_of(self) if form != 'exact' else None):
+        form, grad = getattr(self, 'f32_form', 'exact'), getattr(self, 'grad_form', 'exact')
+        with ops.f32_form(form, workspace=_x3_workspace_of(self) if form != 'exact' else None), ops.grad_form(grad):
             return method(self, *args, **kw)
     return run
 
@@ -120,6 +120,7 @@ class _FinalLayer:
         return y[:, :n1], y[:, n1:n5]
 
 
+@ops.carries_grad_form
 class _FinalTrainable(torch.autograd.Function):
     """the padded final layer: ops.dense on the derived (padded, concatenated) weights forward; one ops.dense_wgrad on them
     backward, handed out as row slices in the order (score.weight, score.bias, bbox.weight, bbox.bias)"""

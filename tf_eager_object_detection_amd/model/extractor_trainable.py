@@ -20,6 +20,7 @@ def block_layers(blk):
     return (blk.c1, blk.c2, blk.c3) + ((blk.short,) if blk.short is not None else ())
 
 
+@ops.carries_grad_form
 class _BlockTrainable(torch.autograd.Function):
     """One bottleneck with a backward pass.  Forward: _Block.forward's float32 launches (pointwise, conv3x3_f32, then pointwise with
     the residual or pointwise_dual); saves the block's input x (a strided block: xs = stride_gather(x, s) in its place, the only form

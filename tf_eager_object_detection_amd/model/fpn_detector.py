@@ -310,10 +310,10 @@ class ResNetFpnDetector(Detector):
     _step_batch_class, _hot_path_class, _kept_rois = FpnStepBatch, FpnHotPath, 'sorted_rois'
 
     def __init__(self, depth=101, num_classes=21, image_shape=(800, 1333), num_proposals=1000, dtype=torch.float32,
-                 max_batch=1, f32_form='exact', **hot_kwargs):
+                 max_batch=1, f32_form='exact', grad_form='exact', **hot_kwargs):
         super().__init__()
         b = _BLOCKS[depth]
-        self.dtype = dtype
+        self.dtype, self.grad_form = dtype, ops.check_grad_form(grad_form)     # grad_form: 'exact' | 'x3' (ops.grad_form)
         # float32 mode only: 'exact' = exact-float32 matrix instructions (the parity mode), 'x3' = split precision (three
         # bfloat16 limbs per operand, six products per k, float32 accumulation: float32-class accuracy at 2.6 x the peak rate)
         self.f32_form = f32_form

@@ -33,10 +33,10 @@ class ResNetC4Detector(C4TrainableParts, Detector):
     _step_batch_class, _hot_path_class = FrcnnStepBatch, FrcnnHotPath
 
     def __init__(self, depth=50, num_classes=21, image_shape=(800, 1333), num_proposals=300, dtype=torch.float32,
-                 max_batch=1, roi_chunk=0, f32_form='exact', **hot_kwargs):
+                 max_batch=1, roi_chunk=0, f32_form='exact', grad_form='exact', **hot_kwargs):
         super().__init__()
         b = _BLOCKS[depth]
-        self.dtype = dtype
+        self.dtype, self.grad_form = dtype, ops.check_grad_form(grad_form)     # grad_form: 'exact' | 'x3' (ops.grad_form)
         self.f32_form = f32_form             # float32 mode: 'exact' | 'x3' | 'x2' (model/detector_base.py)
         self.image_shape = (int(image_shape[0]), int(image_shape[1]))
         self.num_classes = num_classes
@@ -172,9 +172,9 @@ class Vgg16Detector(ResNetC4Detector):
     _CFG = ((64, 2), (128, 2), (256, 3), (512, 3), (512, 3))
 
     def __init__(self, num_classes=21, image_shape=(600, 800), num_proposals=300, dtype=torch.float32, max_batch=1,
-                 f32_form='exact', **hot_kwargs):
+                 f32_form='exact', grad_form='exact', **hot_kwargs):
         nn.Module.__init__(self)
-        self.dtype = dtype
+        self.dtype, self.grad_form = dtype, ops.check_grad_form(grad_form)
         self.f32_form = f32_form
         self.image_shape = (int(image_shape[0]), int(image_shape[1]))
         self.num_classes = num_classes

@@ -12,6 +12,7 @@ from .trainable_common import flipped_weight, in_param_layout, param_layouts, po
 _LAYERS = ('p5', 'l4', 'l3', 'l2', 's4', 's3', 's2')
 
 
+@ops.carries_grad_form
 class _NeckTrainable(torch.autograd.Function):
     """The float32 neck with a backward pass.  Forward: neck()'s launches; saves C2..C5 and the merged maps m2..m4 (the inputs of
     s2..s4, which the forward has in memory anyway).  Backward, with dP2..dP6 arriving (any of them may be absent and drops its

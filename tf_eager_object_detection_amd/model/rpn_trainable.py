@@ -9,6 +9,7 @@ from .fpn_detector import _nhwc, _no_kernel, _own_conv3x3, rpn_pair_padded, rpn_
 from .trainable_common import flipped_weight, in_param_layout, param_layouts, require_exact_f32
 
 
+@ops.carries_grad_form
 class _RpnHeadTrainable(torch.autograd.Function):
     """The float32 RpnHead over all levels with a backward pass.  Forward: rpn()'s launches, with the levels' 512-channel
     activations h in ONE [sum rows, 512] buffer (the 3x3 convolution writes the levels' views), so that the pair of 1x1

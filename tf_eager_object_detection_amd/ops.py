@@ -37,6 +37,7 @@ MAX_LEVELS = 8
 # context, held in a contextvars.ContextVar: two Python threads (or asyncio tasks) that enter and leave `f32_form` blocks in any
 # interleaving each see their own value -- a form switch is never implicit and can never leak into another thread's layers.
 import contextvars
+import functools
 
 _F32_CTX = contextvars.ContextVar('odet_f32_form', default=('exact', None))
 
@@ -64,6 +65,62 @@ class f32_form:
     def __exit__(self, *exc):
         _F32_CTX.reset(self._token)
         return False
+
+
+# ---- the gradient GEMMs' arithmetic form -------------------------------------------------------------------------------------
+# A second ambient form, beside f32_form (which the forward layers read and under which every backward front keeps refusing
+# anything but 'exact'): 'exact' runs the Dense / 3x3 gradients on v_mfma_f32_16x16x4_f32, 'x3' on three bfloat16 limbs and six
+# limb products per k (csrc/grad_gemm.h: dg_tile_x3; the 3x3 input gradient: the forward's x3 kernel on the flipped weight).
+# The bias gradients are the same ordered float32 sums in either.  A two-limb form is not offered.
+# autograd runs `backward` on a thread of its own, where a ContextVar shows its default: a torch.autograd.Function whose backward
+# reaches these ops records the form in `forward` and re-enters it in `backward` (carries_grad_form).
+_GRAD_CTX = contextvars.ContextVar('odet_grad_form', default='exact')
+GRAD_FORMS = ('exact', 'x3')
+
+
+def current_grad_form():
+    return _GRAD_CTX.get()
+
+
+def check_grad_form(form):
+    if form not in GRAD_FORMS:
+        raise ValueError("grad form must be 'exact' or 'x3', got %r" % (form,))
+    return form
+
+
+class grad_form:
+    """with ops.grad_form('x3'): ...  -- the form dense_dgrad / dense_wgrad / conv3x3_wgrad_f32_levels /
+    conv3x3_dgrad_f32_levels calls inside the block, and the backward passes of the *_trainable functions called inside it, run on."""
+
+    def __init__(self, form):
+        self.form = check_grad_form(form)
+
+    def __enter__(self):
+        self._token = _GRAD_CTX.set(self.form)
+        return self
+
+    def __exit__(self, *exc):
+        _GRAD_CTX.reset(self._token)
+        return False
+
+
+def carries_grad_form(cls):
+    """class decorator of a torch.autograd.Function whose backward reaches the gradient ops -- the ONE place that carries the
+    form across threads: forward records the caller's grad form on the node, the whole of backward runs inside it (a node that
+    no forward made has recorded none: the default, 'exact')"""
+    forward, backward = cls.forward, cls.backward
+
+    @functools.wraps(forward)
+    def record(ctx, *args):
+        ctx.grad_form = current_grad_form()
+        return forward(ctx, *args)
+
+    @functools.wraps(backward)
+    def reenter(ctx, *grads):
+        with grad_form(getattr(ctx, 'grad_form', 'exact')):
+            return backward(ctx, *grads)
+    cls.forward, cls.backward = staticmethod(record), staticmethod(reenter)
+    return cls
 
 
 def split_bf16x3(w):
@@ -525,7 +582,7 @@ def _grad_f32(who, what, named):
             raise ValueError('%s: %s must be a float32 tensor (the %s has no float16 form), got %s'
                              % (who, name, what, getattr(t, 'dtype', type(t).__name__)))
     if current_f32_form() != 'exact':
-        raise ValueError("%s: the %s runs only under f32_form 'exact' (no split-precision backward), not %r"
+        raise ValueError("%s: the %s runs only under f32_form 'exact' (its split-precision form is ops.grad_form('x3')), not %r"
                          % (who, what, current_f32_form()))
 
 
@@ -544,6 +601,11 @@ def _grad_on_gpu(who, named):
     for name, t in named:
         if not t.is_cuda:
             raise ValueError('%s: %s must be a GPU tensor' % (who, name))
+
+
+def _grad_symbols(exact, x3):
+    """the (entry point, workspace query) pair of the current grad form"""
+    return x3 if current_grad_form() == 'x3' else exact
 
 
 def _grad_workspace(query_symbol, query_args, device):
@@ -1208,8 +1270,10 @@ def dense_dgrad(dy, weight, y_relu=None, x_relu=None, out=None):
                                or tuple(x_relu.shape) != (rows, cin) or not x_relu.is_contiguous()):
         raise ValueError('dense_dgrad: x_relu must be a contiguous float32 GPU tensor of shape %s' % ((rows, cin),))
     out = _out(out, (rows, cin), torch.float32, dy.device)
-    wsp, wsn = _grad_workspace('odet_dense_grad_workspace_bytes', (0, rows, cin, cout), dy.device)
-    L.call('odet_dense_dgrad_f32', L.dptr(dy), L.dptr(weight), L.dptr(y_relu), L.dptr(x_relu), L.dptr(out), rows, cin, cout,
+    entry, query = _grad_symbols(('odet_dense_dgrad_f32', 'odet_dense_grad_workspace_bytes'),
+                                 ('odet_dense_dgrad_x3', 'odet_dense_grad_x3_workspace_bytes'))
+    wsp, wsn = _grad_workspace(query, (0, rows, cin, cout), dy.device)
+    L.call(entry, L.dptr(dy), L.dptr(weight), L.dptr(y_relu), L.dptr(x_relu), L.dptr(out), rows, cin, cout,
            wsp, wsn, L.stream())
     return out
 
@@ -1220,12 +1284,15 @@ def dense_wgrad(dy, x, y_relu=None, with_bias=True, out=None):
     rows, cin, cout = _dense_grad_args('dense_wgrad', dy, x, 'x', lambda r, c: r, y_relu)
     dw = _out(out, (cout, cin), torch.float32, dy.device)
     db = torch.empty((cout,), dtype=torch.float32, device=dy.device) if with_bias else None
-    wsp, wsn = _grad_workspace('odet_dense_grad_workspace_bytes', (1, rows, cin, cout), dy.device)
-    L.call('odet_dense_wgrad_f32', L.dptr(dy), L.dptr(x), L.dptr(y_relu), L.dptr(dw), L.dptr(db), rows, cin, cout, wsp, wsn,
+    entry, query = _grad_symbols(('odet_dense_wgrad_f32', 'odet_dense_grad_workspace_bytes'),
+                                 ('odet_dense_wgrad_x3', 'odet_dense_grad_x3_workspace_bytes'))
+    wsp, wsn = _grad_workspace(query, (1, rows, cin, cout), dy.device)
+    L.call(entry, L.dptr(dy), L.dptr(x), L.dptr(y_relu), L.dptr(dw), L.dptr(db), rows, cin, cout, wsp, wsn,
            L.stream())
     return dw, db
 
 
+@carries_grad_form
 class _DenseTrainable(torch.autograd.Function):
     """ops.dense forward; odet_dense_wgrad_f32 (and, only when the input needs a gradient, odet_dense_dgrad_f32) backward"""
 
@@ -1305,8 +1372,10 @@ def conv3x3_wgrad_f32_levels(xs, dys, y_relus=None, with_bias=True, out=None):
     dev = xs[0].device
     dw = _out(out, (cout, 3, 3, cin), torch.float32, dev)
     db = torch.empty((cout,), dtype=torch.float32, device=dev) if with_bias else None
-    wsp, wsn = _grad_workspace('odet_conv3x3_wgrad_workspace_bytes', (lv, n, B, cin, cout), dev)
-    L.call('odet_conv3x3_wgrad_f32_levels', lv, n, L.dptr(dw), L.dptr(db), B, cin, cout, wsp, wsn, L.stream())
+    entry, query = _grad_symbols(('odet_conv3x3_wgrad_f32_levels', 'odet_conv3x3_wgrad_workspace_bytes'),
+                                 ('odet_conv3x3_wgrad_x3_levels', 'odet_conv3x3_wgrad_x3_workspace_bytes'))
+    wsp, wsn = _grad_workspace(query, (lv, n, B, cin, cout), dev)
+    L.call(entry, lv, n, L.dptr(dw), L.dptr(db), B, cin, cout, wsp, wsn, L.stream())
     return dw, db
 
 
@@ -1338,9 +1407,13 @@ def conv3x3_dgrad_f32_levels(dzs, weight, outs=None, flipped=None):
     wf = conv3x3_flipped_weight(weight) if flipped is None else flipped
     if tuple(wf.shape) != (cin, 3, 3, cout) or not wf.is_contiguous():
         raise ValueError('%s: flipped must be a contiguous [cin,3,3,cout] tensor' % who)
+    if current_grad_form() == 'x3':                     # (the flipped tensor's limb planes: derived.py's, keyed on it)
+        with f32_form('x3'):
+            return _conv3x3_levels(torch.float32, list(dzs), wf, None, False, outs)
     return _conv3x3_levels(torch.float32, list(dzs), wf, None, False, outs)
 
 
+@carries_grad_form
 class _Conv3x3Trainable(torch.autograd.Function):
     """ops.conv3x3_f32_levels forward; one odet_conv3x3_wgrad_f32_levels over all levels (and, only when an input needs a gradient,
     the forward kernel on the flipped weight) backward"""
@@ -1406,6 +1479,7 @@ def conv3x3_trainable_levels(xs, weight, bias, relu=False, flipped=None):
     return ys
 
 
+@carries_grad_form
 class _Conv3x3ReluPoolTrainable(torch.autograd.Function):
     """conv3x3_f32 without its epilogue, then bias_relu_maxpool (2x2 / 2, ceil mode) forward; relu_maxpool2_backward, then one
     odet_conv3x3_wgrad_f32_levels on the gated gradient (and, only when the input needs a gradient, the forward kernel on the
