@@ -46,7 +46,8 @@ extern "C" {
  * two elementwise launches of the ResNet bottleneck's backward (odet_stride_gather_f32, odet_block_input_grad_f32) and the VGG16
  * training graph's max-pooling and dropout backward (odet_relu_maxpool2_backward_f32, odet_dropout_f32, odet_dropout_backward_f32) and
  * the ResNet-C4 head's global average pooling (odet_global_avg_pool_f32, odet_global_avg_pool_backward_f32) and the
- * data-parallel gradient exchange (odet_bucket_pack_f32, odet_bucket_unpack_f32, odet_rank_mean_f32); no
+ * data-parallel gradient exchange (odet_bucket_pack_f32, odet_bucket_unpack_f32, odet_rank_mean_f32) and the FPN stem's
+ * max-pooling backward (odet_relu_maxpool3_backward_f32); no
  * existing struct or signature changed.  One documented order did: from
  * 4096 rows on, odet_dense_wgrad_f32 adds db in 256 running sums per column, not 4 (its own comment; below 4096 rows every bit is
  * as before). */
@@ -669,6 +670,33 @@ int odet_dropout_f32(const float* x, float* y, long long n, float keep_prob, uin
                      odet_stream_t stream);
 int odet_dropout_backward_f32(const float* dy, float* dx, long long n, float keep_prob, uint64_t seed, uint32_t image_id,
                               uint32_t stream_id, odet_stream_t stream);
+
+/* ---- FPN stem training graph: the overlapping max-pooling's backward (added within 103) --------------------------------------- */
+
+/* The backward of odet_bias_relu_maxpool's float32 3x3 / stride-2 / pad-1 floor-mode form -- conv1_relu, pool1_pad
+ * (ZeroPadding2D(1)) and pool1_pool (MaxPooling2D(3, strides=2)) behind the trainable conv1_conv of the FPN extractor,
+ * model/fpn/resnet_fpn.py:233-242 -- as TF computes it: MaxPoolGrad through the padding, then ReluGrad.  z [B,H,W,C] NHWC float32
+ * is the convolution's raw output WITHOUT its bias (what the forward reads), bias [C], dpool [B,OH,OW,C] with OH = (H-1)/2 + 1,
+ * OW = (W-1)/2 + 1, dz [B,H,W,C]:
+ *   v = z + bias                                  one float32 add, the sum the forward forms; a = max(v, 0)
+ *   window (p,q)                                  rows 2p-1 .. 2p+1, columns 2q-1 .. 2q+1, clipped to the map
+ *   winner(p,q,c)                                 the FIRST tap of the window, in row-major order, that holds its maximum when
+ *                                                 that maximum is > 0: scanning from +0 with a strict '>', so a window whose
+ *                                                 maximum is 0 has no winner and a NaN tap never wins
+ *   dz[b,i,j,c] = sum of dpool[b,p,q,c]           over the windows (p,q) whose winner is (i,j), in ascending (p,q) row-major
+ *                                                 order, every add rounded to float32, started from the first term itself
+ *                 +0                              where there is none
+ * The padding taps are skipped.  In the reference a padding tap holds 0 and can win only a window whose maximum is 0; ReluGrad
+ * zeroes that case (a = 0 at every real tap of such a window, and the padding has no gradient to keep), so skipping the taps and
+ * passing the 0 through are the same function.  An odd row or column belongs to two window rows or columns: a pixel is in up to
+ * four windows, and the order of its at most four terms is part of the contract (tests/stem_grad_np.py states it as a serial
+ * loop; the result is that statement's, bit for bit).  No atomics, no arg-max tensor, no workspace, no host read
+ * (graph-capturable); every element of dz is written exactly once.  Algorithmic bytes: 4 * (2 H W + OH OW) * C * B.
+ * B == 0 is a no-op.
+ * Errors, all before any HIP call: ODET_E_INVALID (a null pointer; H or W <= 0; B < 0; C no positive multiple of 4; a pointer not
+ * 16-byte aligned; more than 2^31 - 1 workgroups of 6 window rows x (256 / min(C/4, 64) - 1) window columns x 256 channels). */
+int odet_relu_maxpool3_backward_f32(const float* z, const float* bias, const float* dpool, float* dz, int B, int H, int W, int C,
+                                    odet_stream_t stream);
 
 /* ---- ResNet-C4 training graph: global average pooling, forward and backward (added within 103) ------------------------------ */
 

@@ -13,7 +13,7 @@ OBJ_DIR = os.path.join(CSRC, '_obj')
 LIB = os.path.join(PKG, 'libodet_hip.so')
 SOURCES = ['boxes.hip', 'sort.hip', 'nms.hip', 'roi.hip', 'roi_half.hip', 'postops.hip', 'neck.hip', 'epilogue.hip', 'conv1x1.hip', 'conv3x3.hip', 'conv_f32.hip', 'conv_x3.hip', 'rpn_tail.hip',
            'calib.hip', 'stem.hip', 'executor.hip', 'preprocess.hip', 'coco_eval.hip', 'voc_eval.hip', 'targets.hip', 'losses.hip', 'optimizer.hip', 'dense_grad.hip', 'conv_grad.hip', 'roi_grad.hip', 'block_grad.hip', 'vgg_grad.hip',
-           'c4_grad.hip', 'grad_exchange.hip']
+           'c4_grad.hip', 'grad_exchange.hip', 'stem_grad.hip']
 HEADERS = [os.path.join(CSRC, 'odet_internal.h'), os.path.join(CSRC, 'conv_f32_common.h'), os.path.join(CSRC, 'conv_diag.h'), os.path.join(CSRC, 'roi_taps.h'),
            os.path.join(CSRC, 'grad_gemm.h'), os.path.join(CSRC, 'grad_elementwise.h'), os.path.join(CSRC, 'x3_split.h'),
            os.path.join(INCLUDE, 'odet.h')]

@@ -167,6 +167,7 @@ SIGNATURES = {
     'odet_stride_gather_f32': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     'odet_block_input_grad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'odet_relu_maxpool2_backward_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'odet_relu_maxpool3_backward_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'odet_dropout_f32': (_i, [_vp, _vp, C.c_longlong, _f, C.c_uint64, C.c_uint32, C.c_uint32, _vp]),
     'odet_dropout_backward_f32': (_i, [_vp, _vp, C.c_longlong, _f, C.c_uint64, C.c_uint32, C.c_uint32, _vp]),
     'odet_global_avg_pool_f32': (_i, [_vp, _i, _i, _i, _vp, _vp]),

@@ -22,7 +22,9 @@ RpnHead returns its input gradient, the two heads' gradients meet in P2..P5 and 
 convolutions -- every parameter downstream of the extractor.  With `train_extractor=True` as well (which needs `train_neck`) the
 extractor runs fpn_detector's extractor_trainable outside no_grad: C2..C5 require a gradient, neck_trainable delivers dC2..dC5 and the
 losses carry a graph into every convolution of conv2..conv5 (reference resnet_fpn.py:208-225: trainable, batch-norm frozen); the stem
-(conv1 and its pooling) stays under no_grad -- it has no backward."""
+(conv1 and its pooling) stays under no_grad unless `train_stem=True` as well (which needs `train_extractor`): then it runs
+ops.stem_trainable and conv1's weight and bias receive a gradient too, as in the reference (resnet_fpn.py:233: trainable=True) --
+with all five keywords every parameter of the detector does (134 at depth 50, 236 at depth 101)."""
 import torch
 
 from .. import ops
@@ -73,13 +75,13 @@ class BaseFPN(CallerModel):
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0., training_targets='torch',
                  training_losses='torch', train_roi_head=False, train_rpn_head=False, train_neck=False, train_extractor=False,
-                 grad_form='exact'):
+                 grad_form='exact', train_stem=False):
         super().__init__()
         self.grad_form = ops.check_grad_form(grad_form)
         self._training_losses = check_training_losses(training_losses, training_targets)
-        check_train_dependencies(train_extractor, train_neck, train_rpn_head, train_roi_head, has_neck=True)
+        check_train_dependencies(train_extractor, train_neck, train_rpn_head, train_roi_head, has_neck=True, train_stem=train_stem)
         # True: the training branches run that part with a backward pass (caller_base.CallerModel)
-        self._train_extractor, self._train_neck = bool(train_extractor), bool(train_neck)
+        self._train_extractor, self._train_neck, self._train_stem = bool(train_extractor), bool(train_neck), bool(train_stem)
         self._train_roi_head, self._train_rpn_head = bool(train_roi_head), bool(train_rpn_head)
         self.roi_feature_size = roi_feature_size
         self.num_classes = num_classes
@@ -135,7 +137,7 @@ class BaseFPN(CallerModel):
 
     # ---- :208-220: the dense parts of the front (CallerModel._anchors_and_proposals) ------------
     def _dense_front(self, image, image_shape, training, train):
-        # extractor: conv2..conv5 OUTSIDE no_grad with train_extractor (the stem stays inside: it has no backward): C2..C5 require
+        # extractor: conv2..conv5 OUTSIDE no_grad with train_extractor (the stem stays inside without train_stem): C2..C5 require
         # a gradient, which the trainable neck delivers.  neck: P2..P6 require a gradient with train_neck, which the RpnHead's
         # input gradient and the trainable RoI pooling deliver.  RpnHead: the head of all levels at once with train_rpn_head, so
         # that the RPN losses see these tensors and carry their graph
@@ -209,14 +211,15 @@ class ResnetV1Fpn(DenseParts, BaseFPN):
                  prediction_max_objects_per_image=50, prediction_max_objects_per_class=50,
                  prediction_nms_iou_threshold=0.3, prediction_score_threshold=0.3, dtype=torch.float32, device='cuda',
                  f32_form='exact', training_targets='torch', training_losses='torch', train_roi_head=False, train_rpn_head=False,
-                 train_neck=False, train_extractor=False, grad_form='exact'):
+                 train_neck=False, train_extractor=False, grad_form='exact', train_stem=False):
         from .fpn_detector import ResNetFpnDetector
         ops.check_grad_form(grad_form)
         check_caller_f32_form(f32_form)
         exact = lambda *flags: check_train_flags('ResnetV1Fpn', dtype, f32_form, *flags)
-        exact((train_extractor, 'train_extractor', 'the bottleneck backward has'),
+        exact((train_stem, 'train_stem', "the stem's backward has"),
+              (train_extractor, 'train_extractor', 'the bottleneck backward has'),
               (train_neck, 'train_neck', "the neck's backward has"))
-        check_train_dependencies(train_extractor, train_neck, train_rpn_head, train_roi_head, has_neck=True)
+        check_train_dependencies(train_extractor, train_neck, train_rpn_head, train_roi_head, has_neck=True, train_stem=train_stem)
         exact((train_roi_head, 'train_roi_head', 'the Dense backward has'),
               (train_rpn_head, 'train_rpn_head', 'the convolution backward has'))
         if top_down_dims != 256 or tuple(roi_feature_size) != (roi_pool_size, roi_pool_size, top_down_dims):
@@ -252,13 +255,17 @@ class ResnetV1Fpn(DenseParts, BaseFPN):
             prediction_max_objects_per_class=prediction_max_objects_per_class,
             prediction_nms_iou_threshold=prediction_nms_iou_threshold, prediction_score_threshold=prediction_score_threshold,
             training_targets=training_targets, training_losses=training_losses, train_roi_head=train_roi_head,
-            train_rpn_head=train_rpn_head, train_neck=train_neck, train_extractor=train_extractor, grad_form=grad_form))
+            train_rpn_head=train_rpn_head, train_neck=train_neck, train_extractor=train_extractor, grad_form=grad_form,
+            train_stem=train_stem))
 
     def _get_extractor(self):
         return _Part(self._dense_ref.extractor)
 
     def _get_neck(self):
         return _Part(self._dense_ref.neck)
+
+    def _get_trainable_extractor_results(self, image):
+        return self._dense_ref.extractor_trainable(image, train_stem=self._train_stem)
 
     def _get_trainable_neck_results(self, c_list):
         return self._dense_ref.neck_trainable(list(c_list))

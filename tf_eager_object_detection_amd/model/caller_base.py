@@ -30,11 +30,13 @@ def check_training_losses(training_losses, training_targets):
     return training_losses
 
 
-def check_train_dependencies(train_extractor, train_neck, train_rpn_head, train_roi_head, has_neck):
+def check_train_dependencies(train_extractor, train_neck, train_rpn_head, train_roi_head, has_neck, train_stem=False):
     """a part trains only when a gradient reaches it.  With a neck (FPN): C2..C5 receive one only through neck_trainable, and the
     neck's outputs only through the RpnHead's input gradient or the trainable RoI pooling.  Without one (single level): the
-    shared map receives one only through those two."""
+    shared map receives one only through those two.  The stem (FPN only) receives one only through conv2's first block."""
     head = train_rpn_head or train_roi_head
+    if train_stem and not train_extractor:
+        raise ValueError('train_stem=True needs train_extractor=True: no gradient reaches the stem otherwise')
     if train_extractor and has_neck and not train_neck:
         raise ValueError('train_extractor=True needs train_neck=True: no gradient reaches the extractor otherwise')
     if train_neck and not head:
@@ -118,6 +120,7 @@ class CallerModel(torch.nn.Module):
     # What the training branches run with a backward pass.  BaseFPN sets these from its keywords; BaseFasterRcnn keeps the
     # reference's arguments, so its concrete models set them on the instance before they call its constructor.
     _train_extractor = False   # the extractor: its outputs require a gradient (FPN: needs the trainable neck; else a trainable head)
+    _train_stem = False        # the FPN stem: conv1 receives a gradient too (needs the trainable extractor)
     _train_neck = False        # the neck: P2..P6 require a gradient (needs a trainable head)
     _train_rpn_head = False    # the RpnHead: the two RPN losses carry a graph into its layers
     _train_roi_head = False    # the RoI head: the two RoI losses carry a graph into its layers

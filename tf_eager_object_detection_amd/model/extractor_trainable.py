@@ -1,14 +1,17 @@
-"""The float32 ResNet extractor of model/fpn_detector.py with a backward pass from conv2 up: ResNetFpnDetector.extractor_trainable
-(reference resnet_fpn.py:208-225, 262-289: conv2..conv5 trainable, batch-norm frozen -- _fold_frozen_bn has folded it into the
-weights, so the folded weights ARE the parameters).  One torch.autograd.Function per bottleneck (_Block): the forward is
+"""The float32 ResNet extractor of model/fpn_detector.py with a backward pass: ResNetFpnDetector.extractor_trainable (reference
+resnet_fpn.py:208-289: conv1_conv and conv2..conv5 trainable, batch-norm frozen -- _fold_frozen_bn has folded it into the weights,
+so the folded weights ARE the parameters).  One torch.autograd.Function per bottleneck (_Block): the forward is
 _Block.forward's own launches (outputs bit-equal, same shapes and strides); the backward runs the block in reverse on this package's
 kernels -- the 1x1 convolutions as the Dense backward over pixels with the ReLU gates applied while staging, the 3x3 convolution's
 weight gradient as ops.conv3x3_wgrad_f32_levels and its input gradient as the forward kernel on the flipped weight, the block's join
-(shortcut + first convolution, with the stride-2 scatter of a stage's first block) as ops.block_input_grad.  The stem stays frozen
-under no_grad: conv1's 7x7 weight gradient and the max-pooling's backward are not built."""
+(shortcut + first convolution, with the stride-2 scatter of a stage's first block) as ops.block_input_grad.  The stem (conv1 and
+its pooling), which the reference trains as well (resnet_fpn.py:233: trainable=True), runs under no_grad by default and conv1 stays
+frozen; with `train_stem` it runs ops.stem_trainable -- the overlapping max-pooling's backward, then conv1's weight and bias
+gradient as ONE ops.dense_wgrad on the stem's patch matrix -- and every parameter of the extractor receives a gradient."""
 import torch
 
 from .. import ops
+from ..derived import derived
 from .fpn_detector import _conv_epi, _nhwc, _stem
 from .trainable_common import flipped_weight, in_param_layout, param_layouts, pointwise_backward, require_exact_f32
 
@@ -97,12 +100,24 @@ def block_trainable(blk, x):
     return _BlockTrainable.apply(blk, wf2, x, *params)
 
 
-def extractor_trainable(det, images_nhwc):
+def stem_trainable(conv1, images_nhwc):
+    """_stem(conv1, images_nhwc, torch.float32) with a backward pass into conv1 (ops.stem_trainable on the layer's cached patch
+    weight): the same launches, bit-equal, with its shape and strides"""
+    w = derived(conv1, 'stem_f32', (conv1.weight,), lambda weight: ops.patch_weight(weight, ops.STEM_PATCH_K))
+    return ops.stem_trainable(images_nhwc, conv1.weight, conv1.bias, stem_weight=w).permute(0, 3, 1, 2)
+
+
+def extractor_trainable(det, images_nhwc, train_stem=False):
     """det.extractor(images_nhwc) with a backward pass into conv2..conv5: (C2, C3, C4, C5), bit-equal to extractor()'s.  The stem
-    (conv1 + pooling) runs under no_grad as in extractor(): conv1 stays frozen."""
+    (conv1 + pooling) runs under no_grad as in extractor() and conv1 stays frozen, unless `train_stem`: then it runs stem_trainable,
+    conv2's first block sees an input that requires a gradient (block_input_grad's convolutional-shortcut form at stride 1) and
+    conv1's weight and bias receive theirs."""
     require_exact_f32(det, 'extractor_trainable')
-    with torch.no_grad():
-        x = _stem(det.conv1, images_nhwc, det.dtype)
+    if train_stem:
+        x = stem_trainable(det.conv1, images_nhwc)
+    else:
+        with torch.no_grad():
+            x = _stem(det.conv1, images_nhwc, det.dtype)
     outs = []
     for name in STAGES:
         for blk in getattr(det, name):

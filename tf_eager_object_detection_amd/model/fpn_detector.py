@@ -123,18 +123,10 @@ def _own_conv3x3(conv, x):
 _FUSED_TAIL_MIN_SLABS = 200
 
 # the float32 mode's patch matrices (stem, VGG16's first convolution) are addressed with 32-bit byte offsets
-_PATCH_BYTES_MAX = 0xF0000000
+_PATCH_BYTES_MAX = ops.PATCH_BYTES_MAX
 
 
-def _patch_weight(weight, kpad):
-    """a [cout, cin, kh, kw] convolution weight as the patch-matrix GEMM's float32 [cout, kpad]: rows in (dy, dx, channel) order,
-    zero columns from kh * kw * cin on"""
-    with torch.no_grad():
-        cout = int(weight.shape[0])
-        k = weight.numel() // cout
-        w = torch.zeros((cout, kpad), dtype=torch.float32, device=weight.device)
-        w[:, :k] = weight.permute(0, 2, 3, 1).reshape(cout, k)
-    return w
+_patch_weight = ops.patch_weight
 
 
 def _patch_gemm(images_nhwc, per_image, patches, w, bias=None, relu=False, tail=None):
@@ -358,11 +350,13 @@ class ResNetFpnDetector(Detector):
         return c2, c3, c4, self.conv5(c4)
 
     @_in_f32_form
-    def extractor_trainable(self, images_nhwc):
+    def extractor_trainable(self, images_nhwc, train_stem=False):
         """extractor with a backward pass into conv2..conv5 (float32, f32_form 'exact'; model/extractor_trainable.py): outputs
-        bit-equal to extractor()'s with its shapes and strides; the stem runs under no_grad and conv1 stays frozen"""
+        bit-equal to extractor()'s with its shapes and strides; the stem runs under no_grad and conv1 stays frozen, unless
+        `train_stem` (one image group): then conv1's weight and bias receive a gradient too, as in the reference
+        (resnet_fpn.py:233), and no parameter of the extractor is left without one"""
         from .extractor_trainable import extractor_trainable
-        return extractor_trainable(self, images_nhwc)
+        return extractor_trainable(self, images_nhwc, train_stem=train_stem)
 
     def features(self, images_nhwc):
         """[B,H,W,3] -> (P2..P6), each [B,256,h,w] channels_last (= NHWC in memory)."""

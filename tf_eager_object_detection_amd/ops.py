@@ -733,6 +733,32 @@ def relu_maxpool2_backward(z, bias, dpool, out=None):
     return out
 
 
+def relu_maxpool3_backward(z, bias, dpool, out=None):
+    """The backward of bias_relu_maxpool(z, bias, 3, 2, 1, ceil_mode=False) in one launch (odet_relu_maxpool3_backward_f32): TF's
+    MaxPoolGrad through pool1_pad, then ReluGrad, behind the FPN stem's trainable conv1 (resnet_fpn.py:233-242).  ``z`` [B,H,W,C]
+    (the convolution's raw output, without bias), ``bias`` [C], ``dpool`` [B,(H-1)//2+1,(W-1)//2+1,C] -> dz [B,H,W,C]: window (p,q)
+    covers rows 2p-1..2p+1 and columns 2q-1..2q+1 inside the map and gives dpool[p,q] to the first tap in row-major order that
+    holds its maximum of max(z + bias, 0) when that is > 0 (a NaN never wins); a pixel sums the up to four windows it wins in
+    ascending (p,q) order, +0 where it wins none.  Elementwise, so the same under both grad forms.  Contiguous NHWC float32 GPU
+    tensors, C % 4 == 0.  float32, f32_form 'exact' only."""
+    who = 'relu_maxpool3_backward'
+    named = [('z', z), ('bias', bias), ('dpool', dpool)]
+    _grad_operands(who, 'max-pooling backward', named)
+    if z.dim() != 4 or int(z.shape[1]) < 1 or int(z.shape[2]) < 1 or int(z.shape[3]) < 4 or int(z.shape[3]) % 4:
+        raise ValueError('%s: z %s must be an NHWC tensor [B,H,W,C] with a positive map size and C a positive multiple of 4'
+                         % (who, tuple(z.shape)))
+    B, H, W, Cc = (int(v) for v in z.shape)
+    if tuple(bias.shape) != (Cc,):
+        raise ValueError('%s: bias %s does not go with z %s' % (who, tuple(bias.shape), tuple(z.shape)))
+    pooled = (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc)
+    if tuple(dpool.shape) != pooled:
+        raise ValueError('%s: dpool %s does not go with z %s (the pooled map is %s)' % (who, tuple(dpool.shape), tuple(z.shape), pooled))
+    _grad_on_gpu(who, named)
+    out = _out(out, (B, H, W, Cc), torch.float32, z.device)
+    L.call('odet_relu_maxpool3_backward_f32', L.dptr(z), L.dptr(bias), L.dptr(dpool), L.dptr(out), B, H, W, Cc, L.stream())
+    return out
+
+
 DROPOUT_STREAM_FC1, DROPOUT_STREAM_FC2 = 6, 7           # the Philox streams of the RoI head's two dropouts (0-5: include/odet.h)
 
 
@@ -1607,6 +1633,82 @@ def stem_patches_f32(images_nhwc):
     out = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 160), dtype=torch.float32, device=x.device)
     L.call('odet_stem_patches_f32', L.dptr(x), L.dptr(out), B, H, W, L.stream())
     return out
+
+
+# the float32 mode's patch matrices (stem, VGG16's first convolution) are addressed with 32-bit byte offsets
+PATCH_BYTES_MAX = 0xF0000000
+STEM_PATCH_K = 160                # floats per row of the stem's patch matrix: 7 x 7 x 3 = 147 used
+
+
+def patch_weight(weight, kpad):
+    """a [cout, cin, kh, kw] convolution weight as the patch-matrix GEMM's float32 [cout, kpad]: rows in (dy, dx, channel) order,
+    zero columns from kh * kw * cin on"""
+    with torch.no_grad():
+        cout = int(weight.shape[0])
+        k = weight.numel() // cout
+        w = torch.zeros((cout, kpad), dtype=torch.float32, device=weight.device)
+        w[:, :k] = weight.permute(0, 2, 3, 1).reshape(cout, k)
+    return w
+
+
+@carries_grad_form
+class _StemTrainable(torch.autograd.Function):
+    """stem_patches_f32, pointwise, bias_relu_maxpool (3x3 / 2, pad 1) forward -- the float32 stem's launches; backward:
+    relu_maxpool3_backward on the saved raw convolution output, the patch matrix built again, then ONE dense_wgrad over the
+    pixels.  The image gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, images, weight, bias, stem_weight):
+        z = pointwise(stem_patches_f32(images), stem_weight, None, None, False)
+        ctx.save_for_backward(images, z, weight, bias)
+        return bias_relu_maxpool(z, bias, 3, 2, 1, False)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dpool):
+        images, z, weight, bias = ctx.saved_tensors
+        dw = db = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dz = relu_maxpool3_backward(z, bias, dpool.contiguous())
+            patches = stem_patches_f32(images)                            # (171 MB at 800 x 1333: built again, never saved)
+            dw, db = dense_wgrad(dz.view(-1, 64), patches.view(-1, STEM_PATCH_K), with_bias=ctx.needs_input_grad[2])
+            if ctx.needs_input_grad[1]:
+                # [64, 147] in (dy, dx, channel) order -> the parameter's [64, 3, 7, 7], in its own memory format
+                dw = dw[:, :147].reshape(64, 7, 7, 3).permute(0, 3, 1, 2)
+                if not weight.is_contiguous(memory_format=torch.channels_last):
+                    dw = dw.contiguous()
+            else:
+                dw = None
+        return None, dw, db, None
+
+
+def stem_trainable(images_nhwc, weight, bias, stem_weight=None):
+    """The float32 ResNet stem -- conv1_pad + 7x7 / 2 convolution + bias + ReLU + pool1_pad + 3x3 / 2 max-pooling
+    (resnet_fpn.py:233-242) -- with a backward pass into conv1's weight and bias (float32, f32_form 'exact'): the forward is the
+    launches of the detectors' float32 stem (stem_patches_f32, pointwise, bias_relu_maxpool), bit for bit; `.backward()` leaves
+    weight.grad in the parameter's own shape [64,3,7,7] and memory format and bias.grad [64].  The forward keeps the raw convolution
+    output (which it writes anyway) and not the patch matrix; the backward builds that again.  ``images_nhwc`` [B,H,W,3] contiguous
+    float32 on the GPU, whose patch matrix stays below PATCH_BYTES_MAX (one group: training runs one image a call); the image gets
+    no gradient.  ``stem_weight``: a caller's cached patch_weight(weight, STEM_PATCH_K).  -> NHWC [B,Hp,Wp,64]."""
+    who = 'stem_trainable'
+    _grad_operands(who, 'stem backward', [('images', images_nhwc), ('bias', bias)])
+    _grad_f32(who, 'stem backward', [('weight', weight)])                         # (channels_last or contiguous)
+    if images_nhwc.dim() != 4 or int(images_nhwc.shape[3]) != 3 or min(int(v) for v in images_nhwc.shape[:3]) < 1:
+        raise ValueError('%s: images %s must be an NHWC tensor [B,H,W,3] with a positive size' % (who, tuple(images_nhwc.shape)))
+    if tuple(weight.shape) != (64, 3, 7, 7) or tuple(bias.shape) != (64,):
+        raise ValueError('%s: weight %s and bias %s must be [64,3,7,7] and [64]' % (who, tuple(weight.shape), tuple(bias.shape)))
+    B, H, W = (int(v) for v in images_nhwc.shape[:3])
+    patch_bytes = B * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1) * STEM_PATCH_K * 4
+    if patch_bytes > PATCH_BYTES_MAX:
+        raise ValueError('%s: the patch matrix of images %s takes %d bytes, more than one group of %d (train one image a call)'
+                         % (who, tuple(images_nhwc.shape), patch_bytes, PATCH_BYTES_MAX))
+    if stem_weight is None:
+        stem_weight = patch_weight(weight, STEM_PATCH_K)
+    elif not isinstance(stem_weight, torch.Tensor) or stem_weight.dtype != torch.float32 \
+            or tuple(stem_weight.shape) != (64, STEM_PATCH_K) or not stem_weight.is_contiguous():
+        raise ValueError('%s: stem_weight must be a contiguous float32 [64, %d] tensor' % (who, STEM_PATCH_K))
+    _grad_on_gpu(who, [('images', images_nhwc), ('weight', weight), ('bias', bias), ('stem_weight', stem_weight)])
+    return _StemTrainable.apply(images_nhwc, weight, bias, stem_weight)
 
 
 def rgb_patches3x3_f32(images_nhwc):
