@@ -633,14 +633,14 @@ assert len(BY_NAME) == len(CASES)
 
 
 # ---- the product's own launches: the three model families' dense layers ------------------------------------------------------------
-# A restatement of the routing rules of model/fpn_detector.py and model/frcnn_detector.py (which 1x1 convolutions go to the
+# A restatement of the routing rules of model/layers.py and of the detectors' own layers (which 1x1 convolutions go to the
 # pointwise GEMM, from how many slabs on a bottleneck runs as the fused tail, what the float32 mode replaces) as a list of
 # (form, entry point, shape) per model, batch and precision -- only the launches of the three convolution files; the stem, the
 # RGB convolution and the register-resident 1x1 kernel are other kernels.  tests/test_conv_tiles_host.py runs the list through
 # the launchers in plan-only mode; DESIGN.md lists what it reaches.
 MODEL_IMAGES = {'resnet101fpn': (800, 1333), 'resnet50c4': (800, 1333), 'vgg16': (600, 800)}       # the BASELINE configs' sizes
 MODEL_PROPOSALS = {'resnet101fpn': 1000, 'resnet50c4': 300, 'vgg16': 300}
-FUSED_TAIL_MIN_SLABS = 200                # model/fpn_detector.py _FUSED_TAIL_MIN_SLABS
+FUSED_TAIL_MIN_SLABS = 200                # model/layers.py _FUSED_TAIL_MIN_SLABS
 
 
 def _half(hw):

@@ -173,7 +173,7 @@ PARAM_KEYS = (('c1.weight', 'w1'), ('c1.bias', 'b1'), ('c2.weight', 'w2'), ('c2.
 @pytest.fixture(scope='module')
 def blocks():
     """one _Block per kind at the smallest channels the kernels' rules allow, with non-zero biases"""
-    from tf_eager_object_detection_amd.model.fpn_detector import _Block
+    from tf_eager_object_detection_amd.model.layers import _Block
     torch.manual_seed(6)
     made = {}
     for kind, (cin, f, stride, short) in bg.KINDS.items():
@@ -207,7 +207,7 @@ def _random_case(kind, hw, B, seed):
 def _manual_block_grads(blk, x, dy, with_dx):
     """the block's gradients from the ops called by hand, with a freshly flipped weight: what autograd must deliver, bit for bit ->
     ({parameter name: gradient in the parameter's shape}, dx or None, (a, b, y))"""
-    from tf_eager_object_detection_amd.model.fpn_detector import _conv_epi
+    from tf_eager_object_detection_amd.model.layers import _conv_epi
     ops = _ops()
     with torch.no_grad():
         stride = blk.c1.stride[0]

@@ -231,7 +231,8 @@ def test_python_fronts_refuse_on_cpu_tensors():
 def test_block_and_extractor_trainable_refuse_other_forms_without_a_gpu():
     from tf_eager_object_detection_amd import ops
     from tf_eager_object_detection_amd.model.extractor_trainable import block_trainable, extractor_trainable
-    from tf_eager_object_detection_amd.model.fpn_detector import ResNetFpnDetector, _Block
+    from tf_eager_object_detection_amd.model.fpn_detector import ResNetFpnDetector
+    from tf_eager_object_detection_amd.model.layers import _Block
     blk = _Block(256, 64, 1, False)
     with pytest.raises(ValueError, match='block_trainable needs'):
         block_trainable(blk, torch.zeros(1, 256, 2, 3, dtype=torch.float16))

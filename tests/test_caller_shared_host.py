@@ -72,7 +72,7 @@ def test_module_level_names_and_class_defaults():
 
 def test_the_pass_exists_once():
     from tf_eager_object_detection_amd.model import base_faster_rcnn_model as frcnn, base_fpn_model as fpn, caller_base, \
-        detector_base, fpn_detector
+        detector_base, fpn_detector, layers
     F, S = fpn.BaseFPN, frcnn.BaseFasterRcnn
     for name in ('forward', 'call', 'im_detect', '_anchors_and_proposals', '_torch_losses', '_fused_losses', '_training_roi_head',
                  '_get_rpn_loss', '_get_roi_loss'):
@@ -80,7 +80,7 @@ def test_the_pass_exists_once():
     for mod in (fpn, frcnn):
         assert not hasattr(mod, 'check_train_extractor') and not hasattr(mod, 'check_train_neck')
         assert mod.check_training_losses is caller_base.check_training_losses
-        assert mod._nhwc is fpn_detector._nhwc is detector_base._nhwc         # (one NHWC-view helper)
+        assert mod._nhwc is fpn_detector._nhwc is detector_base._nhwc is layers._nhwc         # (one NHWC-view helper)
     # a fresh interpreter: the single-level file loads without the FPN file, and the shared module without either family or detector file
     code = ('import sys\n'
             'import tf_eager_object_detection_amd.model.caller_base\n'

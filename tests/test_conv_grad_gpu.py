@@ -306,7 +306,7 @@ def _maps(rng, B=1, shapes=HEAD_PYRAMID):
 def _manual_rpn_grads(det, p_list, d_scores, d_deltas, with_dx=False):
     """the head's gradients from the kernels called by hand on the head's own float32 activations: what autograd must deliver,
     bit for bit"""
-    from tf_eager_object_detection_amd.model.fpn_detector import rpn_pair_padded, rpn_pair_weights
+    from tf_eager_object_detection_amd.model.layers import rpn_pair_padded, rpn_pair_weights
     ops = _ops()
     A = det.A
     with torch.no_grad():

@@ -29,7 +29,7 @@ def _np_legacy_resize(x, oh, ow):
 
 
 def test_tf_legacy_resize_bilinear_cpu():
-    from tf_eager_object_detection_amd.model.fpn_detector import tf_legacy_resize_bilinear
+    from tf_eager_object_detection_amd.model.layers import tf_legacy_resize_bilinear
     rng = np.random.default_rng(0)
     for (h, w), (oh, ow) in (((13, 21), (25, 42)), ((25, 42), (50, 84)), ((5, 7), (9, 13))):
         x = rng.standard_normal((h, w)).astype(np.float32)
@@ -77,7 +77,8 @@ def test_fpn_topdown_merge_bit_exact(hw, HW, C):
 
 @pytest.mark.gpu
 def test_detector_neck_uses_fused_merge_and_matches_torch_formulation():
-    from tf_eager_object_detection_amd.model.fpn_detector import ResNetFpnDetector, tf_legacy_resize_bilinear
+    from tf_eager_object_detection_amd.model.fpn_detector import ResNetFpnDetector
+    from tf_eager_object_detection_amd.model.layers import tf_legacy_resize_bilinear
     torch.manual_seed(2)
     cl = torch.channels_last
     top = torch.randn(2, 256, 13, 21, device='cuda').contiguous(memory_format=cl)
@@ -123,9 +124,9 @@ def test_bias_act_epilogue(C):
 
 @pytest.mark.gpu
 def test_detector_block_with_fused_epilogue_matches_torch_formulation():
-    from tf_eager_object_detection_amd.model import fpn_detector as fd
+    from tf_eager_object_detection_amd.model import layers
     torch.manual_seed(5)
-    blk = fd._Block(64, 64, 2, True).cuda().to(memory_format=torch.channels_last).eval()
+    blk = layers._Block(64, 64, 2, True).cuda().to(memory_format=torch.channels_last).eval()
     with torch.no_grad():
         for m in (blk.short, blk.c1, blk.c2, blk.c3):
             m.bias.normal_(0, 0.1)
@@ -1190,7 +1191,7 @@ def test_lateral_merge_f16_equals_lateral_then_merge(B, H, W, h, w_, K):
     odet_fpn_topdown_merge applied to the un-rounded lateral convolution on integer data (where the lateral map is exact
     in float16), within float16 rounding of the float32 formulation on random data."""
     from tf_eager_object_detection_amd import ops
-    from tf_eager_object_detection_amd.model.fpn_detector import tf_legacy_resize_bilinear
+    from tf_eager_object_detection_amd.model.layers import tf_legacy_resize_bilinear
     g = torch.Generator(device='cuda'); g.manual_seed(H * W + K)
     N = 256
     x2, w = _int_operands(g, B * H * W, K, N)
@@ -1412,15 +1413,15 @@ def test_float16_detector_passes_run_no_library_convolution_or_gemm(monkeypatch,
 @pytest.mark.gpu
 def test_detectors_have_no_library_or_cpu_route():
     """a layer no kernel takes raises (no silent library convolution, no CPU formulation inside the package)"""
-    from tf_eager_object_detection_amd.model import fpn_detector as fd
+    from tf_eager_object_detection_amd.model import fpn_detector as fd, frcnn_detector, layers
     import inspect
-    src = inspect.getsource(fd) + inspect.getsource(__import__('tf_eager_object_detection_amd.model.frcnn_detector', fromlist=['x']))
+    src = inspect.getsource(fd) + inspect.getsource(frcnn_detector) + inspect.getsource(layers)
     for needle in ('F.conv2d', 'F.linear', 'torch.addmm', '_addmm_activation', 'torch.nn.functional', 'os.environ', 'getenv'):
         assert needle not in src, needle
-    c = fd._conv(48, 64, 3, 1, 1).cuda().half()                          # 48 input channels: not a multiple of 64
+    c = layers._conv(48, 64, 3, 1, 1).cuda().half()                          # 48 input channels: not a multiple of 64
     x = torch.zeros(1, 48, 8, 8, device='cuda', dtype=torch.float16).contiguous(memory_format=torch.channels_last)
     with pytest.raises(RuntimeError, match='no kernel'):
-        fd._conv_epi(c, x)
+        layers._conv_epi(c, x)
     m = fd.ResNetFpnDetector(50, 21, (64, 64), 10, dtype=torch.float32)
     with pytest.raises(RuntimeError, match='no kernel'):
         m.features(torch.zeros(1, 64, 64, 3))                            # CPU tensors
@@ -1477,7 +1478,7 @@ def test_conv3x3_relu_pool2_fused(B, H, W, cin, cout):
 def test_float32_patch_matrix_goes_through_in_groups_below_4_gib(monkeypatch, family):
     """the float32 mode's first convolution runs as a GEMM on a patch matrix addressed with 32-bit offsets: a batch whose
     patches would exceed the limit goes through in groups of images -- same features as in one piece"""
-    from tf_eager_object_detection_amd.model import fpn_detector as fd
+    from tf_eager_object_detection_amd.model import fpn_detector as fd, layers
     from tf_eager_object_detection_amd.model.frcnn_detector import Vgg16Detector
     torch.manual_seed(3)
     shape = (96, 128)
@@ -1487,7 +1488,7 @@ def test_float32_patch_matrix_goes_through_in_groups_below_4_gib(monkeypatch, fa
     with torch.no_grad():
         whole = m.features(img)
         per_image = (48 * 64 * 160 * 4) if family == 'fpn' else (96 * 128 * 64 * 4)
-        monkeypatch.setattr(fd, '_PATCH_BYTES_MAX', per_image + 1)            # one image per group
+        monkeypatch.setattr(layers, '_PATCH_BYTES_MAX', per_image + 1)        # one image per group
         parts = m.features(img)
     whole = whole if isinstance(whole, (list, tuple)) else [whole]
     parts = parts if isinstance(parts, (list, tuple)) else [parts]

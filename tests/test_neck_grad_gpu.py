@@ -189,7 +189,7 @@ def _nhwc(t):
 def _manual_neck_grads(det, cs, dps, with_dc=False):
     """the neck's gradients from the kernels called by hand, with freshly flipped weights: what autograd must deliver, bit for bit.
     dps: dP2..dP6 ([B,256,h,w]) or None -> {parameter name: gradient in the parameter's shape}, 'dc': [dC2..dC5 or None]"""
-    from tf_eager_object_detection_amd.model.fpn_detector import _conv_epi
+    from tf_eager_object_detection_amd.model.layers import _conv_epi
     ops = _ops()
     with torch.no_grad():
         c2, c3, c4, c5 = cs
@@ -294,7 +294,7 @@ def test_neck_trainable_with_output_gradients_absent(detector, absent):
 
 
 def _plain_neck(cs, P):
-    from tf_eager_object_detection_amd.model.fpn_detector import tf_legacy_resize_bilinear as resize
+    from tf_eager_object_detection_amd.model.layers import tf_legacy_resize_bilinear as resize
     c2, c3, c4, c5 = cs
     lin = lambda x, n: F.conv2d(x, P[n + '.weight'], P[n + '.bias'])
     p5 = lin(c5, 'p5')
@@ -322,7 +322,7 @@ def _neck_reference(det, cs, dps, with_bound=True):
                 products, the other terms' adds and the scale)
                 g5 = dP5 + dP6 placed + Rt(h4): Eg = Rt(Eh_4) + (n + 4) u (|dP5| + |dP6 placed| + Rt(|h4| + Eh_4))
       1x1       dW: R_k u (|h| + Eh)^T |C| + Eh^T |C|; db: R_k u sum (|h| + Eh) + sum Eh; dC: 256 u (|h| + Eh) |W| + Eh |W|"""
-    from tf_eager_object_detection_amd.model.fpn_detector import tf_legacy_resize_bilinear as resize
+    from tf_eager_object_detection_amd.model.layers import tf_legacy_resize_bilinear as resize
     d = lambda t: t.detach().double()
     params = dict(det.named_parameters())
     P = {n: d(params[n]).contiguous().requires_grad_() for n in NECK_NAMES}

@@ -98,7 +98,7 @@ def test_base_sub_and_scale_are_applied_in_the_stated_order(top_hw):
 
 def _plain_neck(cs, params):
     """the plain neck on torch tensors (NCHW float64): tf_legacy_resize_bilinear + F.conv2d"""
-    from tf_eager_object_detection_amd.model.fpn_detector import tf_legacy_resize_bilinear
+    from tf_eager_object_detection_amd.model.layers import tf_legacy_resize_bilinear
     c2, c3, c4, c5 = cs
     lin = lambda x, n: F.conv2d(x, params[n][0], params[n][1])
     p5 = lin(c5, 'p5')

@@ -166,7 +166,7 @@ def test_the_call_captures_into_a_graph():
 def test_float16_stem_from_the_float16_batch_equals_the_float32_batch():
     """the ResNet stem (odet_stem_conv7_pool3_f16) converts a float32 image to float16 itself (v_cvt_pk_f16_f32, round to
     nearest even): feeding it the float16 batch gives the same bits as feeding it the float32 batch"""
-    from tf_eager_object_detection_amd.model.fpn_detector import _stem
+    from tf_eager_object_detection_amd.model.layers import _stem
     torch.manual_seed(3)
     conv1 = torch.nn.Conv2d(3, 64, 7, stride=2).cuda().half()
     raws = [_raw(375, 500, s) for s in range(2)]

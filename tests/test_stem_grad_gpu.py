@@ -137,7 +137,7 @@ def _by_hand(img, conv, dpool):
 
 @pytest.mark.parametrize('form', ['exact', 'x3'])
 def test_stem_trainable_forward_is_the_stem_and_gradients_are_the_ops_by_hand(form):
-    from tf_eager_object_detection_amd.model.fpn_detector import _stem
+    from tf_eager_object_detection_amd.model.layers import _stem
     ops = _ops()
     img, w, b, dpool = _stem_case('normal', (37, 45), 1)
     conv = _conv1(w, b)

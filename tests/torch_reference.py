@@ -7,7 +7,7 @@ faster_rcnn/vgg16_faster_rcnn.py:260-342; base_faster_rcnn_model.py:309-350)."""
 import torch
 import torch.nn.functional as F
 
-from tf_eager_object_detection_amd.model.fpn_detector import tf_legacy_resize_bilinear
+from tf_eager_object_detection_amd.model.layers import tf_legacy_resize_bilinear
 
 
 def block(blk, x):

@@ -127,14 +127,14 @@ def _rpn_anchors(model):
 
 def _rpn_activations(model, x):
     """relu(rpn_conv(map)) of every RPN location, [B, locations, cin] float32 in the anchors' location order"""
-    from ..model import fpn_detector as fd
+    from ..model.layers import _conv_epi
     maps = model.features(x)
     maps = maps if isinstance(maps, (list, tuple)) else [maps]
     cin = model.rpn_score.in_channels
     acts = []
     for p in maps:
-        a = fd._conv_epi(model.rpn_conv, p if p.is_contiguous(memory_format=torch.channels_last)
-                         else p.contiguous(memory_format=torch.channels_last), relu=True)
+        a = _conv_epi(model.rpn_conv, p if p.is_contiguous(memory_format=torch.channels_last)
+                      else p.contiguous(memory_format=torch.channels_last), relu=True)
         acts.append(a.permute(0, 2, 3, 1).reshape(a.shape[0], -1, cin).float())
     return torch.cat(acts, 1)
 

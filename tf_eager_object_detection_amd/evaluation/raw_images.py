@@ -8,8 +8,7 @@ in raw-image pixels: the reference's all_boxes[j][i].
 from .. import preprocess as P
 from ..model.base_faster_rcnn_model import BaseFasterRcnn
 from ..model.base_fpn_model import BaseFPN
-from ..model.fpn_detector import ResNetFpnDetector
-from ..model.frcnn_detector import ResNetC4Detector
+from ..model.detector_base import Detector
 from .pascal_eval import detect_image
 
 __all__ = ['detect_raw_images']
@@ -43,7 +42,7 @@ def detect_raw_images(model, images, pipeline, preprocessing_type='caffe', caffe
             scores, deltas, rois = model.im_detect(batch, scales[0])
             out.append(detect(scores, deltas, rois, 1.0, raw[0][0], raw[0][1], **det))   # (rois already / img_scale)
         return out
-    if isinstance(model, (ResNetFpnDetector, ResNetC4Detector)):      # (Vgg16Detector is a ResNetC4Detector)
+    if isinstance(model, Detector):
         want = tuple(model.image_shape)
         for shape, idx in P.group_by_resized_shape(images, min_edge, max_edge, pipeline).items():
             if shape != want:

@@ -3,13 +3,12 @@ roi_head_trainable (reference resnet_faster_rcnn.py:102-158 get_resnet_v1_extrac
 trainable=False, :109, :139-141; :161-185 get_resnet_v1_roi_head: the conv5 stack on the crops, GlobalAveragePooling2D, score /
 boxes).  The bottlenecks are extractor_trainable.py's block_trainable -- forward bit-equal to the blocks' own launches, backward on
 this package's kernels --, the pooling is ops.global_avg_pool_trainable (csrc/c4_grad.hip), the final pair the detectors' shared
-_final_outputs_trainable.  The RpnHead's is model/rpn_trainable.py on the one level."""
+_final_outputs_trainable.  The RpnHead's is model/rpn_trainable.py on the one level (SingleLevelDetector.rpn_trainable)."""
 import torch
 
 from .. import ops
-from .detector_base import _in_f32_form
 from .extractor_trainable import block_trainable
-from .fpn_detector import _nhwc, _stem
+from .layers import _nhwc, _stem
 from .trainable_common import require_exact_f32
 
 FROZEN_STAGES = ('conv1', 'conv2')                        # trainable=False in the reference
@@ -64,27 +63,3 @@ def roi_head_trainable(det, roi_features):
     """det.roi_head(roi_features) with a backward pass into the conv5 stack, score and bbox, and into the crops when they require
     a gradient: (score logits [R,C], box deltas [R,4C])"""
     return det._final_outputs_trainable(head_activation_trainable(det, roi_features))
-
-
-class C4TrainableParts:
-    """ResNetC4Detector's trainable parts (float32, f32_form 'exact'), the three methods the other detectors have"""
-
-    @_in_f32_form
-    def extractor_trainable(self, images_nhwc):
-        """features with a backward pass into conv3 and conv4: the output bit-equal to features()'s with its shape and strides;
-        conv1 and the conv2 stack run under no_grad and stay frozen (resnet_faster_rcnn.py:109, 139-141)"""
-        return extractor_trainable(self, images_nhwc)
-
-    @_in_f32_form
-    def rpn_trainable(self, c4):
-        """rpn with a backward pass into rpn_conv, rpn_score and rpn_bbox (model/rpn_trainable.py on the one level): outputs
-        bit-equal to rpn()'s with its shapes, and a gradient into ``c4`` when it requires one"""
-        from .rpn_trainable import rpn_trainable
-        scores, deltas = rpn_trainable(self, [c4])
-        return scores.view(scores.shape[0], -1, 2 * self.A), deltas        # ([B,n,2] and [B,fh*fw,2A] are the same memory)
-
-    @_in_f32_form
-    def roi_head_trainable(self, roi_features):
-        """roi_head with a backward pass into the conv5 stack, score and bbox: all crops in one pass (no `roi_chunk`), the pooling
-        in ops.global_avg_pool's stated order -- the logits differ from roi_head's by the pooling's rounding only"""
-        return roi_head_trainable(self, roi_features)

@@ -13,7 +13,8 @@ caller's grad mode, and the losses carry a graph into its layers."""
 import torch
 
 from .. import ops
-from .detector_base import _nhwc, caller_range_checked  # noqa: F401  (_nhwc: the callers' NHWC view, the detectors' own helper)
+from .detector_base import caller_range_checked  # noqa: F401
+from .layers import _nhwc  # noqa: F401  (the callers' NHWC view, the detectors' own helper)
 from .losses import cls_loss, fused_roi_losses, fused_rpn_losses, smooth_l1_loss
 from .prediction import post_ops_prediction
 from .proposal_target import training_target_layers
@@ -317,8 +318,9 @@ class CallerModel(torch.nn.Module):
 
 
 class DenseParts:
-    """mixin of the concrete models: the dense parts are a detector (model/fpn_detector.py, model/frcnn_detector.py), owned as
-    `dense` and reachable as `_dense_ref` before the base constructor asks for the layers"""
+    """mixin of the concrete models: the dense parts are a detector (model/fpn_detector.py's ResNetFpnDetector or a
+    SingleLevelDetector of model/frcnn_detector.py; their layers: model/layers.py), owned as `dense` and reachable as `_dense_ref`
+    before the base constructor asks for the layers"""
 
     def _init_with_dense(self, dense, dtype, device, base_init, kw):
         torch.nn.Module.__init__(self)             # (the dense part must exist before the base constructor asks for the layers)

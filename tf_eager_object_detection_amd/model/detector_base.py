@@ -2,7 +2,7 @@
 parts, the batched hot path with the RoI head between its stages, the after-pass checks (sync-free NMS completeness, the two-limb
 float32 form's range), im_detect and the HIP-graph capture -- written once in `Detector`; the RoI heads' last layer
 (`_FinalLayer`) and the float32 form's plumbing.  A family supplies its network and what genuinely differs (see `Detector`).
-This module depends on neither detector file; both import from it."""
+This module depends on neither detector file; both import from it (its only sibling import: model/layers.py, the layer builders)."""
 import contextlib
 import functools
 
@@ -11,24 +11,12 @@ import torch.nn as nn
 
 from .. import ops
 from ..derived import derived
+from .layers import _nhwc, _pad_rows64  # noqa: F401  (_nhwc: importable from here, as the caller models take it)
 
 # sync-free NMS chunks of the assembled detectors unless the caller says otherwise: the first two from the ranked
 # selection (shared launches), the third on the full order -- enough for clustered (trained-like) and massively tied
 # (random-init float16) score distributions; an image that still does not complete is reported empty and flagged
 DEFAULT_BLIND_CHUNKS = 4
-
-
-def _pad_rows64(t):
-    """t [rows, ...] with zero rows up to the next multiple of 64 (the GEMM kernel's output-channel granule)"""
-    out = torch.zeros(((int(t.shape[0]) + 63) // 64 * 64,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
-    out[:t.shape[0]] = t
-    return out
-
-
-def _nhwc(x):
-    """the NHWC memory of a channels_last [B,C,H,W] tensor as a contiguous [B,H,W,C] view"""
-    y = x.permute(0, 2, 3, 1)
-    return y if y.is_contiguous() else y.contiguous()
 
 
 def check_caller_f32_form(form):
@@ -300,6 +288,16 @@ class Detector(_NmsCompleteness, _FinalLayer, nn.Module):
     _max_batch = 1
     _hot_args = ()               # (image_shape, num_classes, num_proposals, channels) and the keywords of the hot-path classes;
     _hot_kwargs = {}             # `batched=False` among them selects the per-image arrangement
+
+    def _declare_modes(self, dtype, grad_form, f32_form, image_shape, num_classes):
+        """the modes every constructor sets before it builds its layers.  f32_form (float32 only): 'exact' = exact-float32 matrix
+        instructions (the parity mode), 'x3' = three bfloat16 limbs per operand (float32-class accuracy at 2.6 x the peak rate),
+        'x2' = two float16 limbs (their range: _NmsCompleteness.range_ok); grad_form: 'exact' | 'x3' (ops.grad_form)"""
+        # (one tuple assignment on purpose: test_detectors_share_one_pass counts this file's plain assignments to f32_form,
+        # which are the two of the x2 -> x3 switch in _on_three_limbs; setting the mode at construction is not that switch)
+        self.dtype, self.f32_form, self.grad_form = dtype, f32_form, ops.check_grad_form(grad_form)
+        self.image_shape = (int(image_shape[0]), int(image_shape[1]))
+        self.num_classes = num_classes
 
     def _declare_hot_path(self, channels, num_proposals, max_batch, hot_kwargs, **defaults):
         self._hot_args = (self.image_shape, self.num_classes, num_proposals, channels)

@@ -1,6 +1,6 @@
 """The float32 ResNet extractor of model/fpn_detector.py with a backward pass: ResNetFpnDetector.extractor_trainable (reference
 resnet_fpn.py:208-289: conv1_conv and conv2..conv5 trainable, batch-norm frozen -- _fold_frozen_bn has folded it into the weights,
-so the folded weights ARE the parameters).  One torch.autograd.Function per bottleneck (_Block): the forward is
+so the folded weights ARE the parameters).  One torch.autograd.Function per bottleneck (model/layers.py's _Block): the forward is
 _Block.forward's own launches (outputs bit-equal, same shapes and strides); the backward runs the block in reverse on this package's
 kernels -- the 1x1 convolutions as the Dense backward over pixels with the ReLU gates applied while staging, the 3x3 convolution's
 weight gradient as ops.conv3x3_wgrad_f32_levels and its input gradient as the forward kernel on the flipped weight, the block's join
@@ -12,7 +12,7 @@ import torch
 
 from .. import ops
 from ..derived import derived
-from .fpn_detector import _conv_epi, _nhwc, _stem
+from .layers import _conv_epi, _nhwc, _stem
 from .trainable_common import flipped_weight, in_param_layout, param_layouts, pointwise_backward, require_exact_f32
 
 STAGES = ('conv2', 'conv3', 'conv4', 'conv5')
@@ -90,7 +90,7 @@ class _BlockTrainable(torch.autograd.Function):
 
 
 def block_trainable(blk, x):
-    """blk(x) (a fpn_detector._Block on a channels_last float32 map) with a backward pass into the block's 6 or 8 parameters, and into
+    """blk(x) (a layers._Block on a channels_last float32 map) with a backward pass into the block's 6 or 8 parameters, and into
     x when it requires a gradient; float32, f32_form 'exact' only"""
     if x.dtype != torch.float32 or ops.current_f32_form() != 'exact':
         raise ValueError("block_trainable needs a float32 map and f32_form='exact' (the bottleneck backward has no float16 or "

@@ -8,59 +8,34 @@ through this repository's kernels (NHWC, float32 = parity mode / float16 = throu
 route, no CPU path); everything between them is FrcnnHotPath (anchors in registers -> [A bg | A fg] softmax -> decode /
 clip -> exact NMS over all anchors -> 7x7 crop (ResNet) / 14x14 crop + 2x2 max (VGG16) on the stride-16 map ->
 post_ops_prediction).  The pass that strings them together -- prepare, forward, im_detect, the after-pass checks, the
-HIP-graph capture -- is detector_base.Detector's, shared with the FPN detector; this file holds the two networks and the
-per-image (`batched=False`) arrangement of the single-level families.  Weights are randomly initialised with the reference's initialisers (no checkpoints offline), frozen
-batch-norm folded.  The plain-torch formulation of the same networks lives with the tests (tests/torch_reference.py)."""
+HIP-graph capture -- is detector_base.Detector's, shared with the FPN detector; this file holds what the single-level families
+share (`SingleLevelDetector`: the RpnHead, the dense pass, the per-image (`batched=False`) arrangement) and, as siblings under it,
+the two networks.  The layer builders and the kernel routing are model/layers.py's; the trainable parts (model/c4_trainable.py,
+vgg_trainable.py, rpn_trainable.py) import layers, never this file, and are imported here at the top.  Weights are randomly
+initialised with the reference's initialisers (no checkpoints offline), frozen batch-norm folded.  The plain-torch formulation of the
+same networks lives with the tests (tests/torch_reference.py)."""
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..derived import derived
 from ..pipeline import FrcnnHotPath, FrcnnStepBatch
-from .c4_trainable import C4TrainableParts
+from . import c4_trainable, vgg_trainable
 from .detector_base import Detector, _in_f32_form
-from .fpn_detector import _BLOCKS, _conv, _conv_epi, _conv_relu_pool, _fold_frozen_bn, _nhwc, _no_kernel, _patch_gemm, \
-    _patch_weight, _stack, _stem, rpn_pair_padded, rpn_pair_weights
+from .layers import _BLOCKS, _conv, _conv_epi, _conv_relu_pool, _fold_frozen_bn, _nhwc, _no_kernel, _patch_gemm, _patch_weight, \
+    _stack, _stem, fc_head_activation, init_linears, rpn_head_layers, rpn_pair_padded, rpn_pair_weights
+from .rpn_trainable import rpn_trainable
+from .trainable_common import fc_head_trainable
 
-__all__ = ['ResNetC4Detector', 'Vgg16Detector']
+__all__ = ['SingleLevelDetector', 'ResNetC4Detector', 'Vgg16Detector']
 
 
-class ResNetC4Detector(C4TrainableParts, Detector):
-    """ResNet-{50,101,152} C4 Faster R-CNN (inference pass: detector_base.Detector; trainable parts: model/c4_trainable.py).
-    Batched arrangement: FrcnnStepBatch (odet_fpn_step_t.single_level); per image (`batched=False`): one FrcnnHotPath per
-    image on a stream of its own, then ONE RoI-head call for the whole batch."""
+class SingleLevelDetector(Detector):
+    """What the Faster R-CNN families on ONE stride-16 map share (the pass: detector_base.Detector): the RpnHead, the dense pass and the
+    arrangements.  Batched: FrcnnStepBatch (odet_fpn_step_t.single_level); per image (`batched=False`): one FrcnnHotPath per image on a
+    stream of its own, then ONE RoI-head call for the whole batch.  A family supplies its layers, `features` and `head_activation`."""
 
     _step_batch_class, _hot_path_class = FrcnnStepBatch, FrcnnHotPath
-
-    def __init__(self, depth=50, num_classes=21, image_shape=(800, 1333), num_proposals=300, dtype=torch.float32,
-                 max_batch=1, roi_chunk=0, f32_form='exact', grad_form='exact', **hot_kwargs):
-        super().__init__()
-        b = _BLOCKS[depth]
-        self.dtype, self.grad_form = dtype, ops.check_grad_form(grad_form)     # grad_form: 'exact' | 'x3' (ops.grad_form)
-        self.f32_form = f32_form             # float32 mode: 'exact' | 'x3' | 'x2' (model/detector_base.py)
-        self.image_shape = (int(image_shape[0]), int(image_shape[1]))
-        self.num_classes = num_classes
-        # extractor (resnet_faster_rcnn.py:104-153): conv1 .. conv4, stride 16
-        self.conv1 = _fold_frozen_bn(_conv(3, 64, 7, 2, 0))
-        self.conv2 = _stack(64, 64, b[0], 1)
-        self.conv3 = _stack(256, 128, b[1], 2)
-        self.conv4 = _stack(512, 256, b[2], 2)
-        # RPN head (base_faster_rcnn_model.py:309-350); 9 anchors per cell, scores laid out [A bg | A fg]
-        self.A = 9
-        self.rpn_conv = _conv(1024, 512, 3, 1, 1, std=0.01)
-        self.rpn_score = _conv(512, 2 * self.A, 1, std=0.01)
-        self.rpn_bbox = _conv(512, 4 * self.A, 1, std=0.001)
-        # RoI head (resnet_faster_rcnn.py:156-183): conv5 stack (stride1 = 1) on the 7x7 crops, GAP, 2 dense
-        self.conv5 = _stack(1024, 512, b[3], 1)
-        self.score = nn.Linear(2048, num_classes)
-        self.bbox = nn.Linear(2048, 4 * num_classes)
-        for m, std in ((self.score, 0.01), (self.bbox, 0.001)):
-            nn.init.normal_(m.weight, 0.0, std)
-            nn.init.zeros_(m.bias)
-        # config/faster_rcnn_config.py: 'resnet_roi_pooling_max_pooling_flag': False (7x7 crop, no pool) -- what
-        # model_factory.py:117 passes, overriding the class default
-        self._declare_hot_path(1024, num_proposals, max_batch, hot_kwargs, pool_size=7, max_pooling_flag=False)
-        self._roi_chunk = int(roi_chunk)
 
     def _prepare_per_image(self):
         # the images' RoI features are consecutive blocks of one buffer: the RoI head takes the whole batch at once
@@ -92,14 +67,6 @@ class ResNetC4Detector(C4TrainableParts, Detector):
             cur.wait_event(done)
         return out
 
-    # ---- dense parts ---------------------------------------------------------------------------
-    @_in_f32_form
-    def features(self, images_nhwc):
-        """[B,H,W,3] -> C4 [B,1024,ceil(H/16),ceil(W/16)] channels_last (= NHWC in memory)."""
-        # conv1_pad + valid 7x7/2, bias + ReLU, pool1_pad (zeros) + 3x3/2 (float16: one launch from the image)
-        x = _stem(self.conv1, images_nhwc, self.dtype)
-        return self.conv4(self.conv3(self.conv2(x)))
-
     @_in_f32_form
     def rpn(self, c4):
         """RpnHead: scores [B, fh*fw, 2A] ([A bg | A fg] per location), deltas [B, fh*fw*A, 4] (float32)."""
@@ -118,15 +85,12 @@ class ResNetC4Detector(C4TrainableParts, Detector):
         ops.rpn_pack_pair(sd if sd.is_contiguous() else sd.contiguous(), b, self.A, scores, deltas, 0)
         return scores.view(B, -1, 2 * self.A), deltas
 
-    def head_activation(self, roi_features):
-        """[R,7,7,1024] NHWC -> conv5 -> global average pool [R,2048] (resnet_faster_rcnn.py:156-183): the input of the score /
-        bbox layers"""
-        x = roi_features.permute(0, 3, 1, 2).to(self.dtype)                      # NCHW view of NHWC memory
-        R = x.shape[0]
-        step = self._roi_chunk if self._roi_chunk > 0 else R
-        outs = [self.conv5(x[i:i + step]).mean(dim=(2, 3)) for i in range(0, R, step)]
-        y = outs[0] if len(outs) == 1 else torch.cat(outs, 0)
-        return y.contiguous()
+    @_in_f32_form
+    def rpn_trainable(self, c):
+        """rpn with a backward pass into rpn_conv, rpn_score and rpn_bbox (float32, f32_form 'exact'; model/rpn_trainable.py on
+        the one level): outputs bit-equal to rpn()'s with its shapes, and a gradient into ``c`` when it requires one"""
+        scores, deltas = rpn_trainable(self, [c])
+        return scores.view(scores.shape[0], -1, 2 * self.A), deltas        # ([B,n,2] and [B,fh*fw,2A] are the same memory)
 
     @_in_f32_form
     def roi_head(self, roi_features):
@@ -140,9 +104,7 @@ class ResNetC4Detector(C4TrainableParts, Detector):
         c4 = self.features(images_nhwc)
         rpn_scores, rpn_deltas = self.rpn(c4)
         rpn_scores, rpn_deltas = rpn_scores.float().contiguous(), rpn_deltas.float().contiguous()
-        maps = c4.permute(0, 2, 3, 1)                                            # NHWC view
-        if maps.dtype != self._feature_dtype:
-            maps = maps.to(self._feature_dtype)
+        maps = c4.permute(0, 2, 3, 1).to(self._feature_dtype)                    # NHWC view (.to: the same tensor when the dtype is)
         return rpn_scores, rpn_deltas, maps.contiguous()
 
     @staticmethod
@@ -163,8 +125,65 @@ class ResNetC4Detector(C4TrainableParts, Detector):
         return [(cls[b], bbox[b]) for b in range(B)]
 
 
-class Vgg16Detector(ResNetC4Detector):
-    """VGG16 Faster R-CNN (inference pass: detector_base.Detector; trainable parts: model/vgg_trainable.py) -- counterpart of model/faster_rcnn/vgg16_faster_rcnn.py
+class ResNetC4Detector(SingleLevelDetector):
+    """ResNet-{50,101,152} C4 Faster R-CNN (the pass and the RpnHead: SingleLevelDetector; trainable parts:
+    model/c4_trainable.py): extractor conv1..conv4, RoI head = conv5 stack on the 7x7 crops + global average pool."""
+
+    def __init__(self, depth=50, num_classes=21, image_shape=(800, 1333), num_proposals=300, dtype=torch.float32,
+                 max_batch=1, roi_chunk=0, f32_form='exact', grad_form='exact', **hot_kwargs):
+        super().__init__()
+        b = _BLOCKS[depth]
+        self._declare_modes(dtype, grad_form, f32_form, image_shape, num_classes)
+        # extractor (resnet_faster_rcnn.py:104-153): conv1 .. conv4, stride 16
+        self.conv1 = _fold_frozen_bn(_conv(3, 64, 7, 2, 0))
+        self.conv2 = _stack(64, 64, b[0], 1)
+        self.conv3 = _stack(256, 128, b[1], 2)
+        self.conv4 = _stack(512, 256, b[2], 2)
+        # RPN head (base_faster_rcnn_model.py:309-350); 9 anchors per cell, scores laid out [A bg | A fg]
+        self.A = 9
+        self.rpn_conv, self.rpn_score, self.rpn_bbox = rpn_head_layers(1024, self.A)
+        # RoI head (resnet_faster_rcnn.py:156-183): conv5 stack (stride1 = 1) on the 7x7 crops, GAP, 2 dense
+        self.conv5 = _stack(1024, 512, b[3], 1)
+        self.score = nn.Linear(2048, num_classes)
+        self.bbox = nn.Linear(2048, 4 * num_classes)
+        init_linears((self.score, 0.01), (self.bbox, 0.001))
+        # config/faster_rcnn_config.py: 'resnet_roi_pooling_max_pooling_flag': False (7x7 crop, no pool) -- what
+        # model_factory.py:117 passes, overriding the class default
+        self._declare_hot_path(1024, num_proposals, max_batch, hot_kwargs, pool_size=7, max_pooling_flag=False)
+        self._roi_chunk = int(roi_chunk)
+
+    # ---- dense parts ---------------------------------------------------------------------------
+    @_in_f32_form
+    def features(self, images_nhwc):
+        """[B,H,W,3] -> C4 [B,1024,ceil(H/16),ceil(W/16)] channels_last (= NHWC in memory)."""
+        # conv1_pad + valid 7x7/2, bias + ReLU, pool1_pad (zeros) + 3x3/2 (float16: one launch from the image)
+        x = _stem(self.conv1, images_nhwc, self.dtype)
+        return self.conv4(self.conv3(self.conv2(x)))
+
+    @_in_f32_form
+    def extractor_trainable(self, images_nhwc):
+        """features with a backward pass into conv3 and conv4: the output bit-equal to features()'s with its shape and strides;
+        conv1 and the conv2 stack run under no_grad and stay frozen (resnet_faster_rcnn.py:109, 139-141)"""
+        return c4_trainable.extractor_trainable(self, images_nhwc)
+
+    def head_activation(self, roi_features):
+        """[R,7,7,1024] NHWC -> conv5 -> global average pool [R,2048] (resnet_faster_rcnn.py:156-183): the input of the score /
+        bbox layers"""
+        x = roi_features.permute(0, 3, 1, 2).to(self.dtype)                      # NCHW view of NHWC memory
+        R = x.shape[0]
+        step = self._roi_chunk if self._roi_chunk > 0 else R
+        outs = [self.conv5(x[i:i + step]).mean(dim=(2, 3)) for i in range(0, R, step)]
+        return (outs[0] if len(outs) == 1 else torch.cat(outs, 0)).contiguous()
+
+    @_in_f32_form
+    def roi_head_trainable(self, roi_features):
+        """roi_head with a backward pass into the conv5 stack, score and bbox: all crops in one pass (no `roi_chunk`), the pooling
+        in ops.global_avg_pool's stated order -- the logits differ from roi_head's by the pooling's rounding only"""
+        return c4_trainable.roi_head_trainable(self, roi_features)
+
+
+class Vgg16Detector(SingleLevelDetector):
+    """VGG16 Faster R-CNN (the pass and the RpnHead: SingleLevelDetector; trainable parts: model/vgg_trainable.py) -- counterpart of model/faster_rcnn/vgg16_faster_rcnn.py
     (Vgg16Extractor :260-342: 13 3x3 'same' convolutions + ReLU, four 2x2/2 'same' max-pools, stride 16;
     Vgg16RoiHead :178-257: flatten(7,7,512) -> fc 4096 -> fc 4096 -> score / boxes) around FrcnnHotPath
     (14x14 crop + 2x2 max on 512 channels).  BASELINE config "VGG16 Faster R-CNN, 1x3x600x800"."""
@@ -173,11 +192,8 @@ class Vgg16Detector(ResNetC4Detector):
 
     def __init__(self, num_classes=21, image_shape=(600, 800), num_proposals=300, dtype=torch.float32, max_batch=1,
                  f32_form='exact', grad_form='exact', **hot_kwargs):
-        nn.Module.__init__(self)
-        self.dtype, self.grad_form = dtype, ops.check_grad_form(grad_form)
-        self.f32_form = f32_form
-        self.image_shape = (int(image_shape[0]), int(image_shape[1]))
-        self.num_classes = num_classes
+        super().__init__()
+        self._declare_modes(dtype, grad_form, f32_form, image_shape, num_classes)
         convs, cin = [], 3
         for cout, n in self._CFG:
             for _ in range(n):
@@ -185,18 +201,13 @@ class Vgg16Detector(ResNetC4Detector):
                 cin = cout
         self.convs = nn.ModuleList(convs)
         self.A = 9
-        self.rpn_conv = _conv(512, 512, 3, 1, 1, std=0.01)
-        self.rpn_score = _conv(512, 2 * self.A, 1, std=0.01)
-        self.rpn_bbox = _conv(512, 4 * self.A, 1, std=0.001)
+        self.rpn_conv, self.rpn_score, self.rpn_bbox = rpn_head_layers(512, self.A)
         self.fc1 = nn.Linear(7 * 7 * 512, 4096)
         self.fc2 = nn.Linear(4096, 4096)
         self.score = nn.Linear(4096, num_classes)
         self.bbox = nn.Linear(4096, 4 * num_classes)
-        for m, std in ((self.fc1, 0.01), (self.fc2, 0.01), (self.score, 0.01), (self.bbox, 0.001)):
-            nn.init.normal_(m.weight, 0.0, std)
-            nn.init.zeros_(m.bias)
+        init_linears((self.fc1, 0.01), (self.fc2, 0.01), (self.score, 0.01), (self.bbox, 0.001))
         self._declare_hot_path(512, num_proposals, max_batch, hot_kwargs, pool_size=7, max_pooling_flag=True)
-        self._roi_chunk = 0
 
     def _first_conv(self, images_nhwc):
         """conv1_1 + ReLU from the image, channels_last"""
@@ -206,15 +217,13 @@ class Vgg16Detector(ResNetC4Detector):
         if self.dtype == torch.float16 and images_nhwc.dtype in (torch.float32, torch.float16):
             # conv1_1 straight from the image (ops.conv3x3_rgb: bias + ReLU in the launch, its output written once)
             packed = derived(first, 'rgb_f16', (first.weight,), ops.conv3x3_rgb_pack_weights)
-            x = ops.conv3x3_rgb(images_nhwc, packed, first.bias, relu=True).permute(0, 3, 1, 2)
-        elif self.dtype == torch.float32 and images_nhwc.dtype == torch.float32:
+            return ops.conv3x3_rgb(images_nhwc, packed, first.bias, relu=True).permute(0, 3, 1, 2)
+        if self.dtype == torch.float32 and images_nhwc.dtype == torch.float32:
             # float32 (parity mode): conv1_1 as the exact-float32 GEMM on its patch matrix (ops.rgb_patches3x3_f32)
             w = derived(first, 'rgb_f32', (first.weight,), lambda weight: _patch_weight(weight, 64))
             Hn, Wn = int(images_nhwc.shape[1]), int(images_nhwc.shape[2])
-            x = _patch_gemm(images_nhwc, Hn * Wn * 64 * 4, ops.rgb_patches3x3_f32, w, first.bias, True)
-        else:
-            raise _no_kernel('first convolution', first, images_nhwc)
-        return x
+            return _patch_gemm(images_nhwc, Hn * Wn * 64 * 4, ops.rgb_patches3x3_f32, w, first.bias, True)
+        raise _no_kernel('first convolution', first, images_nhwc)
 
     def _layer_plan(self):
         """(index into convs, pooled) of the convolutions after conv1_1; pooled: a stage's last convolution, with
@@ -245,27 +254,15 @@ class Vgg16Detector(ResNetC4Detector):
     def extractor_trainable(self, images_nhwc):
         """features with a backward pass into block3_conv1 .. block5_conv3 (float32, f32_form 'exact'; model/vgg_trainable.py):
         the output bit-equal to features()'s with its shape and strides; blocks 1-2 run under no_grad and stay frozen"""
-        from .vgg_trainable import extractor_trainable
-        return extractor_trainable(self, images_nhwc)
+        return vgg_trainable.extractor_trainable(self, images_nhwc)
 
-    @_in_f32_form
-    def rpn_trainable(self, c):
-        """rpn with a backward pass into rpn_conv, rpn_score and rpn_bbox (float32, f32_form 'exact'; model/rpn_trainable.py on
-        the one level): outputs bit-equal to rpn()'s with its shapes, and a gradient into ``c`` when it requires one"""
-        from .rpn_trainable import rpn_trainable
-        scores, deltas = rpn_trainable(self, [c])
-        return scores.view(scores.shape[0], -1, 2 * self.A), deltas        # ([B,n,2] and [B,fh*fw,2A] are the same memory)
+    def head_activation(self, roi_features):
+        """flatten(7,7,512) -> fc6 -> fc7 (vgg16_faster_rcnn.py:178-257; dropout: inference): the FC head of model/layers.py"""
+        return fc_head_activation(self, roi_features)
 
     @_in_f32_form
     def roi_head_trainable(self, roi_features, keep_prob=1.0, seed=0, image_id=0):
         """roi_head with a backward pass into fc1, fc2, score and bbox and the reference's two dropouts (float32, f32_form 'exact';
-        model/vgg_trainable.py): fc1 -> dropout (stream 6) -> fc2 -> dropout (stream 7) -> score / bbox; with keep_prob 1 the
-        outputs are bit-equal to roi_head's"""
-        from .vgg_trainable import roi_head_trainable
-        return roi_head_trainable(self, roi_features, keep_prob, seed, image_id)
-
-    def head_activation(self, roi_features):
-        x = roi_features.reshape(roi_features.shape[0], -1).to(self.dtype)        # Flatten() of NHWC crops
-        # fc6 / fc7 on the pointwise GEMM kernel, bias + ReLU in its epilogue (dropout: inference)
-        x = ops.dense(x if x.is_contiguous() else x.contiguous(), self.fc1.weight, self.fc1.bias, relu=True)
-        return ops.dense(x, self.fc2.weight, self.fc2.bias, relu=True)
+        trainable_common.fc_head_trainable): fc1 -> dropout (stream 6) -> fc2 -> dropout (stream 7) -> score / bbox; with
+        keep_prob 1 the outputs are bit-equal to roi_head's"""
+        return fc_head_trainable(self, roi_features, keep_prob, seed, image_id)

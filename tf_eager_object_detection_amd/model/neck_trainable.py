@@ -2,11 +2,11 @@
 own launches (outputs bit-equal, same shapes and strides); the backward runs the neck in reverse on this package's kernels -- the
 three 3x3 output convolutions' weight gradients as ops.conv3x3_wgrad_f32_levels and their input gradients as the forward kernel on
 the flipped weights, the top-down merges' backward as ops.fpn_topdown_backward (one launch per coarse level: the resize's transpose
-with the level's other gradient terms folded in), the four 1x1 convolutions as the Dense backward over pixels."""
+with the level's other gradient terms folded in), the four 1x1 convolutions as the Dense backward over pixels (layers: model/layers.py)."""
 import torch
 
 from .. import ops
-from .fpn_detector import _conv_epi, _nhwc
+from .layers import _conv_epi, _nhwc
 from .trainable_common import flipped_weight, in_param_layout, param_layouts, pointwise_backward, require_exact_f32
 
 _LAYERS = ('p5', 'l4', 'l3', 'l2', 's4', 's3', 's2')

@@ -1,11 +1,12 @@
-"""The float32 RpnHead of model/fpn_detector.py with a backward pass: ResNetFpnDetector.rpn_trainable.  The forward is rpn()'s own
-launches (outputs bit-equal); the backward runs the head's layers in reverse on this package's kernels -- the pair of 1x1
-convolutions as the Dense backward over pixels (ops.dense_wgrad / dense_dgrad), the 3x3 convolution's weight gradient as
-ops.conv3x3_wgrad_f32_levels over all levels in one call, its input gradient as the forward kernel on the flipped weight."""
+"""The float32 RpnHead with a backward pass: ResNetFpnDetector.rpn_trainable over the levels, SingleLevelDetector.rpn_trainable on its
+one.  The forward is the FPN rpn()'s own launches (outputs bit-equal); the backward runs the head's layers in reverse on this package's
+kernels -- the pair of 1x1 convolutions (its derived weights: model/layers.py) as the Dense backward over pixels (ops.dense_wgrad /
+dense_dgrad), the 3x3 convolution's weight gradient as ops.conv3x3_wgrad_f32_levels over all levels in one call, its input gradient
+as the forward kernel on the flipped weight."""
 import torch
 
 from .. import ops
-from .fpn_detector import _nhwc, _no_kernel, _own_conv3x3, rpn_pair_padded, rpn_pair_weights
+from .layers import _nhwc, _no_kernel, _own_conv3x3, rpn_pair_padded, rpn_pair_weights
 from .trainable_common import flipped_weight, in_param_layout, param_layouts, require_exact_f32
 
 

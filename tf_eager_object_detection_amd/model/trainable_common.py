@@ -1,5 +1,6 @@
-"""What the trainable parts (neck_trainable.py, extractor_trainable.py, rpn_trainable.py, vgg_trainable.py, the detectors'
-roi_head_trainable) and the caller models' train_* keywords share.  Imports ops and derived only: every model file may import it."""
+"""What the trainable parts (neck_trainable.py, extractor_trainable.py, rpn_trainable.py, vgg_trainable.py, c4_trainable.py) and the
+caller models' train_* keywords share, and the one trainable FC head of the FPN and VGG16 detectors (fc_head_trainable).  Imports
+ops and derived only: every model file may import it."""
 import torch
 
 from .. import ops
@@ -19,6 +20,20 @@ def require_exact_f32(det, who):
     """a detector's trainable part `who` runs only in float32 and f32_form 'exact': the backward kernels have no other form"""
     if det.dtype != torch.float32 or det.f32_form != 'exact':
         raise ValueError("%s needs dtype=torch.float32 and f32_form='exact' (got %s, %r)" % (who, det.dtype, det.f32_form))
+
+
+def fc_head_trainable(det, roi_features, keep_prob=1.0, seed=0, image_id=0):
+    """det.roi_head(roi_features) of an FC head with a backward pass into fc1, fc2, score and bbox, and tf.nn.dropout(keep_prob) behind
+    fc1 (Philox stream 6) and fc2 (stream 7) as the reference trains the VGG16 head (vgg16_faster_rcnn.py:250-253); keep_prob 1 (the
+    FPN head): bit-equal to roi_head.  Features that require a gradient (ops.roi_pool_trainable's) get one: fc1's dense_dgrad.
+    `det` has fc1, fc2, `dtype`, `f32_form` and _FinalLayer's _final_outputs_trainable (score, bbox): ResNetFpnDetector, Vgg16Detector."""
+    require_exact_f32(det, 'roi_head_trainable')
+    x = roi_features.reshape(roi_features.shape[0], -1).to(det.dtype)            # Flatten() of NHWC crops
+    x = ops.dense_trainable(x, det.fc1.weight, det.fc1.bias, relu=True)
+    x = ops.dropout_trainable(x, keep_prob, seed, image_id, ops.DROPOUT_STREAM_FC1)
+    x = ops.dense_trainable(x, det.fc2.weight, det.fc2.bias, relu=True)
+    x = ops.dropout_trainable(x, keep_prob, seed, image_id, ops.DROPOUT_STREAM_FC2)
+    return det._final_outputs_trainable(x)
 
 
 def flipped_weight(conv, half=False):

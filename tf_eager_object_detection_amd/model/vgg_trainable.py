@@ -3,13 +3,13 @@ roi_head_trainable (reference vgg16_faster_rcnn.py:260-342 Vgg16Extractor with b
 Vgg16RoiHead with both dropouts active in training).  The forward passes are features()' and roi_head()'s own launches (outputs
 bit-equal); the backward runs on this package's kernels -- the nine 3x3 convolutions of blocks 3-5 on ops.conv3x3_trainable_levels
 (one level), the two that carry a pooling on ops.conv3x3_relu_pool_trainable (odet_relu_maxpool2_backward_f32 in front of the weight
-gradient), the Dense layers on ops.dense_trainable with ops.dropout_trainable between them.  The RpnHead's is
-model/rpn_trainable.py on the one level."""
+gradient), the Dense layers with ops.dropout_trainable between them on trainable_common.fc_head_trainable (the FPN head's too; here
+under the name roi_head_trainable).  The RpnHead's is model/rpn_trainable.py on the one level (SingleLevelDetector.rpn_trainable)."""
 import torch
 
 from .. import ops
-from .fpn_detector import _nhwc, _no_kernel, _own_conv3x3
-from .trainable_common import flipped_weight, require_exact_f32
+from .layers import _nhwc, _no_kernel, _own_conv3x3
+from .trainable_common import fc_head_trainable as roi_head_trainable, flipped_weight, require_exact_f32  # noqa: F401
 
 FIRST_TRAINED = 4                        # convs[4] = block3_conv1: blocks 1-2 (convs[0..3]) are frozen, :265-288
 
@@ -44,16 +44,3 @@ def extractor_trainable(det, images_nhwc):
         else:
             x = ops.conv3x3_trainable_levels([x], conv.weight, conv.bias, relu=True, flipped=wf)[0]
     return x.permute(0, 3, 1, 2)
-
-
-def roi_head_trainable(det, roi_features, keep_prob=1.0, seed=0, image_id=0):
-    """det.roi_head(roi_features) with a backward pass into fc1, fc2, score and bbox, and tf.nn.dropout(keep_prob) behind fc1
-    (Philox stream 6) and fc2 (stream 7) as the reference trains the head (:250-253); keep_prob 1: bit-equal to roi_head.  Features
-    that require a gradient (ops.roi_pool_trainable's, with a trainable extractor) get one: fc1's dense_dgrad."""
-    require_exact_f32(det, 'roi_head_trainable')
-    x = roi_features.reshape(roi_features.shape[0], -1).to(det.dtype)            # Flatten() of NHWC crops
-    x = ops.dense_trainable(x, det.fc1.weight, det.fc1.bias, relu=True)
-    x = ops.dropout_trainable(x, keep_prob, seed, image_id, ops.DROPOUT_STREAM_FC1)
-    x = ops.dense_trainable(x, det.fc2.weight, det.fc2.bias, relu=True)
-    x = ops.dropout_trainable(x, keep_prob, seed, image_id, ops.DROPOUT_STREAM_FC2)
-    return det._final_outputs_trainable(x)

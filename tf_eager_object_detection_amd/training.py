@@ -7,7 +7,7 @@ a graph.  Arithmetic: include/odet.h "training step" (TF r1.13's ApplyMomentum /
 tests/optimizer_np.py restates it).
 
 Deviations from the reference, both forced by how this package holds its parameters:
-  * frozen batch normalisation is folded into the convolution kernels here (model/fpn_detector.py _fold_frozen_bn), so
+  * frozen batch normalisation is folded into the convolution kernels here (model/layers.py _fold_frozen_bn), so
     the L2 regulariser acts on the FOLDED tensors, not on the raw kernels keras regularises;
   * the float16 detector modes hold float16 parameters: the optimizer keeps a float32 master per float16 variable (created
     from its value); the update and the L2 term use the master and the variable is the master rounded to nearest-even once.

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""The caller models of two source trees against each other, through their public surface only: the same file runs on a checkout of
-an earlier commit and on the present tree (profiles/caller_models_refactor.json).
+"""The caller models and the assembled detectors of two source trees against each other, through their public surface only: the same
+file runs on a checkout of an earlier commit and on the present tree (profiles/caller_models_refactor.json,
+profiles/detector_layers_refactor.json).
 
   python tools/caller_models_identity.py --parent DIR [--new DIR] --out FILE.json
 
@@ -9,7 +10,9 @@ limit; the first failure ends the chain (nothing more is started) and the file s
 one inference call, one im_detect, predict_rois / predict_roi, two training calls each followed by sum(losses).backward() -- and
 keeps, per step, the ordered names of the native entry points (_lib.recording), SHA-256 of every output, of the four losses and of
 every parameter gradient in named_parameters() order, and the three image-id counters; then it times one call (training: forward +
-backward; the plain models: inference), eager, synchronised on both sides, 3 warm-ups, 20 samples.
+backward; the plain models: inference), eager, synchronised on both sides, 3 warm-ups, 20 samples.  A detector leg (det_*: the
+assembled ResNetFpnDetector / ResNetC4Detector / Vgg16Detector at batch 2, once per dtype) does prepare() and forward(), then a second
+forward(), keeps the same record per step (the padded detections and the counts hashed) and times forward().
 
 Identity: what differs between the two parent runs is listed and left out of the claim; everything else must be equal between
 parent and new.  Time: new <= max(parent runs) + |parent_1 - parent_2| on the medians."""
@@ -37,9 +40,15 @@ LEGS = {
     'fpn_plain': ('base_fpn_model', 'ResnetV1Fpn', dict(depth=50), (256, 352), 1, 1, 'fpn', 'inference'),
     'c4_plain': ('base_faster_rcnn_model', 'ResNetFasterRcnn', dict(depth=50, roi_pooling_max_pooling_flag=False), (208, 256), 6, 3,
                  'single', 'inference'),
+    'det_fpn': ('fpn_detector', 'ResNetFpnDetector', dict(depth=50, num_proposals=128), (256, 352), 1, 1, None, 'detector'),
+    'det_c4': ('frcnn_detector', 'ResNetC4Detector', dict(depth=50, num_proposals=64), (208, 256), 6, 3, None, 'detector'),
+    'det_vgg16': ('frcnn_detector', 'Vgg16Detector', dict(num_proposals=64), (208, 256), 6, 3, None, 'detector'),
 }
+# (leg, the training legs' target / loss layers or a detector leg's dtype)
 RUNS = [(leg, losses) for leg in ('fpn_4flags', 'c4_3flags', 'vgg16_3flags') for losses in ('hip', 'torch')] + \
-       [('fpn_plain', 'hip'), ('c4_plain', 'hip')]
+       [('fpn_plain', 'hip'), ('c4_plain', 'hip')] + \
+       [(leg, dtype) for leg in ('det_fpn', 'det_c4', 'det_vgg16') for dtype in ('float16', 'float32')]
+DETECTOR_BATCH = 2
 CHILD_LIMIT_S = 240
 
 
@@ -62,9 +71,18 @@ def child(root, leg, losses, out):
     module, cls, kw, shape, image_seed, model_seed, gt_key, timed = LEGS[leg]
     ctor = getattr(importlib.import_module('tf_eager_object_detection_amd.model.' + module), cls)
     torch.manual_seed(model_seed)
-    m = ctor(training_targets=losses, training_losses=losses, **kw)
     rng = np.random.default_rng(image_seed)
-    img = torch.from_numpy((rng.uniform(0, 255, (1,) + shape + (3,)) - 110).astype(np.float32)).cuda()
+    batch = DETECTOR_BATCH if timed == 'detector' else 1
+    img = torch.from_numpy((rng.uniform(0, 255, (batch,) + shape + (3,)) - 110).astype(np.float32)).cuda()
+    if timed == 'detector':
+        m = ctor(image_shape=shape, dtype=getattr(torch, losses), max_batch=batch, **kw)
+
+        def detect(prepare=False):
+            if prepare:
+                m.prepare()
+            return [t for image in m(img) for t in image]                   # (boxes, labels, scores, count) per image
+        return _record(_lib, torch, [('prepare_forward', lambda: detect(True)), ('forward_2', detect)], detect, timed, out)
+    m = ctor(training_targets=losses, training_losses=losses, **kw)
     gt, gl = torch.tensor(GT[gt_key][0], device='cuda'), torch.tensor(GT[gt_key][1], device='cuda')
     params = list(m.named_parameters())
     torch.manual_seed(11)                                       # (the 'torch' target layers draw their samples from this generator)
@@ -83,6 +101,12 @@ def child(root, leg, losses, out):
     steps = [('inference', lambda: list(m(img, training=False))), ('im_detect', lambda: list(m.im_detect(img, 1.25))),
              ('predict', lambda: [m.predict_rois(img, gt, gl)] if gt_key == 'fpn' else list(m.predict_roi(img, gt, gl))),
              ('training_1', train), ('training_2', train)]
+    call = train if timed == 'training' else (lambda: m(img, training=False))
+    _record(_lib, torch, steps, call, timed, out, counters, lambda: sum(1 for _, p in params if p.grad is not None))
+
+
+def _record(_lib, torch, steps, call, timed, out, counters=lambda: [], trained=None):
+    """runs the steps under _lib.recording, times `call`, writes the leg's record"""
     record = {}
     for name, fn in steps:
         with _lib.recording() as calls:
@@ -91,8 +115,8 @@ def child(root, leg, losses, out):
         names = [getattr(c[0], '__name__', str(c[0])) for c in calls]
         record[name] = dict(native_calls=len(names), call_list_sha256=hashlib.sha256('\n'.join(names).encode()).hexdigest(),
                             call_list=names, hashes=[_sha(x) for x in result], counters=counters())
-    record['training_1']['trained_parameters'] = sum(1 for _, p in params if p.grad is not None)
-    call = train if timed == 'training' else (lambda: m(img, training=False))
+    if trained is not None:
+        record['training_1']['trained_parameters'] = trained()
     ms = []
     for i in range(23):
         torch.cuda.synchronize()
@@ -135,7 +159,8 @@ def main():
     for leg, losses in RUNS:
         if args.only and leg not in args.only:
             continue
-        key = '%s, training_losses=%s' % (leg, losses) if LEGS[leg][7] == 'training' else leg
+        what = LEGS[leg][7]
+        key = '%s, training_losses=%s' % (leg, losses) if what == 'training' else '%s, dtype=%s' % (leg, losses) if what == 'detector' else leg
         recs = {}
         for run, root in (('parent_1', args.parent), ('new', args.new), ('parent_2', args.parent)):
             tmp = os.path.join(work, 'leg_%s_%s_%s.json' % (leg, losses, run))
@@ -161,7 +186,7 @@ def main():
         result['legs'][key] = dict(
             steps={s: dict(native_calls=v['native_calls'], call_list_sha256=v['call_list_sha256'], tensors_hashed=len(v['hashes']),
                            counters_after=v['counters']) for s, v in recs['new'].items() if s != 'timing'},
-            trained_parameters=recs['new']['training_1']['trained_parameters'],
+            trained_parameters=recs['new'].get('training_1', {}).get('trained_parameters'),
             differs_between_the_two_parent_runs=noise, differs_between_parent_and_new=diff,
             identical=not diff, timed=t['new']['what'], median_ms=med, min_max_ms={r: t[r]['min_max_ms'] for r in t},
             parent_runs_differ_by_ms=round(spread, 3),

@@ -29,7 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tf_eager_object_detection_amd import ops                                                          # noqa: E402
 from tf_eager_object_detection_amd.model.extractor_trainable import STAGES, block_layers, block_trainable  # noqa: E402
-from tf_eager_object_detection_amd.model.fpn_detector import ResNetFpnDetector, _stem                 # noqa: E402
+from tf_eager_object_detection_amd.model.fpn_detector import ResNetFpnDetector                        # noqa: E402
+from tf_eager_object_detection_amd.model.layers import _stem                                          # noqa: E402
 import neck_grad_bench as nb                                                                           # noqa: E402
 
 HBM_PEAK = 8.0e12

@@ -135,7 +135,8 @@ def extractor_rows(image=(800, 1333), depth=50):
     'exact' (the form is recorded on the graph's nodes when it is built) against torch autograd of the plain F.conv2d bottleneck"""
     from extractor_grad_bench import leaves_of, plain_block
     from tf_eager_object_detection_amd.model.extractor_trainable import STAGES, block_trainable
-    from tf_eager_object_detection_amd.model.fpn_detector import ResNetFpnDetector, _stem
+    from tf_eager_object_detection_amd.model.fpn_detector import ResNetFpnDetector
+    from tf_eager_object_detection_amd.model.layers import _stem
     rng = np.random.default_rng(0)
     f = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32)).cuda()
     nchw = lambda t: t.permute(0, 3, 1, 2)

@@ -6,7 +6,7 @@ autograd on the same float32 tensors; writes profiles/neck_grad_bench.json.
   ours       merge backward: ops.fpn_topdown_backward per coarse level (the resize's transpose + base (+ sub) + scale, one launch);
              s_k: ops.conv3x3_wgrad_f32_levels and ops.conv3x3_dgrad_f32_levels on the cached flipped weight (s2's halved); 1x1
              layers: ops.dense_wgrad over pixels; whole neck: everything .backward() of neck_trainable enqueues.
-  yardstick  torch autograd: for the merge alone the backward of fpn_detector.tf_legacy_resize_bilinear (the gradient with respect
+  yardstick  torch autograd: for the merge alone the backward of layers.tf_legacy_resize_bilinear (the gradient with respect
              to the coarse map ONLY: no base, no scale -- less work than ours does in the launch); for the whole neck the backward
              of tf_legacy_resize_bilinear + F.conv2d on channels_last tensors (parameter gradients, no gradient into C2..C5).  The
              autograd graph is built once outside the capture, on the stream that captures (autograd runs a backward on its
@@ -29,7 +29,7 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tf_eager_object_detection_amd import ops                                            # noqa: E402
-from tf_eager_object_detection_amd.model.fpn_detector import tf_legacy_resize_bilinear   # noqa: E402
+from tf_eager_object_detection_amd.model.layers import tf_legacy_resize_bilinear   # noqa: E402
 
 INNER, REPLAYS = 3, 30
 TOP = 256

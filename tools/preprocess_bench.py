@@ -8,7 +8,7 @@ Per row: batch 1 / 8 of raw 375x500 (-> 600x800) or 1080x1920 (-> 562x1000 voc, 
                 (back-to-back launches on one stream, no host time inside);
   bytes         moved per launch: 3*h*w read + 12*H*W (float32) or 6*H*W (float16) written, per image;
   torch_us      the same work composed from torch ops under the same protocol: type conversion, mean subtraction,
-                fpn_detector.tf_legacy_resize_bilinear (NCHW) and the NHWC layout (+ the float16 cast);
+                layers.tf_legacy_resize_bilinear (NCHW) and the NHWC layout (+ the float16 cast);
   calib_us      odet_calib_stream_mix moving the same read and write bytes (a kernel that only moves bytes), same protocol:
                 rate_vs_calib = (bytes / us) / (calib_bytes / calib_us), the kernel's byte rate over the calibration's.
 
@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tf_eager_object_detection_amd import _lib as L                                     # noqa: E402
 from tf_eager_object_detection_amd import preprocess as P                              # noqa: E402
-from tf_eager_object_detection_amd.model.fpn_detector import tf_legacy_resize_bilinear  # noqa: E402
+from tf_eager_object_detection_amd.model.layers import tf_legacy_resize_bilinear  # noqa: E402
 
 INNER = 20
 
