@@ -47,7 +47,8 @@ extern "C" {
  * training graph's max-pooling and dropout backward (odet_relu_maxpool2_backward_f32, odet_dropout_f32, odet_dropout_backward_f32) and
  * the ResNet-C4 head's global average pooling (odet_global_avg_pool_f32, odet_global_avg_pool_backward_f32) and the
  * data-parallel gradient exchange (odet_bucket_pack_f32, odet_bucket_unpack_f32, odet_rank_mean_f32) and the FPN stem's
- * max-pooling backward (odet_relu_maxpool3_backward_f32); no
+ * max-pooling backward (odet_relu_maxpool3_backward_f32) and the K-image step's accumulate launch
+ * (odet_bucket_accumulate_f32); no
  * existing struct or signature changed.  One documented order did: from
  * 4096 rows on, odet_dense_wgrad_f32 adds db in 256 running sums per column, not 4 (its own comment; below 4096 rows every bit is
  * as before). */
@@ -1321,6 +1322,23 @@ int odet_bucket_pack_f32(const void* const* tensors, const int64_t* numels, int 
 int odet_bucket_unpack_f32(const float* bucket, int64_t bucket_chunks, void* const* tensors, const int64_t* numels,
                            int num_tensors, const odet_opt_chunk_t* chunks, int num_chunks, odet_stream_t stream);
 int odet_rank_mean_f32(const float* parts, int world, int64_t n, int average, float* out, odet_stream_t stream);
+
+/* odet_bucket_accumulate_f32: one image of a K-image training step (training.GradientAccumulator) in ONE launch over the whole
+ * gradient list.  The tables, the layout, the "a record that does not fit is absent" rule and the alignment rules are those of
+ * odet_bucket_pack_f32.  For every element e of a present tensor, g the tensor's element and b = bucket[e]:
+ *   s = g when first, else s = b + g (ONE float32 add, no contraction);
+ *   bucket[e] = s when divisor == 1.0f, else s / divisor (one correctly rounded IEEE division, not a multiplication by a
+ *   reciprocal).
+ * A window of K images is first = 1 on image 0, first = 0 after it, divisor = float32(K) on the last call (1.0f before): the
+ * statement of odet_rank_mean_f32 -- the first image's bits, one add per image in ascending image order, one division at the end.
+ * first = 1 writes EVERY element of the bucket as pack does (+0.0f in the tail of a tensor's last chunk, in absent records and in
+ * the chunks num_chunks .. bucket_chunks - 1); first = 0 writes the present tensors' elements and nothing else.  Every element
+ * that is written is written once; no atomics, no allocation, no host read (graph-capturable).  Per element 8 bytes are read and
+ * 4 written (first: 4 and 4).
+ * Errors, before any HIP call: ODET_E_INVALID (pack's conditions, first outside {0, 1}, a divisor that is not finite and > 0),
+ * ODET_E_LIMIT (pack's limits). */
+int odet_bucket_accumulate_f32(const void* const* tensors, const int64_t* numels, int num_tensors, const odet_opt_chunk_t* chunks,
+                               int num_chunks, float* bucket, int64_t bucket_chunks, int first, float divisor, odet_stream_t stream);
 
 /* ---- Dense backward, float32 (added within 103) --------------------------------------------------------------------
  * The gradients of a keras Dense layer y = relu?(x . w^T + b) (resnet_fpn.py:292-336, the FPN RoI head) on the exact-float32

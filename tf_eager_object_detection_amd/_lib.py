@@ -240,6 +240,7 @@ SIGNATURES = {
     'odet_bucket_pack_f32': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i64, _vp]),
     'odet_bucket_unpack_f32': (_i, [_vp, _i64, _vp, _vp, _i, _vp, _i, _vp]),
     'odet_rank_mean_f32': (_i, [_vp, _i, _i64, _i, _vp, _vp]),
+    'odet_bucket_accumulate_f32': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i64, _i, _f, _vp]),
     'odet_dense_grad_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'odet_dense_dgrad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),
     'odet_dense_wgrad_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp]),

@@ -2,7 +2,8 @@
 // packed into one contiguous float32 bucket in ONE launch, its inverse, and the sum over the ranks' parts in ASCENDING RANK
 // order.  The collectives around them (all_to_all_single, all_gather_into_tensor) only move bytes, so the exchanged gradient is
 // a function of the data alone: tests/grad_exchange_np.py restates all three bit for bit.  No allocation, no host read, no
-// atomics; every output element is written exactly once by one lane.
+// atomics; every output element is written exactly once by one lane.  odet_bucket_accumulate_f32 adds one image's gradient list
+// into such a bucket (training.GradientAccumulator, tests/grad_accumulate_np.py): the K-image step in one launch per image.
 //
 // Layout (include/odet.h "gradient exchange"): the optimizer's chunk table (odet_opt_chunk_t, ODET_OPT_CHUNK elements) built over
 // the PRESENT tensors, so chunk c of the table is chunk c of the bucket; the chunks past the table pad the bucket to a whole
@@ -80,6 +81,81 @@ __global__ void __launch_bounds__(GX_THREADS) k_bucket_move(BucketArgs a) {
       }
     }
   }
+}
+
+// One image of a K-image window (training.GradientAccumulator): one workgroup per bucket chunk, shaped as k_bucket_move<true> is (a
+// sibling: pack and unpack keep their machine code).  FIRST: bucket = g, and every element of the bucket is written as pack
+// writes it (+0.0f in the tails, in absent records and in the padding chunks); else bucket = bucket + g, ONE float32 add, over
+// the present tensors' own elements and nothing else.  DIVIDE: the sum then goes through one IEEE division by `divisor`.
+// Per element 8 bytes are read and 4 written (FIRST: 4 and 4); both operands of a lane's share are loaded before its first store.
+//
+// WHOLE (uniform over the workgroup): the chunk lies inside its tensor and the tensor is 16-byte aligned -- 16-byte accesses on
+// both sides and no bound in the code.  Every other chunk (a tensor's last one, a shifted tensor, an absent record) goes element
+// by element under its bound, with the same bits.  Two bodies under a uniform branch, not one body with a per-group test: the
+// compiler folds a per-group "whole group, else by element" into the by-element form and the 16-byte stores are gone.
+template <bool FIRST, bool DIVIDE, bool WHOLE>
+__device__ __forceinline__ void bucket_accumulate_chunk(float* __restrict__ slot, const float* __restrict__ t, int64_t base, int64_t n,
+                                                        float divisor) {
+  float g[GX_GROUPS][4], b[GX_GROUPS][4];
+#pragma unroll
+  for (int k = 0; k < GX_GROUPS; ++k) {                     // every load before the first store
+    const int e0 = (k * GX_THREADS + (int)threadIdx.x) * 4;
+    const int64_t j = base + e0;
+    if (WHOLE) {
+      const float4 q = *reinterpret_cast<const float4*>(t + j);
+      g[k][0] = q.x; g[k][1] = q.y; g[k][2] = q.z; g[k][3] = q.w;
+      if (!FIRST) {
+        const float4 r = *reinterpret_cast<const float4*>(slot + e0);
+        b[k][0] = r.x; b[k][1] = r.y; b[k][2] = r.z; b[k][3] = r.w;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const bool in = t && j + e < n;
+        g[k][e] = in ? t[j + e] : 0.0f;
+        if (!FIRST) b[k][e] = in ? slot[e0 + e] : 0.0f;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < GX_GROUPS; ++k) {
+    const int e0 = (k * GX_THREADS + (int)threadIdx.x) * 4;
+    const int64_t j = base + e0;
+    float s[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      s[e] = FIRST ? g[k][e] : b[k][e] + g[k][e];           // one float32 add per image
+      if (DIVIDE) s[e] = s[e] / divisor;                    // IEEE division, correctly rounded (+0.0f stays +0.0f: divisor > 0)
+    }
+    if (FIRST || WHOLE) {
+      *reinterpret_cast<float4*>(slot + e0) = make_float4(s[0], s[1], s[2], s[3]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (j + e < n) slot[e0 + e] = s[e];
+    }
+  }
+}
+
+template <bool FIRST, bool DIVIDE>
+__global__ void __launch_bounds__(GX_THREADS) k_bucket_accumulate(BucketArgs a, float divisor) {
+  const int64_t c = blockIdx.x;
+  float* const slot = a.bucket + c * ODET_OPT_CHUNK;        // (16-byte aligned: the host checked the bucket)
+  const float* t = nullptr;
+  int64_t n = 0, base = 0;
+  if (c < a.num_chunks) {
+    const odet_opt_chunk_t ck = a.chunks[c];
+    if ((unsigned)ck.tensor < (unsigned)a.num_tensors) {
+      t = (const float*)a.tensors[ck.tensor];
+      n = a.numels[ck.tensor];
+      base = ck.offset;
+      if (base < 0 || base >= n || base % ODET_OPT_CHUNK) t = nullptr;     // (a record that does not fit: absent)
+    }
+  }
+  if (!FIRST && !t) return;                                 // (uniform over the workgroup)
+  // (base is a multiple of the chunk: t + base is aligned with t)
+  if (t && ((uintptr_t)t & 15) == 0 && base + ODET_OPT_CHUNK <= n) bucket_accumulate_chunk<FIRST, DIVIDE, true>(slot, t, base, n, divisor);
+  else bucket_accumulate_chunk<FIRST, DIVIDE, false>(slot, t, base, n, divisor);
 }
 
 // out[i] = ((parts[0][i] + parts[1][i]) + ...) + parts[world - 1][i], then / float32(world) with `average`.  A lane owns
@@ -176,6 +252,31 @@ extern "C" int odet_bucket_unpack_f32(const float* bucket, int64_t bucket_chunks
   a.tensors = (const void* const*)tensors; a.numels = numels; a.chunks = chunks; a.bucket = const_cast<float*>(bucket);
   a.num_tensors = num_tensors; a.num_chunks = num_chunks;
   hipLaunchKernelGGL(k_bucket_move<false>, dim3((unsigned)num_chunks), dim3(GX_THREADS), 0, (hipStream_t)stream, a);
+  ODET_LAUNCH_CHECK();
+  return ODET_OK;
+}
+
+extern "C" int odet_bucket_accumulate_f32(const void* const* tensors, const int64_t* numels, int num_tensors,
+                                          const odet_opt_chunk_t* chunks, int num_chunks, float* bucket, int64_t bucket_chunks,
+                                          int first, float divisor, odet_stream_t stream) {
+  const int rc = bucket_check("odet_bucket_accumulate_f32", tensors, numels, num_tensors, chunks, num_chunks, bucket, bucket_chunks);
+  if (rc != ODET_OK) return rc;
+  ODET_REQUIRE(first == 0 || first == 1, "odet_bucket_accumulate_f32: first must be 0 or 1, got %d", first);
+  ODET_REQUIRE(divisor > 0.0f && divisor <= 3.402823466e38f, "odet_bucket_accumulate_f32: the divisor must be finite and > 0");
+  const int64_t blocks = first ? bucket_chunks : num_chunks;            // (a later image touches the table's chunks only)
+  if (blocks == 0) return ODET_OK;
+  BucketArgs a;
+  a.tensors = tensors; a.numels = numels; a.chunks = chunks; a.bucket = bucket;
+  a.num_tensors = num_tensors; a.num_chunks = num_chunks;
+  const dim3 grid((unsigned)blocks), block(GX_THREADS);
+  const hipStream_t st = (hipStream_t)stream;
+  if (divisor == 1.0f) {
+    if (first) hipLaunchKernelGGL((k_bucket_accumulate<true, false>), grid, block, 0, st, a, divisor);
+    else hipLaunchKernelGGL((k_bucket_accumulate<false, false>), grid, block, 0, st, a, divisor);
+  } else {
+    if (first) hipLaunchKernelGGL((k_bucket_accumulate<true, true>), grid, block, 0, st, a, divisor);
+    else hipLaunchKernelGGL((k_bucket_accumulate<false, true>), grid, block, 0, st, a, divisor);
+  }
   ODET_LAUNCH_CHECK();
   return ODET_OK;
 }

@@ -2448,6 +2448,20 @@ def bucket_pack(tables, tensors, bucket=None):
     return bucket
 
 
+def bucket_accumulate(tables, tensors, bucket, first, divisor=1.0):
+    """odet_bucket_accumulate_f32: one image of a K-image window, one launch.  first: bucket = tensors, every element of the
+    bucket written as bucket_pack writes it; else bucket += tensors (one float32 add) over the present tensors' elements only.
+    divisor != 1: the sum then goes through one IEEE float32 division (the window's last call carries float32(K))."""
+    tables._bucket(bucket)
+    divisor = float(divisor)
+    if not (0.0 < divisor < float('inf')):
+        raise ValueError('the divisor must be finite and > 0, got %r' % divisor)
+    tables.set_pointers(tensors)
+    L.call('odet_bucket_accumulate_f32', L.dptr(tables.pointers), L.dptr(tables.numels_dev), tables.num_tensors, L.dptr(tables.chunks),
+           tables.num_chunks, L.dptr(bucket), tables.bucket_chunks, 1 if first else 0, divisor, L.stream())
+    return bucket
+
+
 def bucket_unpack(tables, bucket, tensors):
     """odet_bucket_unpack_f32: the bucket -> the tensors' own elements, one launch; nothing else is written"""
     tables._bucket(bucket)

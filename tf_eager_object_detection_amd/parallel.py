@@ -13,7 +13,8 @@ exactly one collective.
 
 Training is data-parallel with one image per rank (second half of this file): GradientExchange averages the gradients over
 the ranks in ascending rank order on csrc/grad_exchange.hip, between two collectives that only move bytes;
-broadcast_variables starts the replicas equal; DataParallelTrainer is the loop body around them.
+broadcast_variables starts the replicas equal; DataParallelTrainer is the loop body around them (images_per_rank = K > 1: every
+rank first forms the mean of its own K images, training.GradientAccumulator).
 """
 import torch
 import torch.distributed as dist
@@ -166,6 +167,25 @@ def _rank_mean_torch(parts, average):
     return s / torch.full_like(s, float(parts.shape[0])) if average else s
 
 
+def check_gradients(variables, gradients):
+    """the rule of GradientExchange (and of training.GradientAccumulator): one gradient or None per variable, float32, on the
+    variable's device, with its shape and strides"""
+    if len(gradients) != len(variables):
+        raise ValueError('%d gradients for %d variables' % (len(gradients), len(variables)))
+    for i, (g, v) in enumerate(zip(gradients, variables)):
+        if g is None:
+            continue
+        if g.dtype == torch.float16:
+            raise TypeError('gradient %d is float16: the gradient exchange is float32 only' % i)
+        if g.dtype != torch.float32:
+            raise TypeError('gradient %d must be float32, got %s' % (i, g.dtype))
+        if g.device != v.device:
+            raise ValueError('gradient %d lives on %s, its variable on %s' % (i, g.device, v.device))
+        if g.shape != v.shape or (g.numel() > 1 and g.stride() != v.stride() and not (g.is_contiguous() and v.is_contiguous())):
+            raise ValueError('gradient %d (shape %s, strides %s) does not have the layout of its variable (shape %s, strides %s)'
+                             % (i, tuple(g.shape), g.stride(), tuple(v.shape), v.stride()))
+
+
 class _ExchangeLayout:
     """the buffers of one set of present gradients: the bucket, what the all-to-all receives, the reduced shard, the views"""
 
@@ -214,20 +234,7 @@ class GradientExchange:
         self._key = None
 
     def _check(self, gradients, scalars):
-        if len(gradients) != len(self.variables):
-            raise ValueError('%d gradients for %d variables' % (len(gradients), len(self.variables)))
-        for i, (g, v) in enumerate(zip(gradients, self.variables)):
-            if g is None:
-                continue
-            if g.dtype == torch.float16:
-                raise TypeError('gradient %d is float16: the gradient exchange is float32 only' % i)
-            if g.dtype != torch.float32:
-                raise TypeError('gradient %d must be float32, got %s' % (i, g.dtype))
-            if g.device != v.device:
-                raise ValueError('gradient %d lives on %s, its variable on %s' % (i, g.device, v.device))
-            if g.shape != v.shape or (g.numel() > 1 and g.stride() != v.stride() and not (g.is_contiguous() and v.is_contiguous())):
-                raise ValueError('gradient %d (shape %s, strides %s) does not have the layout of its variable (shape %s, strides %s)'
-                                 % (i, tuple(g.shape), g.stride(), tuple(v.shape), v.stride()))
+        check_gradients(self.variables, gradients)
         if scalars is not None and (scalars.dtype != torch.float32 or not scalars.is_contiguous()):
             raise TypeError('scalars must be a contiguous float32 tensor')
 
@@ -331,9 +338,12 @@ class DataParallelTrainer:
     The constructor broadcasts rank 0's variables.  model: a trainable caller model (model.dense holds the parameters);
     weight_decay: None, or the L2 coefficient of training.l2_variables."""
 
-    def __init__(self, model, optimizer, group=None, learning_rate_bias_double=False, weight_decay=None):
+    def __init__(self, model, optimizer, group=None, learning_rate_bias_double=False, weight_decay=None, images_per_rank=1):
         from . import training
         self.model, self.optimizer, self.group = model, optimizer, group
+        self.images_per_rank = int(images_per_rank)
+        if self.images_per_rank < 1:
+            raise ValueError('images_per_rank must be at least 1, got %d' % self.images_per_rank)
         self.learning_rate_bias_double = bool(learning_rate_bias_double)
         self.named = training.model_variables(model.dense)
         self.weight_decays = None if weight_decay is None else training.l2_variables(model.dense, weight_decay)
@@ -342,20 +352,49 @@ class DataParallelTrainer:
         self.step_index = 0
         broadcast_variables([p for _, p in self.named], 0, group)
         self.exchange = GradientExchange([p for _, p in self.named], group)
+        self.accumulator = None
+        if self.images_per_rank > 1:
+            # the four losses travel as one more tensor of the accumulated list
+            variables = [p for _, p in self.named]
+            device = variables[0].device if variables else torch.device('cpu')
+            self.accumulator = training.GradientAccumulator(variables + [torch.zeros(4, dtype=torch.float32, device=device)],
+                                                            self.images_per_rank)
 
-    def step(self, inputs):
-        """inputs: (image, gt_bboxes, gt_labels) of THIS rank's image.  Returns the four losses' rank means (device tensors)."""
-        from . import training
+    def _image(self, inputs, image_id):
+        """forward and backward of one image under its Philox image id; returns the four losses as a float32 [4] tensor"""
         m = self.model
-        image_id = self.step_index * self.world + self.rank      # ranks draw different samples and dropout masks
         m._anchor_target._next_image_id = image_id
         m._proposal_target._next_image_id = image_id
         if hasattr(m, '_next_dropout_image_id'):
             m._next_dropout_image_id = image_id
         losses = m(inputs, True)
         sum(losses).backward()
-        scalars = torch.stack([x.detach().reshape(()) for x in losses])
-        gradients, means = self.exchange.exchange([p.grad for _, p in self.named], scalars=scalars)
+        return torch.stack([x.detach().reshape(()) for x in losses])
+
+    def step(self, inputs):
+        """inputs: (image, gt_bboxes, gt_labels) of THIS rank's image; with images_per_rank = K > 1 the list of this rank's K
+        images.  Returns the four losses' rank means (device tensors).
+
+        K > 1: image k of the step has the id (step_index * K + k) * world + rank; the rank forms its own mean over its images
+        (training.GradientAccumulator: the float32 sum in ascending k, / float32(K)), then the exchange averages the ranks'
+        means as before -- the rank mean of the ranks' image means, two roundings; the losses go the same way.  K == 1 is the
+        path, the ids and the bits of one image per rank."""
+        from . import training
+        if self.accumulator is not None:
+            inputs = list(inputs)
+            K = self.images_per_rank
+            if len(inputs) != K:
+                raise ValueError('%d images for a step of %d images per rank' % (len(inputs), K))
+            self.accumulator.reset()
+            for k, one in enumerate(inputs):
+                scalars = self._image(one, (self.step_index * K + k) * self.world + self.rank)
+                out = self.accumulator.add([p.grad for _, p in self.named] + [scalars])
+                for _, p in self.named:
+                    p.grad = None
+            gradients, means = self.exchange.exchange(out[:-1], scalars=out[-1])
+        else:
+            scalars = self._image(inputs, self.step_index * self.world + self.rank)   # ranks draw different samples and dropout masks
+            gradients, means = self.exchange.exchange([p.grad for _, p in self.named], scalars=scalars)
         training.train_step(self.named, gradients, self.optimizer, learning_rate_bias_double=self.learning_rate_bias_double,
                             weight_decays=self.weight_decays)
         for _, p in self.named:

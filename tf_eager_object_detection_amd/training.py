@@ -21,6 +21,10 @@ replay call `mark_updated()` so that the tensors the detectors derive from their
 a derived tensor is valid while every source is the same object with the same (data_ptr, version, dtype, device, shape,
 stride) -- in-place ops through the tensor, load_state_dict and this step rebuild by themselves; `.data` / set_() writes need
 derived.invalidate (ops.invalidate_planes, the detectors' prepare()); a captured graph keeps the derived tensors it was captured with.
+
+The loop around the step (second half of this file): GradientAccumulator forms the mean gradient of K images with one
+odet_bucket_accumulate_f32 launch per image, in ascending image order; Trainer is train_one_epoch / train of
+scripts/train.py:77-202 with checkpoints (model.ckpt-<global_step>) from which a run resumes with the same bits.
 """
 import collections
 import ctypes as C
@@ -246,7 +250,9 @@ class _Optimizer:
         st.global_step = int(state['global_step'])
         st.beta1_power, st.beta2_power = float(state['beta1_power']), float(state['beta2_power'])
         self._state_block().copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8))
-        if self._variables:
+        if not state['slots'] and not self._variables:
+            self._pending = None      # (a state saved before the first step: no variable list, every slot still zero)
+        elif self._variables:
             self._load_slots(state['slots'])
         else:
             self._pending = state['slots']
@@ -312,3 +318,247 @@ def train_step(named_variables, gradients, optimizer, learning_rate_bias_double=
     wds = None if weight_decays is None else [float(weight_decays.get(n, 0.0)) for n in names]
     return optimizer.apply_gradients(zip(gradients, (v for _, v in named_variables)),
                                      grad_scales=grad_scales(names, learning_rate_bias_double), weight_decays=wds, l2=l2)
+
+
+# ---- steps over K images, and the loop around them (scripts/train.py:77-202) ------------------------------------------------------
+def _accumulate_torch(tables, tensors, bucket, first, divisor):
+    """ops.bucket_accumulate in torch ops (CPU tensors): one float32 add per element, one float32 division by a TENSOR divisor,
+    +0.0 wherever no tensor lives on a first call"""
+    if first:
+        bucket.zero_()
+    for i, t in enumerate(tables.check(tensors)):
+        if t is not None and t.numel():
+            o, n = tables.offset(i), t.numel()
+            g = torch.as_strided(t, (n,), (1,), t.storage_offset())
+            s = g.clone() if first else bucket[o:o + n] + g
+            if divisor != 1.0:
+                s = s / torch.full_like(s, divisor)
+            bucket[o:o + n] = s
+    return bucket
+
+
+class _WindowLayout:
+    """the bucket of one set of present gradients and the views the window's last image returns"""
+
+    def __init__(self, numels, variables, device):
+        self.tables = ops.BucketTables(numels, 1, device)
+        self.bucket = torch.zeros(self.tables.bucket_numel, dtype=torch.float32, device=device)
+        self.views = [None if n is None else torch.as_strided(self.bucket, tuple(v.shape), v.stride(), self.tables.offset(i))
+                      for i, (n, v) in enumerate(zip(numels, variables))]
+
+
+class GradientAccumulator:
+    """One optimizer step over K images (a WINDOW) with ONE launch per image over the whole gradient list
+    (odet_bucket_accumulate_f32): the step's gradient is the float32 sum of the images' gradients in ASCENDING IMAGE order,
+    starting from the first image's bits, divided by float32(K) once at the end with `average` -- the statement of
+    odet_rank_mean_f32, restated by tests/grad_accumulate_np.py.
+
+    add(gradients) takes one float32 gradient or None per variable (GradientExchange's rules) and returns None for images
+    1 .. K - 1 of a window; on the K-th it returns a list of VIEWS into the accumulator's own bucket with the variables' shapes
+    and strides (None where the gradient is absent): the same tensors in every window, so the optimizer's pointer column is
+    uploaded once (and the next window overwrites them).  The set of present gradients is fixed by a window's first image; a
+    later image with another set raises ValueError and leaves the window as it was.  images == 1 returns the gradients as given,
+    with no launch.  CPU tensors run the same steps in torch ops."""
+
+    def __init__(self, variables, images, average=True):
+        self.variables = list(variables)
+        self.images = int(images)
+        if self.images < 1:
+            raise ValueError('images must be at least 1, got %d' % self.images)
+        for i, v in enumerate(self.variables):
+            if v.dtype != torch.float32:
+                raise TypeError('variable %d must be float32, got %s' % (i, v.dtype))
+            if not _dense(v):
+                raise ValueError('variable %d is not dense in memory (shape %s, strides %s)' % (i, tuple(v.shape), v.stride()))
+        self.average = bool(average)
+        self._layouts = {}
+        self._key = None              # the open window's set of present gradients
+        self._count = 0
+
+    @property
+    def pending(self):
+        """images in the open window (0 = none open)"""
+        return self._count
+
+    def reset(self):
+        """drops the open window"""
+        self._key, self._count = None, 0
+
+    def _layout(self, numels):
+        lay = self._layouts.get(numels)
+        if lay is None:
+            device = self.variables[0].device if self.variables else torch.device('cpu')
+            lay = self._layouts[numels] = _WindowLayout(list(numels), self.variables, device)
+        return lay
+
+    def add(self, gradients):
+        from . import parallel
+        gradients = list(gradients)
+        parallel.check_gradients(self.variables, gradients)
+        if self.images == 1:
+            return gradients
+        numels = tuple(None if g is None else g.numel() for g in gradients)
+        if self._count and numels != self._key:
+            raise ValueError('image %d of the window has another set of present gradients than its first image' % (self._count + 1))
+        lay = self._layout(numels)
+        first, last = self._count == 0, self._count + 1 == self.images
+        divisor = float(self.images) if (last and self.average) else 1.0        # (float32(K) exactly: K < 2^24)
+        if lay.tables.bucket_numel:
+            if lay.bucket.is_cuda:
+                ops.bucket_accumulate(lay.tables, gradients, lay.bucket, first, divisor)
+            else:
+                _accumulate_torch(lay.tables, gradients, lay.bucket, first, divisor)
+        else:
+            lay.tables.check(gradients)
+        self._key, self._count = numels, self._count + 1
+        if not last:
+            return None
+        self._count = 0
+        return list(lay.views)
+
+    def state_dict(self):
+        """the open window: its count, its set of present gradients and a host copy of its bucket"""
+        open_ = self._count > 0
+        return {'images': self.images, 'average': self.average, 'count': self._count,
+                'numels': list(self._key) if open_ else None,
+                'bucket': self._layouts[self._key].bucket.detach().cpu().clone() if open_ else None}
+
+    def load_state_dict(self, state):
+        if int(state['images']) != self.images or bool(state['average']) != self.average:
+            raise ValueError('state of an accumulator over %d images (average=%s), this one has %d (average=%s)'
+                             % (state['images'], state['average'], self.images, self.average))
+        count = int(state['count'])
+        if not 0 <= count < self.images:
+            raise ValueError('an open window holds 0 .. %d images, got %d' % (self.images - 1, count))
+        if count == 0:
+            self.reset()
+            return
+        numels = tuple(None if n is None else int(n) for n in state['numels'])
+        if len(numels) != len(self.variables) or any(n is not None and n != v.numel() for n, v in zip(numels, self.variables)):
+            raise ValueError('the state does not match the variable list')
+        lay = self._layout(numels)
+        if state['bucket'].numel() != lay.bucket.numel():
+            raise ValueError('a bucket of %d elements, the layout has %d' % (state['bucket'].numel(), lay.bucket.numel()))
+        lay.bucket.copy_(state['bucket'])
+        self._key, self._count = numels, count
+
+
+CHECKPOINT_PREFIX = 'model.ckpt'
+
+
+def checkpoint_path(directory, global_step):
+    """train.py:157: <directory>/model.ckpt-<global_step>"""
+    import os
+    return os.path.join(directory, '%s-%d' % (CHECKPOINT_PREFIX, int(global_step)))
+
+
+def latest_checkpoint(directory):
+    """tf.train.latest_checkpoint for the files Trainer.save writes: the model.ckpt-<step> of the HIGHEST step (as a number: 100
+    after 10 after 9), None when the directory holds none"""
+    import os
+    import re
+    if directory is None or not os.path.isdir(directory):
+        return None
+    best = None
+    for name in os.listdir(directory):
+        m = re.fullmatch(re.escape(CHECKPOINT_PREFIX) + r'-(\d+)', name)
+        if m and (best is None or int(m.group(1)) > best[0]):
+            best = (int(m.group(1)), os.path.join(directory, name))
+    return None if best is None else best[1]
+
+
+class Trainer:
+    """The single-process counterpart of scripts/train.py:77-202: train_one_epoch and train around a caller model (model.dense
+    holds the parameters), with an optimizer step every `images_per_step` images on the images' mean gradient
+    (GradientAccumulator) and a state that resumes a run exactly: the parameters, the optimizer's slots and step, the number of
+    images seen -- which is the Philox image id of the target samplers and the dropout -- and the open window.
+    weight_decay: None, or the L2 coefficient of l2_variables.  The image summaries and TensorBoard are not built."""
+
+    LOG_FORMAT = 'steps %d, lr is %.5f, loss: %.4f, %.4f, %.4f, %.4f, %.4f, %.4f'           # train.py:150
+
+    def __init__(self, model, optimizer, images_per_step=1, learning_rate_bias_double=False, weight_decay=None):
+        self.model, self.optimizer = model, optimizer
+        self.learning_rate_bias_double = bool(learning_rate_bias_double)
+        self.named = model_variables(model.dense)
+        self.weight_decays = None if weight_decay is None else l2_variables(model.dense, weight_decay)
+        self.accumulator = GradientAccumulator([p for _, p in self.named], images_per_step)
+        self.images_seen = 0
+        self.l2_loss = None           # of the last optimizer step's pre-update values (a device tensor), with weight_decay
+
+    def step(self, inputs):
+        """inputs: (image, gt_bboxes, gt_labels) of ONE image.  Returns (the image's four losses as detached device tensors,
+        whether the optimizer stepped)."""
+        m = self.model
+        image_id = self.images_seen
+        m._anchor_target._next_image_id = image_id
+        m._proposal_target._next_image_id = image_id
+        if hasattr(m, '_next_dropout_image_id'):
+            m._next_dropout_image_id = image_id
+        losses = m(inputs, True)
+        sum(losses).backward()
+        gradients = self.accumulator.add([p.grad for _, p in self.named])
+        for _, p in self.named:
+            p.grad = None
+        self.images_seen += 1
+        if gradients is not None:
+            out = train_step(self.named, gradients, self.optimizer, learning_rate_bias_double=self.learning_rate_bias_double,
+                             weight_decays=self.weight_decays, l2=self.weight_decays is not None)
+            if out is not None:
+                self.l2_loss = out.l2_loss
+        return tuple(x.detach() for x in losses), gradients is not None
+
+    # ---- state ------------------------------------------------------------------------------------------------------------------
+    def global_step(self):
+        """the optimizer's step count as a Python int (a host read)"""
+        return int(self.optimizer.global_step)
+
+    def state_dict(self):
+        return {'model': self.model.dense.state_dict(), 'optimizer': self.optimizer.state_dict(),
+                'images_seen': self.images_seen, 'accumulator': self.accumulator.state_dict()}
+
+    def load_state_dict(self, state):
+        self.model.dense.load_state_dict(state['model'])
+        self.optimizer.load_state_dict(state['optimizer'])
+        self.images_seen = int(state['images_seen'])
+        self.accumulator.load_state_dict(state['accumulator'])
+
+    def save(self, directory):
+        """writes <directory>/model.ckpt-<global_step> and returns its path"""
+        import os
+        os.makedirs(directory, exist_ok=True)
+        path = checkpoint_path(directory, self.global_step())
+        torch.save(self.state_dict(), path)
+        return path
+
+    def restore(self, path):
+        self.load_state_dict(torch.load(path, map_location='cpu'))
+
+    # ---- the loop ---------------------------------------------------------------------------------------------------------------
+    def train_one_epoch(self, dataset, logging_every_n_steps=20, save_every_n_steps=5000, save_path=None):
+        """train.py:77-159 over an iterable of (image, gt_bboxes, gt_labels); idx counts images, as the reference's does"""
+        idx = 0
+        for inputs in dataset:
+            losses, _ = self.step(inputs)
+            if idx % logging_every_n_steps == 0:
+                four = [float(x) for x in losses]
+                l2 = 0.0 if self.l2_loss is None else float(self.l2_loss)
+                lr = learning_rate_at(self.optimizer._schedule, self.global_step())
+                print(self.LOG_FORMAT % ((idx + 1, lr) + tuple(four) + (l2, sum(four) + l2)), flush=True)
+            if save_path is not None and idx % save_every_n_steps == 0 and idx != 0:
+                self.save(save_path)
+            idx += 1
+
+    def train(self, dataset, epochs, ckpt_dir, restore_ckpt_file_path=None, logging_every_n_steps=20, save_every_n_steps=5000):
+        """train.py:162-202: the explicit checkpoint file first, then the directory's latest checkpoint (which therefore wins),
+        then `epochs` passes over the dataset"""
+        import time
+        if restore_ckpt_file_path is not None:
+            self.restore(restore_ckpt_file_path)
+        latest = latest_checkpoint(ckpt_dir)
+        if latest is not None:
+            self.restore(latest)
+        for i in range(int(epochs)):
+            print('epoch %d starting...' % (i + 1), flush=True)
+            start = time.time()
+            self.train_one_epoch(dataset, logging_every_n_steps, save_every_n_steps, ckpt_dir)
+            print('epoch %d training finished, costing %d seconds...' % (i + 1, time.time() - start), flush=True)
