@@ -48,7 +48,8 @@ extern "C" {
  * the ResNet-C4 head's global average pooling (odet_global_avg_pool_f32, odet_global_avg_pool_backward_f32) and the
  * data-parallel gradient exchange (odet_bucket_pack_f32, odet_bucket_unpack_f32, odet_rank_mean_f32) and the FPN stem's
  * max-pooling backward (odet_relu_maxpool3_backward_f32) and the K-image step's accumulate launch
- * (odet_bucket_accumulate_f32); no
+ * (odet_bucket_accumulate_f32) and the RoI pooling over a dense batch of images (odet_roi_pool_images,
+ * odet_roi_pool_argmax_images, odet_roi_pool_backward_images, odet_roi_pool_backward_images_plan); no
  * existing struct or signature changed.  One documented order did: from
  * 4096 rows on, odet_dense_wgrad_f32 adds db in 256 running sums per column, not 4 (its own comment; below 4096 rows every bit is
  * as before). */
@@ -1452,6 +1453,40 @@ int odet_roi_pool_argmax(const odet_level_t* levels, int num_levels, int C, cons
 int odet_roi_pool_backward(const odet_level_t* levels, int num_levels, int C, const float* rois, const int32_t* roi_level, int n,
                            const int32_t* count_dev, int norm_mode, int image_h, int image_w, int pool_size, int pool_mode,
                            const float* dy, const uint8_t* sel, odet_stream_t stream);
+
+/* ---- RoI pooling over a batch of images, float32 (added within 103) -------------------------------------------------
+ * B images in one call, dense and strided: levels[i].data = the base of a contiguous [B,H,W,C] tensor (the maps; for the
+ * backward, dx); rois [B,n,4]; roi_level int32 [B,n] (nullable with one level); count_dev int32 [B] (nullable: every image has
+ * n RoIs); out / dy float32 [B,n,P,P,C]; sel uint8 [B,n,P,P,C].  The images share the level shapes, n, P, the modes and the
+ * image shape; image offsets are size_t, and the 2 GiB limit of a level holds per image.  Image b's out, sel and dx are, bit
+ * for bit, what odet_roi_pool, odet_roi_pool_argmax and odet_roi_pool_backward give on image b alone (the order of sums
+ * above, per image).
+ *   odet_roi_pool_images: the forward's own batched launch, ODET_MAX_BATCH (8) images per launch -- ceil(B / 8) launches.
+ *   odet_roi_pool_argmax_images: ONE launch, a wave per (image, RoI, output row); rows at or beyond count_dev[b] get 4.
+ *   odet_roi_pool_backward_images: ONE launch of B x the single-image call's workgroups, the image the slowest index; a
+ *     workgroup walks the RoIs of its own image only (r < count_dev[b]), so its serial depth does not grow with B.  Every
+ *     element of every image's dx is written once, also where count_dev[b] == 0 (zeros).
+ *   odet_roi_pool_backward_images_plan: host only, no device call -- the launch odet_roi_pool_backward_images makes for these
+ *     shapes (levels[i].H / W; data and stride are not looked at): *grid = B * *tiles_per_image workgroups of one wave,
+ *     tiles_per_image = the sum over levels of H * ceil(W / 32) * ceil(C / 256), level_start[num_levels] = the first workgroup
+ *     of each level among an image's, *slices = ceil(C / 256), *lds_bytes = min(Wmax, 32) * min(C, 256) * 4 <= 32768.  The
+ *     launcher sizes its launch with the same code.
+ * Errors, all before any HIP call: those of the single-image entry points with the same rules (alignment: of the base
+ * pointers; C % 4 == 0 keeps every image's offset 16-byte aligned; odet_roi_pool_images also wants out 16-byte aligned), and
+ * ODET_E_INVALID for B < 1, ODET_E_LIMIT for B > 64 and for a grid of 2^31 workgroups or more.  n == 0: the forward and argmax
+ * are no-ops, the backward writes zeros.  No allocation, no host read (graph-capturable). */
+int odet_roi_pool_images(const odet_level_t* levels, int num_levels, int C, int B, const float* rois, const int32_t* roi_level,
+                         int n, const int32_t* count_dev, int norm_mode, int image_h, int image_w, int pool_size, int pool_mode,
+                         float* out, odet_stream_t stream);
+int odet_roi_pool_argmax_images(const odet_level_t* levels, int num_levels, int C, int B, const float* rois,
+                                const int32_t* roi_level, int n, const int32_t* count_dev, int norm_mode, int image_h, int image_w,
+                                int pool_size, uint8_t* sel, odet_stream_t stream);
+int odet_roi_pool_backward_images(const odet_level_t* levels, int num_levels, int C, int B, const float* rois,
+                                  const int32_t* roi_level, int n, const int32_t* count_dev, int norm_mode, int image_h,
+                                  int image_w, int pool_size, int pool_mode, const float* dy, const uint8_t* sel,
+                                  odet_stream_t stream);
+int odet_roi_pool_backward_images_plan(const odet_level_t* levels, int num_levels, int C, int B, int n, int pool_size, int* grid,
+                                       int* tiles_per_image, int* level_start, int* slices, int* lds_bytes);
 
 #ifdef __cplusplus
 }

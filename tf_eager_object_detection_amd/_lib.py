@@ -257,6 +257,10 @@ SIGNATURES = {
                                   _vp]),
     'odet_roi_pool_argmax': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
     'odet_roi_pool_backward': (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'odet_roi_pool_images': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'odet_roi_pool_argmax_images': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    'odet_roi_pool_backward_images': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'odet_roi_pool_backward_images_plan': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

@@ -5,13 +5,16 @@ sampling + the 2x2 max / avg pool, without materialising the [R,14,14,C] crops.
 
 `trainable=True` (a constructor argument of the layers, a keyword of the functions; default False = the plain path): when the
 feature map requires a gradient the call goes through ops.roi_pool_trainable -- the same forward bits, and a graph whose
-backward is odet_roi_pool_backward into the map (float32 only; the RoIs get none, as the reference stops it: roi_pooling.py:78)."""
+backward is odet_roi_pool_backward into the map (float32 only; the RoIs get none, as the reference stops it: roi_pooling.py:78).
+
+`roi_pooling_images` is the same for a batch of images in dense [B,...] tensors (ops.roi_pool_images and its trainable form): one
+select and one backward launch for the whole batch."""
 import torch
 
 from .. import ops
 
 __all__ = ['RoiPoolingCropAndResize', 'RoiPoolingRoiAlign', 'RoiPoolingCropAndResize2', 'crop_and_resize',
-           'roi_align', 'roi_pooling_fpn_levels']
+           'roi_align', 'roi_pooling_fpn_levels', 'roi_pooling_images']
 
 
 def _spatial_order(feature_map, rois, stride):
@@ -132,3 +135,16 @@ def roi_pooling_fpn_levels(p_list, rois_sorted, roi_level, image_shape, pool_siz
                                image_shape=image_shape, count_dev=count_dev)
     return ops.roi_pool(list(p_list), rois_sorted, roi_level, ops.ROI_NORM_IMAGE, pool_size, ops.ROI_POOL_MAX2,
                         image_shape=image_shape, count_dev=count_dev, out=out)
+
+
+def roi_pooling_images(maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None, image_shape=None, count_dev=None,
+                       trainable=False):
+    """Native addition: the pooling of B images at once.  maps = one float32 [B,H,W,C] tensor per level, rois [B,n,4], roi_level
+    int32 [B,n] (None with one level), count_dev int32 [B] (None: n RoIs in every image) -> [B,n,P,P,C]; image b is what the
+    single-image layers give on image b, bit for bit.  With norm_mode=ROI_NORM_IMAGE, pool_mode=ROI_POOL_MAX2 and per-image
+    level-sorted RoIs this is roi_pooling_fpn_levels for a batch.  ``trainable`` as everywhere in this module."""
+    kw = dict(strides=strides, image_shape=image_shape, count_dev=count_dev)
+    if _wants_grad(trainable, maps):
+        with torch.enable_grad():
+            return ops.roi_pool_trainable_images(list(maps), rois, roi_level, norm_mode, pool_size, pool_mode, **kw)
+    return ops.roi_pool_images(list(maps), rois, roi_level, norm_mode, pool_size, pool_mode, **kw)

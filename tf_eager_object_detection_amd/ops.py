@@ -1860,9 +1860,10 @@ ROI_GRAD_MAX_ROIS = 8192       # odet_roi_pool_argmax / odet_roi_pool_backward: 
 ROI_GRAD_MAX_POOL = 16
 
 
-def _roi_grad_levels(who, maps_or_shapes, strides, device, alloc):
+def _roi_grad_levels(who, maps_or_shapes, strides, device, alloc, batch=1):
     """the level table of the RoI backward: `maps_or_shapes` = float32 NHWC GPU tensors [1,H,W,C] (the maps, or dx buffers to
-    write) or shapes (1,H,W,C) (alloc: buffers are made) -> (levels, tensors, C)"""
+    write) or shapes (1,H,W,C) (alloc: buffers are made) -> (levels, tensors, C).  `batch` = B of the *_images calls: every map
+    is [B,H,W,C]."""
     nl = len(maps_or_shapes)
     if nl < 1 or nl > MAX_LEVELS:
         raise ValueError('%s: between 1 and %d feature maps expected' % (who, MAX_LEVELS))
@@ -1875,8 +1876,11 @@ def _roi_grad_levels(who, maps_or_shapes, strides, device, alloc):
             fm = torch.empty(tuple(int(v) for v in fm), dtype=torch.float32, device=device)
         if fm.dtype != torch.float32:
             raise ValueError('%s: feature maps must be float32 (the RoI backward has no float16 form), got %s' % (who, fm.dtype))
-        if fm.dim() != 4 or fm.shape[0] != 1:
+        if fm.dim() != 4 or (batch == 1 and fm.shape[0] != 1):
             raise ValueError('%s: feature map must be NHWC with batch 1, got %s' % (who, tuple(fm.shape)))
+        if int(fm.shape[0]) != batch:
+            raise L.OdetError('%s: the maps, the RoIs and dy of a call must share the batch size (%d), got a map of shape %s'
+                              % (who, batch, tuple(fm.shape)))
         if not fm.is_cuda:
             raise L.OdetError('%s: shared_layers must live on the GPU: tf_eager_object_detection_amd has no CPU path' % who)
         if not fm.is_contiguous():
@@ -1992,6 +1996,151 @@ def roi_pool_trainable(feature_maps, rois, roi_level, norm_mode, pool_size, pool
     cfg = (int(norm_mode), int(pool_size), int(pool_mode), None if strides is None else tuple(float(s) for s in strides),
            None if image_shape is None else (int(image_shape[0]), int(image_shape[1])))
     return _RoiPoolTrainable.apply(rois, roi_level, count_dev, cfg, *maps)
+
+
+# ---- RoI pooling over a batch of images (odet_roi_pool_*_images) -------------------------------------------------------------------
+# Dense and strided, what the batched targets and dense parts hand over: maps / dx [B,H,W,C] per level, rois [B,n,4], roi_level
+# int32 [B,n], count_dev int32 [B], features / dy / sel [B,n,P,P,C]; the images share the level shapes, n, P and the modes.  Image
+# b's results are the single-image functions' on image b alone, bit for bit; float32 only.
+ROI_IMAGES_MAX_BATCH = 64      # ODET_E_LIMIT above (TARGETS_MAX_BATCH: what one targets call produces)
+
+
+def _roi_images_rois(who, rois, roi_level, pool_size):
+    """-> (rois [B,n,4] float32, roi_level int32 [B,n] or None, B, n, P)"""
+    rois = L.f32c(rois, 'rois')
+    if rois.dim() != 3 or rois.shape[2] != 4:
+        raise ValueError('%s: rois must have shape [B,n,4], got %s' % (who, tuple(rois.shape)))
+    B, n = int(rois.shape[0]), int(rois.shape[1])
+    if roi_level is not None:
+        if roi_level.dtype != torch.int32:
+            roi_level = roi_level.to(torch.int32)
+        if tuple(roi_level.shape) != (B, n):
+            raise L.OdetError('%s: roi_level must have shape [B,n] = %s, got %s' % (who, (B, n), tuple(roi_level.shape)))
+    return rois, roi_level, B, n, int(pool_size)
+
+
+def _roi_images_count(who, count_dev, B):
+    if count_dev is not None and (count_dev.dtype != torch.int32 or count_dev.numel() != B):
+        raise L.OdetError('%s: count_dev must be int32 [B] = [%d], got %s %s' % (who, B, count_dev.dtype, tuple(count_dev.shape)))
+    return count_dev
+
+
+def _roi_images_rows(who, t, name, dtype, shape):
+    if tuple(t.shape[1:]) == tuple(shape[1:]) and t.dim() == 5 and int(t.shape[0]) != shape[0]:
+        raise L.OdetError('%s: the maps, the RoIs and dy of a call must share the batch size (%d), got %s of shape %s'
+                          % (who, shape[0], name, tuple(t.shape)))
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError('%s: %s must be contiguous %s [B,n,P,P,C] = %s, got %s %s' % (who, name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+    return t
+
+
+def roi_pool_images(feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None, image_shape=None, count_dev=None,
+                    out=None):
+    """roi_pool over B images (odet_roi_pool_images): feature_maps = one float32 [B,H,W,C] GPU tensor per level, rois [B,n,4] ->
+    [B,n,P,P,C]; ceil(B / 8) launches of the forward's own batched form, image b bit-equal to roi_pool on image b."""
+    who = 'roi_pool_images'
+    _roi_grad_f32(who, feature_maps)
+    rois, roi_level, B, n, P = _roi_images_rois(who, rois, roi_level, pool_size)
+    levels, keep, Cc = _roi_grad_levels(who, list(feature_maps), strides, rois.device, alloc=False, batch=B)
+    _roi_images_count(who, count_dev, B)
+    out = _out(out, (B, n, P, P, Cc), torch.float32, rois.device)
+    ih, iw = (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
+    L.call('odet_roi_pool_images', levels, len(keep), Cc, B, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev), int(norm_mode),
+           ih, iw, P, int(pool_mode), L.dptr(out), L.stream())
+    return out
+
+
+def roi_pool_argmax_images(feature_maps, rois, roi_level, norm_mode, pool_size, strides=None, image_shape=None, count_dev=None,
+                           out=None):
+    """roi_pool_argmax over B images in one launch (odet_roi_pool_argmax_images): uint8 [B,n,P,P,C], rows at or beyond
+    count_dev[b] 4."""
+    who = 'roi_pool_argmax_images'
+    _roi_grad_f32(who, feature_maps)
+    rois, roi_level, B, n, P = _roi_images_rois(who, rois, roi_level, pool_size)
+    levels, keep, Cc = _roi_grad_levels(who, list(feature_maps), strides, rois.device, alloc=False, batch=B)
+    _roi_images_count(who, count_dev, B)
+    out = _out(out, (B, n, P, P, Cc), torch.uint8, rois.device)
+    ih, iw = (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
+    L.call('odet_roi_pool_argmax_images', levels, len(keep), Cc, B, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev),
+           int(norm_mode), ih, iw, P, L.dptr(out), L.stream())
+    return out
+
+
+def roi_pool_backward_images(dy, feature_shapes_or_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None,
+                             image_shape=None, count_dev=None, outs=None, sel=None):
+    """roi_pool_backward over B images in one launch (odet_roi_pool_backward_images): dy [B,n,P,P,C] -> list of dx, one
+    [B,H,W,C] float32 per level, every element written once (zeros for an image without RoIs); a workgroup walks the RoIs of its
+    own image only.  Arguments as roi_pool_backward, with the batched shapes."""
+    who = 'roi_pool_backward_images'
+    if not isinstance(dy, torch.Tensor) or dy.dtype != torch.float32:
+        raise ValueError('%s: dy must be a float32 tensor (the RoI backward has no float16 form)' % who)
+    _roi_grad_f32(who, feature_shapes_or_maps if outs is None else outs)
+    if (int(pool_mode) == ROI_POOL_MAX2) != (sel is not None):
+        raise ValueError('%s: sel (roi_pool_argmax_images) is required for ROI_POOL_MAX2 and goes with no other pool_mode' % who)
+    rois, roi_level, B, n, P = _roi_images_rois(who, rois, roi_level, pool_size)
+    if outs is None:
+        outs = [tuple(fm.shape) if isinstance(fm, torch.Tensor) else tuple(fm) for fm in feature_shapes_or_maps]
+    levels, dxs, Cc = _roi_grad_levels(who, list(outs), strides, rois.device, alloc=True, batch=B)
+    _roi_images_count(who, count_dev, B)
+    _roi_images_rows(who, dy, 'dy', torch.float32, (B, n, P, P, Cc))
+    if sel is not None:
+        _roi_images_rows(who, sel, 'sel', torch.uint8, (B, n, P, P, Cc))
+    ih, iw = (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
+    L.call('odet_roi_pool_backward_images', levels, len(dxs), Cc, B, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev),
+           int(norm_mode), ih, iw, P, int(pool_mode), L.dptr(dy), L.dptr(sel), L.stream())
+    return dxs
+
+
+class _RoiPoolTrainableImages(torch.autograd.Function):
+    """_RoiPoolTrainable over a batch: roi_pool_images forward (and the one select launch for ROI_POOL_MAX2); one
+    roi_pool_backward_images backward"""
+
+    @staticmethod
+    def forward(ctx, rois, roi_level, count_dev, cfg, *maps):
+        norm_mode, pool_size, pool_mode, strides, image_shape = cfg
+        out = roi_pool_images(list(maps), rois, roi_level, norm_mode, pool_size, pool_mode, strides=strides, image_shape=image_shape,
+                              count_dev=count_dev)
+        sel = None
+        if pool_mode == ROI_POOL_MAX2:
+            sel = roi_pool_argmax_images(maps, rois, roi_level, norm_mode, pool_size, strides=strides, image_shape=image_shape,
+                                         count_dev=count_dev)
+        ctx.cfg = cfg
+        ctx.shapes = [tuple(m.shape) for m in maps]
+        ctx.save_for_backward(rois, roi_level, count_dev, sel)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        rois, roi_level, count_dev, sel = ctx.saved_tensors
+        norm_mode, pool_size, pool_mode, strides, image_shape = ctx.cfg
+        dxs = roi_pool_backward_images(dy if dy.is_contiguous() else dy.contiguous(), ctx.shapes, rois, roi_level, norm_mode,
+                                       pool_size, pool_mode, strides=strides, image_shape=image_shape, count_dev=count_dev, sel=sel)
+        return (None, None, None, None) + tuple(dx if need else None for dx, need in zip(dxs, ctx.needs_input_grad[4:]))
+
+
+def roi_pool_trainable_images(feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None, image_shape=None,
+                              count_dev=None):
+    """roi_pool_images with a backward pass into the float32 maps: the forward is `roi_pool_images`, bit for bit; `.backward()` is
+    one roi_pool_backward_images and leaves a gradient on every map that requires one (None for the others).  The RoIs get no
+    gradient.  No host read anywhere: graph-capturable."""
+    maps = []
+    for fm in feature_maps:
+        if not isinstance(fm, torch.Tensor) or fm.dtype != torch.float32:
+            raise ValueError('roi_pool_trainable_images: feature maps must be float32 tensors (the RoI backward has no float16 form), '
+                             'got %s' % getattr(fm, 'dtype', type(fm).__name__))
+        maps.append(fm if fm.is_contiguous() else fm.contiguous())
+    if rois.dim() != 3 or rois.shape[2] != 4:
+        raise ValueError('roi_pool_trainable_images: rois must have shape [B,n,4], got %s' % (tuple(rois.shape),))
+    if int(rois.shape[0]) > ROI_IMAGES_MAX_BATCH or int(rois.shape[1]) > ROI_GRAD_MAX_ROIS or int(pool_size) > ROI_GRAD_MAX_POOL:
+        raise ValueError('roi_pool_trainable_images: at most %d images, %d RoIs per image and pool_size %d'
+                         % (ROI_IMAGES_MAX_BATCH, ROI_GRAD_MAX_ROIS, ROI_GRAD_MAX_POOL))
+    rois = L.f32c(rois.detach(), 'rois')
+    if roi_level is not None and roi_level.dtype != torch.int32:
+        roi_level = roi_level.to(torch.int32)
+    cfg = (int(norm_mode), int(pool_size), int(pool_mode), None if strides is None else tuple(float(s) for s in strides),
+           None if image_shape is None else (int(image_shape[0]), int(image_shape[1])))
+    return _RoiPoolTrainableImages.apply(rois, roi_level, count_dev, cfg, *maps)
 
 
 def post_ops(scores, deltas, rois, image_shape, means, stds, max_per_class, max_per_image, nms_iou_threshold,
