@@ -8,7 +8,9 @@ feature map requires a gradient the call goes through ops.roi_pool_trainable -- 
 backward is odet_roi_pool_backward into the map (float32 only; the RoIs get none, as the reference stops it: roi_pooling.py:78).
 
 `roi_pooling_images` is the same for a batch of images in dense [B,...] tensors (ops.roi_pool_images and its trainable form): one
-select and one backward launch for the whole batch."""
+select and one backward launch for the whole batch.
+
+Every entry states its modes and hands over to `_pool`, which alone decides between the trainable and the plain call."""
 import torch
 
 from .. import ops
@@ -29,14 +31,22 @@ def _spatial_order(feature_map, rois, stride):
     return ops.roi_order(rois, None, (max(1, int(round(h * float(stride)))), max(1, int(round(w * float(stride))))))
 
 
-def _wants_grad(trainable, maps):
-    return bool(trainable) and any(isinstance(m, torch.Tensor) and m.requires_grad for m in maps)
-
-
-def _pool_trainable(maps, rois, roi_level, norm_mode, pool_size, pool_mode, **kw):
-    """the trainable form records a graph whatever the caller's grad mode (the layers' forward is decorated no_grad)"""
-    with torch.enable_grad():
-        return ops.roi_pool_trainable(list(maps), rois, roi_level, norm_mode, pool_size, pool_mode, **kw)
+def _pool(trainable, maps, rois, roi_level, norm_mode, pool_size, pool_mode, order_stride=None, images=False, out=None, **kw):
+    """The one place that decides between the trainable and the plain call, for the single-image entries and (`images`) the
+    batch.  Trainable, when asked for and a map requires a gradient: no order and no `out`, and a graph is recorded whatever the
+    caller's grad mode (the layers' forward is decorated no_grad).  Plain: `order_stride` = the map's stride where the entry
+    sorts its RoIs (_spatial_order)."""
+    maps = list(maps)
+    if trainable and any(isinstance(m, torch.Tensor) and m.requires_grad for m in maps):
+        if out is not None:
+            raise ValueError('the trainable form of the RoI pooling allocates its output (out must be None)')
+        with torch.enable_grad():
+            return (ops.roi_pool_trainable_images if images else ops.roi_pool_trainable)(maps, rois, roi_level, norm_mode,
+                                                                                         pool_size, pool_mode, **kw)
+    if images:
+        return ops.roi_pool_images(maps, rois, roi_level, norm_mode, pool_size, pool_mode, **kw)
+    order = None if order_stride is None else _spatial_order(maps[0], rois, order_stride)
+    return ops.roi_pool(maps, rois, roi_level, norm_mode, pool_size, pool_mode, out=out, order=order, **kw)
 
 
 class RoiPoolingCropAndResize2(torch.nn.Module):
@@ -51,11 +61,8 @@ class RoiPoolingCropAndResize2(torch.nn.Module):
     @torch.no_grad()
     def forward(self, inputs, training=None, mask=None):
         shared_layers, rois, image_shape = inputs
-        if _wants_grad(self._trainable, [shared_layers]):
-            return _pool_trainable([shared_layers], rois, None, ops.ROI_NORM_IMAGE, self._pool_size, ops.ROI_POOL_MAX2,
-                                   image_shape=image_shape)
-        return ops.roi_pool([shared_layers], rois, None, ops.ROI_NORM_IMAGE, self._pool_size, ops.ROI_POOL_MAX2,
-                            image_shape=image_shape)
+        return _pool(self._trainable, [shared_layers], rois, None, ops.ROI_NORM_IMAGE, self._pool_size, ops.ROI_POOL_MAX2,
+                     image_shape=image_shape)
 
     call = forward
 
@@ -74,11 +81,8 @@ class RoiPoolingCropAndResize(torch.nn.Module):
     def forward(self, inputs, training=None, mask=None):
         shared_layers, rois, extractor_stride = inputs
         mode = ops.ROI_POOL_MAX2 if self._max_pooling_flag else ops.ROI_POOL_NONE
-        if _wants_grad(self._trainable, [shared_layers]):
-            return _pool_trainable([shared_layers], rois, None, ops.ROI_NORM_STRIDE, self._pool_size, mode,
-                                   strides=[float(extractor_stride)])
-        return ops.roi_pool([shared_layers], rois, None, ops.ROI_NORM_STRIDE, self._pool_size, mode,
-                            strides=[float(extractor_stride)], order=_spatial_order(shared_layers, rois, extractor_stride))
+        return _pool(self._trainable, [shared_layers], rois, None, ops.ROI_NORM_STRIDE, self._pool_size, mode,
+                     order_stride=extractor_stride, strides=[float(extractor_stride)])
 
     call = forward
 
@@ -88,19 +92,14 @@ def crop_and_resize(image, boxes, box_ind, crop_size, pad_border=True, trainable
     feature-map coordinates; ``box_ind`` must be all zeros (batch = 1, as everywhere in the
     reference: roi_pooling.py:28,66,152)."""
     assert isinstance(crop_size, int), crop_size
-    mode = ops.ROI_NORM_TP_ALIGN if pad_border else 3
-    if _wants_grad(trainable, [image]):
-        return _pool_trainable([image], boxes, None, mode, crop_size, ops.ROI_POOL_NONE, strides=[1.0])
-    return ops.roi_pool([image], boxes, None, mode, crop_size, ops.ROI_POOL_NONE, strides=[1.0],
-                        order=_spatial_order(image, boxes, 1.0))
+    return _pool(trainable, [image], boxes, None, ops.ROI_NORM_TP_ALIGN if pad_border else 3, crop_size, ops.ROI_POOL_NONE,
+                 order_stride=1.0, strides=[1.0])
 
 
 def roi_align(featuremap, boxes, resolution, trainable=False):
     """reference model/roi_pooling.py:140-155: 4 samples per bin (crop 2*resolution) + 2x2 avg."""
-    if _wants_grad(trainable, [featuremap]):
-        return _pool_trainable([featuremap], boxes, None, ops.ROI_NORM_TP_ALIGN, resolution, ops.ROI_POOL_AVG2, strides=[1.0])
-    return ops.roi_pool([featuremap], boxes, None, ops.ROI_NORM_TP_ALIGN, resolution, ops.ROI_POOL_AVG2,
-                        strides=[1.0], order=_spatial_order(featuremap, boxes, 1.0))
+    return _pool(trainable, [featuremap], boxes, None, ops.ROI_NORM_TP_ALIGN, resolution, ops.ROI_POOL_AVG2, order_stride=1.0,
+                 strides=[1.0])
 
 
 class RoiPoolingRoiAlign(torch.nn.Module):
@@ -114,12 +113,8 @@ class RoiPoolingRoiAlign(torch.nn.Module):
     @torch.no_grad()
     def forward(self, inputs, training=None, mask=None):
         shared_layers, rois, extractor_stride = inputs
-        if _wants_grad(self._trainable, [shared_layers]):
-            return _pool_trainable([shared_layers], rois, None, ops.ROI_NORM_TP_ALIGN, self._pool_size, ops.ROI_POOL_AVG2,
-                                   strides=[float(extractor_stride)])
-        return ops.roi_pool([shared_layers], rois, None, ops.ROI_NORM_TP_ALIGN, self._pool_size,
-                            ops.ROI_POOL_AVG2, strides=[float(extractor_stride)],
-                            order=_spatial_order(shared_layers, rois, extractor_stride))
+        return _pool(self._trainable, [shared_layers], rois, None, ops.ROI_NORM_TP_ALIGN, self._pool_size, ops.ROI_POOL_AVG2,
+                     order_stride=extractor_stride, strides=[float(extractor_stride)])
 
     call = forward
 
@@ -128,13 +123,8 @@ def roi_pooling_fpn_levels(p_list, rois_sorted, roi_level, image_shape, pool_siz
     """Native addition: what reference model/fpn/base_fpn_model.py:152-161 (_get_roi_features)
     does with one RoiPoolingCropAndResize2 call per non-empty level + concat, as ONE launch over
     the level-sorted RoIs (``roi_level`` = 0-based level of each row)."""
-    if _wants_grad(trainable, p_list):
-        if out is not None:
-            raise ValueError('roi_pooling_fpn_levels: the trainable form allocates its output (out must be None)')
-        return _pool_trainable(p_list, rois_sorted, roi_level, ops.ROI_NORM_IMAGE, pool_size, ops.ROI_POOL_MAX2,
-                               image_shape=image_shape, count_dev=count_dev)
-    return ops.roi_pool(list(p_list), rois_sorted, roi_level, ops.ROI_NORM_IMAGE, pool_size, ops.ROI_POOL_MAX2,
-                        image_shape=image_shape, count_dev=count_dev, out=out)
+    return _pool(trainable, p_list, rois_sorted, roi_level, ops.ROI_NORM_IMAGE, pool_size, ops.ROI_POOL_MAX2,
+                 image_shape=image_shape, count_dev=count_dev, out=out)
 
 
 def roi_pooling_images(maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None, image_shape=None, count_dev=None,
@@ -143,8 +133,5 @@ def roi_pooling_images(maps, rois, roi_level, norm_mode, pool_size, pool_mode, s
     int32 [B,n] (None with one level), count_dev int32 [B] (None: n RoIs in every image) -> [B,n,P,P,C]; image b is what the
     single-image layers give on image b, bit for bit.  With norm_mode=ROI_NORM_IMAGE, pool_mode=ROI_POOL_MAX2 and per-image
     level-sorted RoIs this is roi_pooling_fpn_levels for a batch.  ``trainable`` as everywhere in this module."""
-    kw = dict(strides=strides, image_shape=image_shape, count_dev=count_dev)
-    if _wants_grad(trainable, maps):
-        with torch.enable_grad():
-            return ops.roi_pool_trainable_images(list(maps), rois, roi_level, norm_mode, pool_size, pool_mode, **kw)
-    return ops.roi_pool_images(list(maps), rois, roi_level, norm_mode, pool_size, pool_mode, **kw)
+    return _pool(trainable, maps, rois, roi_level, norm_mode, pool_size, pool_mode, images=True, strides=strides,
+                 image_shape=image_shape, count_dev=count_dev)

@@ -1796,132 +1796,200 @@ def roi_order(rois, roi_level, image_shape, count_dev=None, out=None):
     return out
 
 
-def roi_pool(feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None, image_shape=None,
-             count_dev=None, out=None, events=None, order=None):
-    """feature_maps: list of NHWC float32 GPU tensors [1,H,W,C] (one per level).  ``events`` = (start, stop)
-    ProfEvent pair attached to the dispatch (profiling); ``order`` = int32 processing order (roi_order)."""
-    rois = _boxes(rois, 'rois')
-    n = rois.shape[0]
-    nl = len(feature_maps)
-    if nl < 1 or nl > MAX_LEVELS:
-        raise ValueError('between 1 and %d feature maps expected' % MAX_LEVELS)
-    levels = (L.OdetLevel * nl)()
-    keep = []
-    Cc = None
-    f16 = all(isinstance(fm, torch.Tensor) and fm.dtype == torch.float16 for fm in feature_maps)
-    for i, fm in enumerate(feature_maps):
-        if f16:
-            if not fm.is_cuda:
-                raise L.OdetError('shared_layers must live on the GPU: tf_eager_object_detection_amd has no CPU path')
-            fm = fm.contiguous()
-        else:
-            fm = L.f32c(fm, 'shared_layers')
-        if fm.dim() != 4 or fm.shape[0] != 1:
-            raise ValueError('feature map must be NHWC with batch 1, got %s' % (tuple(fm.shape),))
-        if Cc is None:
-            Cc = fm.shape[3]
-        elif fm.shape[3] != Cc:
-            raise ValueError('all levels must share the channel count')
-        keep.append(fm)
-        levels[i].data = fm.data_ptr()
-        levels[i].H = fm.shape[1]
-        levels[i].W = fm.shape[2]
-        levels[i].stride = float(strides[i]) if strides is not None else 0.0
-    P = int(pool_size)
-    if out is None:
-        out = torch.empty((n, P, P, Cc), dtype=torch.float16 if f16 else torch.float32, device=rois.device)
-    ih, iw = (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
-    if roi_level is not None and roi_level.dtype != torch.int32:
-        roi_level = roi_level.to(torch.int32)
-    if f16:
-        if out.dtype != torch.float16:
-            raise TypeError('out must be float16 for float16 feature maps')
-        args = (levels, nl, Cc, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev),
-                L.dptr(order, torch.int32, 'order') if order is not None else None, int(norm_mode), ih, iw, P,
-                int(pool_mode), C.c_void_p(out.data_ptr()), L.stream())
-        if events is None:
-            L.call('odet_roi_pool_f16', *args)
-        else:
-            L.call('odet_roi_pool_f16_timed', *(args + (events[0].handle, events[1].handle)))
-    elif order is not None:
-        L.call('odet_roi_pool_ordered', levels, nl, Cc, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev),
-               L.dptr(order, torch.int32, 'order'), int(norm_mode), ih, iw, P, int(pool_mode), L.dptr(out), L.stream(),
-               events[0].handle if events else None, events[1].handle if events else None)
-    elif events is None:
-        L.call('odet_roi_pool', levels, nl, Cc, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev),
-               int(norm_mode), ih, iw, P, int(pool_mode), L.dptr(out), L.stream())
-    else:
-        L.call('odet_roi_pool_timed', levels, nl, Cc, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev),
-               int(norm_mode), ih, iw, P, int(pool_mode), L.dptr(out), L.stream(), events[0].handle, events[1].handle)
-    return out
-
-
 ROI_GRAD_MAX_ROIS = 8192       # odet_roi_pool_argmax / odet_roi_pool_backward: ODET_E_LIMIT above
 ROI_GRAD_MAX_POOL = 16
+ROI_IMAGES_MAX_BATCH = 64      # ODET_E_LIMIT above (TARGETS_MAX_BATCH: what one targets call produces)
+
+# The two forms of every RoI operation.  One image: maps / dx [1,H,W,C] per level, rois [n,4], roi_level int32 [n], count_dev
+# int32 [1], features / dy / sel [n,P,P,C].  A batch of images (odet_roi_pool_*_images), dense and strided, what the batched targets
+# and dense parts hand over: the same with a leading B; the images share the level shapes, n, P and the modes, and image b's results
+# are the single-image functions' on image b alone, bit for bit; float32 only.  A form names its three C symbols (a function's
+# `who` in error texts is its symbol without 'odet_'); everything else that differs hangs on `batched`.
+_RoiForm = collections.namedtuple('_RoiForm', 'batched pool argmax backward')
+_ROI_ONE = _RoiForm(False, 'odet_roi_pool', 'odet_roi_pool_argmax', 'odet_roi_pool_backward')
+_ROI_IMAGES = _RoiForm(True, 'odet_roi_pool_images', 'odet_roi_pool_argmax_images', 'odet_roi_pool_backward_images')
 
 
-def _roi_grad_levels(who, maps_or_shapes, strides, device, alloc, batch=1):
-    """the level table of the RoI backward: `maps_or_shapes` = float32 NHWC GPU tensors [1,H,W,C] (the maps, or dx buffers to
-    write) or shapes (1,H,W,C) (alloc: buffers are made) -> (levels, tensors, C).  `batch` = B of the *_images calls: every map
-    is [B,H,W,C]."""
+def _roi_image_shape(image_shape):
+    return (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
+
+
+def _roi_f32(who, what, tensors, strict=False):
+    """the float32 rule of the gradient forms, asked before anything needs a device; shapes pass unless `strict`"""
+    for t in tensors:
+        if getattr(t, 'dtype', None if strict else torch.float32) != torch.float32:
+            raise ValueError('%s: %s must be float32 tensors (the RoI backward has no float16 form), got %s'
+                             % (who, what, getattr(t, 'dtype', type(t).__name__)))
+
+
+def _roi_rois(form, who, rois, roi_level, pool_size):
+    """the RoI front -> (float32 rois [n,4] or [B,n,4], roi_level int32 of the leading shape or None, the leading shape (n,) or
+    (B, n), P)"""
+    if form.batched:
+        rois = L.f32c(rois, 'rois')
+        if rois.dim() != 3 or rois.shape[2] != 4:
+            raise ValueError('%s: rois must have shape [B,n,4], got %s' % (who, tuple(rois.shape)))
+    else:
+        rois = _boxes(rois, 'rois')
+    lead = tuple(rois.shape[:-1])
+    if roi_level is not None:
+        if roi_level.dtype != torch.int32:
+            roi_level = roi_level.to(torch.int32)
+        if form.batched and tuple(roi_level.shape) != lead:
+            raise L.OdetError('%s: roi_level must have shape [B,n] = %s, got %s' % (who, lead, tuple(roi_level.shape)))
+    return rois, roi_level, lead, int(pool_size)
+
+
+def _roi_levels(who, maps_or_shapes, strides, device=None, alloc=False, batch=1, forward=False):
+    """the level table of every RoI call -> (levels, tensors, C).  `maps_or_shapes` = NHWC GPU tensors [batch,H,W,C], one per
+    level.  The gradient forms take contiguous float32 tensors (the maps, or dx buffers to write; _roi_f32 has been asked) or,
+    with `alloc`, shapes: buffers are made on `device`.  `forward`: float16 maps stay when every map is float16, anything else is
+    cast (L.f32c)."""
     nl = len(maps_or_shapes)
     if nl < 1 or nl > MAX_LEVELS:
         raise ValueError('%s: between 1 and %d feature maps expected' % (who, MAX_LEVELS))
     levels = (L.OdetLevel * nl)()
     keep, Cc = [], None
+    f16 = forward and all(isinstance(fm, torch.Tensor) and fm.dtype == torch.float16 for fm in maps_or_shapes)
     for i, fm in enumerate(maps_or_shapes):
-        if not isinstance(fm, torch.Tensor):
+        if f16 and fm.is_cuda:
+            fm = fm.contiguous()
+        elif forward:                                                    # (a float16 map on the CPU is refused here as well)
+            fm = L.f32c(fm, 'shared_layers')
+        elif not isinstance(fm, torch.Tensor):
             if not alloc:
                 raise TypeError('%s: feature maps must be tensors' % who)
             fm = torch.empty(tuple(int(v) for v in fm), dtype=torch.float32, device=device)
-        if fm.dtype != torch.float32:
-            raise ValueError('%s: feature maps must be float32 (the RoI backward has no float16 form), got %s' % (who, fm.dtype))
-        if fm.dim() != 4 or (batch == 1 and fm.shape[0] != 1):
-            raise ValueError('%s: feature map must be NHWC with batch 1, got %s' % (who, tuple(fm.shape)))
-        if int(fm.shape[0]) != batch:
+        shape = tuple(fm.shape)
+        if len(shape) != 4 or (batch == 1 and shape[0] != 1):
+            raise ValueError('%s: feature map must be NHWC with batch 1, got %s' % (who, shape))
+        if shape[0] != batch:
             raise L.OdetError('%s: the maps, the RoIs and dy of a call must share the batch size (%d), got a map of shape %s'
-                              % (who, batch, tuple(fm.shape)))
+                              % (who, batch, shape))
         if not fm.is_cuda:
             raise L.OdetError('%s: shared_layers must live on the GPU: tf_eager_object_detection_amd has no CPU path' % who)
         if not fm.is_contiguous():
             raise ValueError('%s: feature maps must be contiguous' % who)
         if Cc is None:
-            Cc = int(fm.shape[3])
-        elif int(fm.shape[3]) != Cc:
+            Cc = shape[3]
+        elif shape[3] != Cc:
             raise ValueError('%s: all levels must share the channel count' % who)
         keep.append(fm)
-        levels[i].data = fm.data_ptr()
-        levels[i].H = fm.shape[1]
-        levels[i].W = fm.shape[2]
-        levels[i].stride = float(strides[i]) if strides is not None else 0.0
+        lv = levels[i]
+        lv.data, lv.H, lv.W, lv.stride = fm.data_ptr(), shape[1], shape[2], float(strides[i]) if strides is not None else 0.0
     return levels, keep, Cc
 
 
-def _roi_grad_f32(who, maps):
-    for fm in maps:
-        if isinstance(fm, torch.Tensor) and fm.dtype != torch.float32:
-            raise ValueError('%s: feature maps must be float32 (the RoI backward has no float16 form), got %s' % (who, fm.dtype))
+def _roi_images_count(who, count_dev, B):
+    if count_dev is not None and (count_dev.dtype != torch.int32 or count_dev.numel() != B):
+        raise L.OdetError('%s: count_dev must be int32 [B] = [%d], got %s %s' % (who, B, count_dev.dtype, tuple(count_dev.shape)))
 
 
-def _roi_grad_rois(who, rois, roi_level, pool_size):
-    rois = _boxes(rois, 'rois')
-    if roi_level is not None and roi_level.dtype != torch.int32:
-        roi_level = roi_level.to(torch.int32)
-    return rois, roi_level, int(rois.shape[0]), int(pool_size)
+def _roi_rows(who, t, name, dtype, shape):
+    """dy or sel: a contiguous `dtype` tensor of `shape` = [n,P,P,C] or [B,n,P,P,C]"""
+    if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+        if t.dim() == 5 and tuple(t.shape[1:]) == shape[1:] and t.shape[0] != shape[0]:
+            raise L.OdetError('%s: the maps, the RoIs and dy of a call must share the batch size (%d), got %s of shape %s'
+                              % (who, shape[0], name, tuple(t.shape)))
+        raise ValueError('%s: %s must be contiguous %s %s = %s, got %s %s'
+                         % (who, name, dtype, '[B,n,P,P,C]' if len(shape) == 5 else '[n,P,P,C]', shape, t.dtype, tuple(t.shape)))
+
+
+def roi_pool(feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None, image_shape=None,
+             count_dev=None, out=None, events=None, order=None):
+    """feature_maps: list of NHWC float32 GPU tensors [1,H,W,C] (one per level).  ``events`` = (start, stop)
+    ProfEvent pair attached to the dispatch (profiling); ``order`` = int32 processing order (roi_order)."""
+    rois, roi_level, (n,), P = _roi_rois(_ROI_ONE, 'roi_pool', rois, roi_level, pool_size)
+    levels, keep, Cc = _roi_levels('roi_pool', feature_maps, strides, forward=True)
+    f16 = keep[0].dtype == torch.float16
+    if out is None:
+        out = torch.empty((n, P, P, Cc), dtype=keep[0].dtype, device=rois.device)
+    elif f16 and out.dtype != torch.float16:
+        raise TypeError('out must be float16 for float16 feature maps')
+    ih, iw = _roi_image_shape(image_shape)
+    head = (levels, len(keep), Cc, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev))
+    tail = (int(norm_mode), ih, iw, P, int(pool_mode), C.c_void_p(out.data_ptr()) if f16 else L.dptr(out), L.stream())
+    timed = (events[0].handle, events[1].handle) if events else ()
+    if f16 or order is not None:
+        head += (L.dptr(order, torch.int32, 'order') if order is not None else None,)
+    if f16:
+        L.call('odet_roi_pool_f16_timed' if timed else 'odet_roi_pool_f16', *(head + tail + timed))
+    elif order is not None:
+        L.call('odet_roi_pool_ordered', *(head + tail + (timed or (None, None))))
+    else:
+        L.call('odet_roi_pool_timed' if timed else 'odet_roi_pool', *(head + tail + timed))
+    return out
+
+
+def _roi_pool_rows(form, pool_mode, select, feature_maps, rois, roi_level, norm_mode, pool_size, strides, image_shape, count_dev,
+                   out=None, sel=None):
+    """The launches of a form over float32 maps that fill rows, on one level table and one set of pointers -> (out, sel): the
+    forward (`pool_mode` not None: form.pool, float32 rows into `out`) and / or the select (`select`: form.argmax, uint8 rows into
+    `sel`), in this order."""
+    who = (form.argmax if pool_mode is None else form.pool)[5:]
+    _roi_f32(who, 'feature maps', feature_maps)
+    rois, roi_level, lead, P = _roi_rois(form, who, rois, roi_level, pool_size)
+    levels, keep, Cc = _roi_levels(who, list(feature_maps), strides, batch=lead[0] if form.batched else 1)
+    if form.batched:
+        _roi_images_count(who, count_dev, lead[0])
+    ih, iw = _roi_image_shape(image_shape)
+    args = (levels, len(keep), Cc) + lead[:-1] + (L.dptr(rois), L.dptr(roi_level), lead[-1], L.dptr(count_dev), int(norm_mode),
+                                                   ih, iw, P)
+    stream = L.stream()
+    if pool_mode is not None:
+        out = _out(out, lead + (P, P, Cc), torch.float32, rois.device)
+        L.call(form.pool, *args, int(pool_mode), L.dptr(out), stream)
+    if select:
+        sel = _out(sel, lead + (P, P, Cc), torch.uint8, rois.device)
+        L.call(form.argmax, *args, L.dptr(sel), stream)
+    return out, sel
 
 
 def roi_pool_argmax(feature_maps, rois, roi_level, norm_mode, pool_size, strides=None, image_shape=None, count_dev=None,
                     out=None):
     """Which sample of each 2x2 bin roi_pool(..., ROI_POOL_MAX2) took (odet_roi_pool_argmax): uint8 [n,P,P,C], 0..3 = 2*di+dj
     (the first sample equal to the pooled value), 4 = none.  float32 maps only."""
-    _roi_grad_f32('roi_pool_argmax', feature_maps)
-    rois, roi_level, n, P = _roi_grad_rois('roi_pool_argmax', rois, roi_level, pool_size)
-    levels, keep, Cc = _roi_grad_levels('roi_pool_argmax', list(feature_maps), strides, rois.device, alloc=False)
-    out = _out(out, (n, P, P, Cc), torch.uint8, rois.device)
-    ih, iw = (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
-    L.call('odet_roi_pool_argmax', levels, len(keep), Cc, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev), int(norm_mode),
-           ih, iw, P, L.dptr(out), L.stream())
-    return out
+    return _roi_pool_rows(_ROI_ONE, None, True, feature_maps, rois, roi_level, norm_mode, pool_size, strides, image_shape, count_dev,
+                          sel=out)[1]
+
+
+def roi_pool_images(feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None, image_shape=None, count_dev=None,
+                    out=None):
+    """roi_pool over B images (odet_roi_pool_images): feature_maps = one float32 [B,H,W,C] GPU tensor per level, rois [B,n,4] ->
+    [B,n,P,P,C]; ceil(B / 8) launches of the forward's own batched form, image b bit-equal to roi_pool on image b."""
+    return _roi_pool_rows(_ROI_IMAGES, int(pool_mode), False, feature_maps, rois, roi_level, norm_mode, pool_size, strides,
+                          image_shape, count_dev, out=out)[0]
+
+
+def roi_pool_argmax_images(feature_maps, rois, roi_level, norm_mode, pool_size, strides=None, image_shape=None, count_dev=None,
+                           out=None):
+    """roi_pool_argmax over B images in one launch (odet_roi_pool_argmax_images): uint8 [B,n,P,P,C], rows at or beyond
+    count_dev[b] 4."""
+    return _roi_pool_rows(_ROI_IMAGES, None, True, feature_maps, rois, roi_level, norm_mode, pool_size, strides, image_shape,
+                          count_dev, sel=out)[1]
+
+
+def _roi_pool_backward(form, dy, feature_shapes_or_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides, image_shape,
+                       count_dev, outs, sel):
+    who = form.backward[5:]
+    _roi_f32(who, 'dy', [dy], strict=True)
+    _roi_f32(who, 'feature maps', feature_shapes_or_maps if outs is None else outs)
+    if (int(pool_mode) == ROI_POOL_MAX2) != (sel is not None):
+        raise ValueError('%s: sel (%s) is required for ROI_POOL_MAX2 and goes with no other pool_mode' % (who, form.argmax[5:]))
+    rois, roi_level, lead, P = _roi_rois(form, who, rois, roi_level, pool_size)
+    if outs is None:
+        outs = [tuple(fm.shape) if isinstance(fm, torch.Tensor) else tuple(fm) for fm in feature_shapes_or_maps]
+    levels, dxs, Cc = _roi_levels(who, list(outs), strides, rois.device, alloc=True, batch=lead[0] if form.batched else 1)
+    if form.batched:
+        _roi_images_count(who, count_dev, lead[0])
+    rows = lead + (P, P, Cc)
+    _roi_rows(who, dy, 'dy', torch.float32, rows)
+    if sel is not None:
+        _roi_rows(who, sel, 'sel', torch.uint8, rows)
+    ih, iw = _roi_image_shape(image_shape)
+    L.call(form.backward, levels, len(dxs), Cc, *lead[:-1], L.dptr(rois), L.dptr(roi_level), lead[-1], L.dptr(count_dev),
+           int(norm_mode), ih, iw, P, int(pool_mode), L.dptr(dy), L.dptr(sel), L.stream())
+    return dxs
 
 
 def roi_pool_backward(dy, feature_shapes_or_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None,
@@ -1930,140 +1998,8 @@ def roi_pool_backward(dy, feature_shapes_or_maps, rois, roi_level, norm_mode, po
     [1,H,W,C] float32 per level, every element written once in an order fixed by the data's indices (bit-reproducible).
     `feature_shapes_or_maps`: the maps (only their shapes are used) or their shapes; `sel`: roi_pool_argmax's output, required
     for ROI_POOL_MAX2 and refused otherwise; `outs`: buffers to write instead of new ones."""
-    who = 'roi_pool_backward'
-    if not isinstance(dy, torch.Tensor) or dy.dtype != torch.float32:
-        raise ValueError('%s: dy must be a float32 tensor (the RoI backward has no float16 form)' % who)
-    _roi_grad_f32(who, feature_shapes_or_maps if outs is None else outs)
-    if (int(pool_mode) == ROI_POOL_MAX2) != (sel is not None):
-        raise ValueError('%s: sel (roi_pool_argmax) is required for ROI_POOL_MAX2 and goes with no other pool_mode' % who)
-    rois, roi_level, n, P = _roi_grad_rois(who, rois, roi_level, pool_size)
-    if outs is None:
-        outs = [tuple(fm.shape) if isinstance(fm, torch.Tensor) else tuple(fm) for fm in feature_shapes_or_maps]
-    levels, dxs, Cc = _roi_grad_levels(who, list(outs), strides, rois.device, alloc=True)
-    if tuple(dy.shape) != (n, P, P, Cc) or not dy.is_contiguous():
-        raise ValueError('%s: dy must be contiguous [n,P,P,C] = %s, got %s' % (who, (n, P, P, Cc), tuple(dy.shape)))
-    if sel is not None and (sel.dtype != torch.uint8 or tuple(sel.shape) != (n, P, P, Cc) or not sel.is_contiguous()):
-        raise ValueError('%s: sel must be contiguous uint8 [n,P,P,C]' % who)
-    ih, iw = (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
-    L.call('odet_roi_pool_backward', levels, len(dxs), Cc, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev), int(norm_mode),
-           ih, iw, P, int(pool_mode), L.dptr(dy), L.dptr(sel), L.stream())
-    return dxs
-
-
-class _RoiPoolTrainable(torch.autograd.Function):
-    """ops.roi_pool forward (and, for ROI_POOL_MAX2, the select launch while the maps are warm); one roi_pool_backward backward"""
-
-    @staticmethod
-    def forward(ctx, rois, roi_level, count_dev, cfg, *maps):
-        norm_mode, pool_size, pool_mode, strides, image_shape = cfg
-        out = roi_pool(list(maps), rois, roi_level, norm_mode, pool_size, pool_mode, strides=strides, image_shape=image_shape,
-                       count_dev=count_dev)
-        sel = None
-        if pool_mode == ROI_POOL_MAX2:
-            sel = roi_pool_argmax(maps, rois, roi_level, norm_mode, pool_size, strides=strides, image_shape=image_shape,
-                                  count_dev=count_dev)
-        ctx.cfg = cfg
-        ctx.shapes = [tuple(m.shape) for m in maps]
-        ctx.save_for_backward(rois, roi_level, count_dev, sel)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, dy):
-        rois, roi_level, count_dev, sel = ctx.saved_tensors
-        norm_mode, pool_size, pool_mode, strides, image_shape = ctx.cfg
-        dxs = roi_pool_backward(dy if dy.is_contiguous() else dy.contiguous(), ctx.shapes, rois, roi_level, norm_mode, pool_size,
-                                pool_mode, strides=strides, image_shape=image_shape, count_dev=count_dev, sel=sel)
-        return (None, None, None, None) + tuple(dx if need else None for dx, need in zip(dxs, ctx.needs_input_grad[4:]))
-
-
-def roi_pool_trainable(feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None, image_shape=None,
-                       count_dev=None):
-    """ops.roi_pool with a backward pass into the float32 maps: the forward is `roi_pool`, bit for bit; `.backward()` is one
-    roi_pool_backward and leaves a gradient on every map that requires one (None for the others).  The RoIs get no gradient
-    (the reference stops it: roi_pooling.py:78)."""
-    maps = []
-    for fm in feature_maps:
-        if not isinstance(fm, torch.Tensor) or fm.dtype != torch.float32:
-            raise ValueError('roi_pool_trainable: feature maps must be float32 tensors (the RoI backward has no float16 form), got %s'
-                             % getattr(fm, 'dtype', type(fm).__name__))
-        maps.append(fm if fm.is_contiguous() else fm.contiguous())
-    if int(rois.shape[0]) > ROI_GRAD_MAX_ROIS or int(pool_size) > ROI_GRAD_MAX_POOL:
-        raise ValueError('roi_pool_trainable: at most %d RoIs and pool_size %d' % (ROI_GRAD_MAX_ROIS, ROI_GRAD_MAX_POOL))
-    rois = _boxes(rois.detach(), 'rois')
-    if roi_level is not None and roi_level.dtype != torch.int32:
-        roi_level = roi_level.to(torch.int32)
-    cfg = (int(norm_mode), int(pool_size), int(pool_mode), None if strides is None else tuple(float(s) for s in strides),
-           None if image_shape is None else (int(image_shape[0]), int(image_shape[1])))
-    return _RoiPoolTrainable.apply(rois, roi_level, count_dev, cfg, *maps)
-
-
-# ---- RoI pooling over a batch of images (odet_roi_pool_*_images) -------------------------------------------------------------------
-# Dense and strided, what the batched targets and dense parts hand over: maps / dx [B,H,W,C] per level, rois [B,n,4], roi_level
-# int32 [B,n], count_dev int32 [B], features / dy / sel [B,n,P,P,C]; the images share the level shapes, n, P and the modes.  Image
-# b's results are the single-image functions' on image b alone, bit for bit; float32 only.
-ROI_IMAGES_MAX_BATCH = 64      # ODET_E_LIMIT above (TARGETS_MAX_BATCH: what one targets call produces)
-
-
-def _roi_images_rois(who, rois, roi_level, pool_size):
-    """-> (rois [B,n,4] float32, roi_level int32 [B,n] or None, B, n, P)"""
-    rois = L.f32c(rois, 'rois')
-    if rois.dim() != 3 or rois.shape[2] != 4:
-        raise ValueError('%s: rois must have shape [B,n,4], got %s' % (who, tuple(rois.shape)))
-    B, n = int(rois.shape[0]), int(rois.shape[1])
-    if roi_level is not None:
-        if roi_level.dtype != torch.int32:
-            roi_level = roi_level.to(torch.int32)
-        if tuple(roi_level.shape) != (B, n):
-            raise L.OdetError('%s: roi_level must have shape [B,n] = %s, got %s' % (who, (B, n), tuple(roi_level.shape)))
-    return rois, roi_level, B, n, int(pool_size)
-
-
-def _roi_images_count(who, count_dev, B):
-    if count_dev is not None and (count_dev.dtype != torch.int32 or count_dev.numel() != B):
-        raise L.OdetError('%s: count_dev must be int32 [B] = [%d], got %s %s' % (who, B, count_dev.dtype, tuple(count_dev.shape)))
-    return count_dev
-
-
-def _roi_images_rows(who, t, name, dtype, shape):
-    if tuple(t.shape[1:]) == tuple(shape[1:]) and t.dim() == 5 and int(t.shape[0]) != shape[0]:
-        raise L.OdetError('%s: the maps, the RoIs and dy of a call must share the batch size (%d), got %s of shape %s'
-                          % (who, shape[0], name, tuple(t.shape)))
-    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise ValueError('%s: %s must be contiguous %s [B,n,P,P,C] = %s, got %s %s' % (who, name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
-    return t
-
-
-def roi_pool_images(feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None, image_shape=None, count_dev=None,
-                    out=None):
-    """roi_pool over B images (odet_roi_pool_images): feature_maps = one float32 [B,H,W,C] GPU tensor per level, rois [B,n,4] ->
-    [B,n,P,P,C]; ceil(B / 8) launches of the forward's own batched form, image b bit-equal to roi_pool on image b."""
-    who = 'roi_pool_images'
-    _roi_grad_f32(who, feature_maps)
-    rois, roi_level, B, n, P = _roi_images_rois(who, rois, roi_level, pool_size)
-    levels, keep, Cc = _roi_grad_levels(who, list(feature_maps), strides, rois.device, alloc=False, batch=B)
-    _roi_images_count(who, count_dev, B)
-    out = _out(out, (B, n, P, P, Cc), torch.float32, rois.device)
-    ih, iw = (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
-    L.call('odet_roi_pool_images', levels, len(keep), Cc, B, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev), int(norm_mode),
-           ih, iw, P, int(pool_mode), L.dptr(out), L.stream())
-    return out
-
-
-def roi_pool_argmax_images(feature_maps, rois, roi_level, norm_mode, pool_size, strides=None, image_shape=None, count_dev=None,
-                           out=None):
-    """roi_pool_argmax over B images in one launch (odet_roi_pool_argmax_images): uint8 [B,n,P,P,C], rows at or beyond
-    count_dev[b] 4."""
-    who = 'roi_pool_argmax_images'
-    _roi_grad_f32(who, feature_maps)
-    rois, roi_level, B, n, P = _roi_images_rois(who, rois, roi_level, pool_size)
-    levels, keep, Cc = _roi_grad_levels(who, list(feature_maps), strides, rois.device, alloc=False, batch=B)
-    _roi_images_count(who, count_dev, B)
-    out = _out(out, (B, n, P, P, Cc), torch.uint8, rois.device)
-    ih, iw = (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
-    L.call('odet_roi_pool_argmax_images', levels, len(keep), Cc, B, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev),
-           int(norm_mode), ih, iw, P, L.dptr(out), L.stream())
-    return out
+    return _roi_pool_backward(_ROI_ONE, dy, feature_shapes_or_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides,
+                              image_shape, count_dev, outs, sel)
 
 
 def roi_pool_backward_images(dy, feature_shapes_or_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None,
@@ -2071,39 +2007,20 @@ def roi_pool_backward_images(dy, feature_shapes_or_maps, rois, roi_level, norm_m
     """roi_pool_backward over B images in one launch (odet_roi_pool_backward_images): dy [B,n,P,P,C] -> list of dx, one
     [B,H,W,C] float32 per level, every element written once (zeros for an image without RoIs); a workgroup walks the RoIs of its
     own image only.  Arguments as roi_pool_backward, with the batched shapes."""
-    who = 'roi_pool_backward_images'
-    if not isinstance(dy, torch.Tensor) or dy.dtype != torch.float32:
-        raise ValueError('%s: dy must be a float32 tensor (the RoI backward has no float16 form)' % who)
-    _roi_grad_f32(who, feature_shapes_or_maps if outs is None else outs)
-    if (int(pool_mode) == ROI_POOL_MAX2) != (sel is not None):
-        raise ValueError('%s: sel (roi_pool_argmax_images) is required for ROI_POOL_MAX2 and goes with no other pool_mode' % who)
-    rois, roi_level, B, n, P = _roi_images_rois(who, rois, roi_level, pool_size)
-    if outs is None:
-        outs = [tuple(fm.shape) if isinstance(fm, torch.Tensor) else tuple(fm) for fm in feature_shapes_or_maps]
-    levels, dxs, Cc = _roi_grad_levels(who, list(outs), strides, rois.device, alloc=True, batch=B)
-    _roi_images_count(who, count_dev, B)
-    _roi_images_rows(who, dy, 'dy', torch.float32, (B, n, P, P, Cc))
-    if sel is not None:
-        _roi_images_rows(who, sel, 'sel', torch.uint8, (B, n, P, P, Cc))
-    ih, iw = (0, 0) if image_shape is None else (int(image_shape[0]), int(image_shape[1]))
-    L.call('odet_roi_pool_backward_images', levels, len(dxs), Cc, B, L.dptr(rois), L.dptr(roi_level), n, L.dptr(count_dev),
-           int(norm_mode), ih, iw, P, int(pool_mode), L.dptr(dy), L.dptr(sel), L.stream())
-    return dxs
+    return _roi_pool_backward(_ROI_IMAGES, dy, feature_shapes_or_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides,
+                              image_shape, count_dev, outs, sel)
 
 
-class _RoiPoolTrainableImages(torch.autograd.Function):
-    """_RoiPoolTrainable over a batch: roi_pool_images forward (and the one select launch for ROI_POOL_MAX2); one
-    roi_pool_backward_images backward"""
+class _RoiPoolTrainable(torch.autograd.Function):
+    """cfg[0] = the form.  The form's forward launch (over float32 maps form.pool is what roi_pool / roi_pool_images call) and,
+    for ROI_POOL_MAX2, its select launch while the maps are warm, on one level table; one backward launch of the form.  Both go
+    straight to the bodies behind the public functions, not through the names ops.roi_pool_argmax* / ops.roi_pool_backward*."""
 
     @staticmethod
     def forward(ctx, rois, roi_level, count_dev, cfg, *maps):
-        norm_mode, pool_size, pool_mode, strides, image_shape = cfg
-        out = roi_pool_images(list(maps), rois, roi_level, norm_mode, pool_size, pool_mode, strides=strides, image_shape=image_shape,
-                              count_dev=count_dev)
-        sel = None
-        if pool_mode == ROI_POOL_MAX2:
-            sel = roi_pool_argmax_images(maps, rois, roi_level, norm_mode, pool_size, strides=strides, image_shape=image_shape,
-                                         count_dev=count_dev)
+        form, norm_mode, pool_size, pool_mode, strides, image_shape = cfg
+        out, sel = _roi_pool_rows(form, pool_mode, pool_mode == ROI_POOL_MAX2, maps, rois, roi_level, norm_mode, pool_size, strides,
+                                  image_shape, count_dev)
         ctx.cfg = cfg
         ctx.shapes = [tuple(m.shape) for m in maps]
         ctx.save_for_backward(rois, roi_level, count_dev, sel)
@@ -2113,10 +2030,36 @@ class _RoiPoolTrainableImages(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
         rois, roi_level, count_dev, sel = ctx.saved_tensors
-        norm_mode, pool_size, pool_mode, strides, image_shape = ctx.cfg
-        dxs = roi_pool_backward_images(dy if dy.is_contiguous() else dy.contiguous(), ctx.shapes, rois, roi_level, norm_mode,
-                                       pool_size, pool_mode, strides=strides, image_shape=image_shape, count_dev=count_dev, sel=sel)
+        form, norm_mode, pool_size, pool_mode, strides, image_shape = ctx.cfg
+        dxs = _roi_pool_backward(form, dy if dy.is_contiguous() else dy.contiguous(), ctx.shapes, rois, roi_level, norm_mode,
+                                 pool_size, pool_mode, strides, image_shape, count_dev, None, sel)
         return (None, None, None, None) + tuple(dx if need else None for dx, need in zip(dxs, ctx.needs_input_grad[4:]))
+
+
+def _roi_pool_trainable(form, feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides, image_shape, count_dev):
+    who = 'roi_pool_trainable_images' if form.batched else 'roi_pool_trainable'
+    _roi_f32(who, 'feature maps', feature_maps, strict=True)
+    maps = [fm if fm.is_contiguous() else fm.contiguous() for fm in feature_maps]
+    if form.batched:                                                     # (the limits come before anything asks for a device)
+        if rois.dim() != 3 or rois.shape[2] != 4:
+            raise ValueError('%s: rois must have shape [B,n,4], got %s' % (who, tuple(rois.shape)))
+        if int(rois.shape[0]) > ROI_IMAGES_MAX_BATCH or int(rois.shape[1]) > ROI_GRAD_MAX_ROIS or int(pool_size) > ROI_GRAD_MAX_POOL:
+            raise ValueError('%s: at most %d images, %d RoIs per image and pool_size %d'
+                             % (who, ROI_IMAGES_MAX_BATCH, ROI_GRAD_MAX_ROIS, ROI_GRAD_MAX_POOL))
+    elif int(rois.shape[0]) > ROI_GRAD_MAX_ROIS or int(pool_size) > ROI_GRAD_MAX_POOL:
+        raise ValueError('%s: at most %d RoIs and pool_size %d' % (who, ROI_GRAD_MAX_ROIS, ROI_GRAD_MAX_POOL))
+    cfg = (form, int(norm_mode), int(pool_size), int(pool_mode), None if strides is None else tuple(float(s) for s in strides),
+           None if image_shape is None else _roi_image_shape(image_shape))
+    return _RoiPoolTrainable.apply(rois.detach() if rois.requires_grad else rois, roi_level, count_dev, cfg, *maps)
+
+
+def roi_pool_trainable(feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None, image_shape=None,
+                       count_dev=None):
+    """ops.roi_pool with a backward pass into the float32 maps: the forward is `roi_pool`, bit for bit; `.backward()` is one
+    roi_pool_backward and leaves a gradient on every map that requires one (None for the others).  The RoIs get no gradient
+    (the reference stops it: roi_pooling.py:78)."""
+    return _roi_pool_trainable(_ROI_ONE, feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides, image_shape,
+                               count_dev)
 
 
 def roi_pool_trainable_images(feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides=None, image_shape=None,
@@ -2124,23 +2067,8 @@ def roi_pool_trainable_images(feature_maps, rois, roi_level, norm_mode, pool_siz
     """roi_pool_images with a backward pass into the float32 maps: the forward is `roi_pool_images`, bit for bit; `.backward()` is
     one roi_pool_backward_images and leaves a gradient on every map that requires one (None for the others).  The RoIs get no
     gradient.  No host read anywhere: graph-capturable."""
-    maps = []
-    for fm in feature_maps:
-        if not isinstance(fm, torch.Tensor) or fm.dtype != torch.float32:
-            raise ValueError('roi_pool_trainable_images: feature maps must be float32 tensors (the RoI backward has no float16 form), '
-                             'got %s' % getattr(fm, 'dtype', type(fm).__name__))
-        maps.append(fm if fm.is_contiguous() else fm.contiguous())
-    if rois.dim() != 3 or rois.shape[2] != 4:
-        raise ValueError('roi_pool_trainable_images: rois must have shape [B,n,4], got %s' % (tuple(rois.shape),))
-    if int(rois.shape[0]) > ROI_IMAGES_MAX_BATCH or int(rois.shape[1]) > ROI_GRAD_MAX_ROIS or int(pool_size) > ROI_GRAD_MAX_POOL:
-        raise ValueError('roi_pool_trainable_images: at most %d images, %d RoIs per image and pool_size %d'
-                         % (ROI_IMAGES_MAX_BATCH, ROI_GRAD_MAX_ROIS, ROI_GRAD_MAX_POOL))
-    rois = L.f32c(rois.detach(), 'rois')
-    if roi_level is not None and roi_level.dtype != torch.int32:
-        roi_level = roi_level.to(torch.int32)
-    cfg = (int(norm_mode), int(pool_size), int(pool_mode), None if strides is None else tuple(float(s) for s in strides),
-           None if image_shape is None else (int(image_shape[0]), int(image_shape[1])))
-    return _RoiPoolTrainableImages.apply(rois, roi_level, count_dev, cfg, *maps)
+    return _roi_pool_trainable(_ROI_IMAGES, feature_maps, rois, roi_level, norm_mode, pool_size, pool_mode, strides, image_shape,
+                               count_dev)
 
 
 def post_ops(scores, deltas, rois, image_shape, means, stds, max_per_class, max_per_image, nms_iou_threshold,
