@@ -405,8 +405,8 @@ def pointwise_f32(ops, x, w, bias, residual, relu, stride):
     B, H, W = (int(v) for v in x.shape[:3])
     cout = int(w.shape[0])
     out = torch.empty((B, (H + stride - 1) // stride, (W + stride - 1) // stride, cout), dtype=torch.float32, device=x.device)
-    form, sym, wp, extra = ops._f32_sym('odet_pointwise_%s', w, w)
-    ops._f32_call(form, sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None,
+    ws, sym, wp, extra = ops._f32_sym('odet_pointwise_%s', w, w)
+    ops._f32_call(ws, sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None,
                   L.dptr(residual) if residual is not None else None, L.dptr(out), B, H, W, stride, cin, cout, 1 if relu else 0,
                   *extra, L.stream())
     return out

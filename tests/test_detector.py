@@ -1764,6 +1764,125 @@ def test_caller_object_on_two_limbs_repeats_an_out_of_range_pass():
 
 
 @pytest.mark.gpu
+def test_range_report_survives_a_workspace_reset_and_is_latched_behind_unchecked_launches():
+    """ops.X3Workspace's rules (tests/test_f32_forms_host.py walks them on a CPU workspace) with the word written by the kernel:
+    the launch that is known to report; reset() zeroes the tickets and keeps the word; passed() behind mark_unchecked() clears the
+    word and keeps the report for range_ok(), once"""
+    from tf_eager_object_detection_amd import ops
+    g = torch.Generator(device='cuda'); g.manual_seed(5)
+    x = torch.rand((1, 24, 32, 64), device='cuda', generator=g)
+    x[0, 11, 17, 5] = 70000.0                             # the only value beyond 65504
+    w = -torch.rand((128, 64), device='cuda', generator=g) - 0.01
+    b = torch.zeros(128, device='cuda')
+    ws = ops.X3Workspace(x.device)
+
+    def launch():
+        with ops.f32_form('x2', workspace=ws):
+            ops.pointwise(x, w, b, None, True)
+    launch()
+    ws.reset()
+    assert int(ws.range_flag().item()) == 1
+    ws.mark_unchecked()
+    assert not ws.passed() and int(ws.range_flag().item()) == 0
+    assert not ws.range_ok()
+    assert ws.range_ok()
+    launch()                                             # no mark: the checked pass's own report, nothing for the caller
+    assert not ws.passed() and ws.range_ok()
+
+
+@pytest.fixture(scope='module')
+def x2_range_case():
+    """the detector that is known to overflow on `big`, as its three-limb twin `a` sees the ordinary image: (a's state dict, img,
+    big, a(img), a.im_detect(img, 1.0)) -- computed once, shared by the tests below and left unchanged"""
+    torch.manual_seed(1)
+    a = _x2_range_detector('x3')
+    rng = np.random.default_rng(1)
+    img = torch.from_numpy((rng.uniform(0, 255, (1, 256, 352, 3)) - 110).astype(np.float32)).cuda()
+    out = [tuple(t.clone() for t in o) for o in a(img)]
+    return a.state_dict(), img, img * 3000.0, out, a.im_detect(img, 1.0)
+
+
+def _x2_range_detector(form, state=None):
+    from tf_eager_object_detection_amd.model.fpn_detector import ResNetFpnDetector
+    m = ResNetFpnDetector(50, 21, (256, 352), 300, dtype=torch.float32, max_batch=1, blind_chunks=3, f32_form=form)
+    if state is not None:
+        m.load_state_dict(state)
+    return m.prepare()
+
+
+def _same_detections(got, want):
+    """per image (boxes, labels, scores, count): the same count and the same rows below it, bit for bit"""
+    assert len(got) == len(want)
+    for x, y in zip(got, want):
+        n = int(y[3].item())
+        assert n > 0 and int(x[3].item()) == n
+        assert torch.equal(x[0][:n], y[0][:n]) and torch.equal(x[1][:n], y[1][:n]) and torch.equal(x[2][:n], y[2][:n])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('entry', ['forward', 'im_detect'])
+def test_unchecked_two_limb_overflow_stays_reported_behind_a_checked_pass(entry, x2_range_case):
+    """an unchecked pass (check_nms = False) goes out of float16's range; the next checked forward() / im_detect
+    finds the word set, cannot call it its own, runs again on three limbs (the three-limb twin's results bit for bit: harmless)
+    -- and the instance's range_ok() still says False, once"""
+    state, img, big, want_out, want_eval = x2_range_case
+    b = _x2_range_detector('x2', state)
+    b.check_nms = False
+    b(big)
+    b.check_nms = True
+    if entry == 'forward':
+        _same_detections(b(img), want_out)
+    else:
+        got = b.im_detect(img, 1.0)
+        assert len(got) == len(want_eval) and all(torch.equal(u, v) for x, y in zip(got, want_eval) for u, v in zip(x, y))
+    assert b.range_reruns == 1 and b.f32_form == 'x2'
+    assert not b.range_ok()
+    assert b.range_ok()
+
+
+@pytest.mark.gpu
+def test_graph_replay_overflow_stays_reported_behind_im_detect(x2_range_case):
+    """ADVICE r6 #1 for a captured graph: a replay goes out of range, im_detect reads (and clears) the word; run.range_ok() says
+    False once all the same; a replay inside the range reports nothing"""
+    state, img, big, _, want_eval = x2_range_case
+    b = _x2_range_detector('x2', state)
+    run = b.capture(1)
+    b(big)                                               # (the captured pass launched nothing: this checked pass's report is
+    assert b.range_reruns == 1 and run.range_ok()        # its own -- repeated, and no alarm for the caller)
+    run(big)
+    got = b.im_detect(img, 1.0)
+    assert all(torch.equal(u, v) for x, y in zip(got, want_eval) for u, v in zip(x, y))
+    assert not run.range_ok()
+    assert run.range_ok()
+    run(img)
+    assert run.range_ok()
+
+
+@pytest.mark.gpu
+def test_graph_recover_reruns_from_the_captured_pass(monkeypatch, x2_range_case):
+    """run.recover() starts from the tensors of the CAPTURED pass.  An eager checked pass on another image between
+    two replays replaces the instance's _last_pass and releases its maps; a replay flagged afterwards is still re-run from its
+    own RPN outputs: the exact proposal stage gives what the complete sync-free one gave"""
+    state, img, _, _, _ = x2_range_case
+    b = _x2_range_detector('x2', state)
+    run = b.capture(1)
+    want = [tuple(t.clone() for t in o) for o in run(img)]
+    b(torch.flip(img, dims=(2,)))
+    assert b._last_pass[2] is None
+    out = run(img)
+    real, answers = b.incomplete, [[0]]
+    monkeypatch.setattr(b, 'incomplete', lambda batch=None: answers.pop() if answers else real(batch))
+    reruns = b.nms_reruns
+    assert run.recover() == [0] and not answers
+    torch.cuda.synchronize()
+    assert b.nms_reruns == reruns + 1
+    hot = b._hot[0]
+    _same_detections([(hot.det_boxes, hot.det_labels, hot.det_scores, hot.det_count)], want)
+    _same_detections(out, want)
+    assert run.range_ok() and b.range_reruns == 0
+
+
+@pytest.mark.gpu
 def test_float16_detections_of_one_image_do_not_depend_on_the_batch_beyond_rounding():
     """the float16 bottleneck route depends on the batch (the fused 3x3 + 1x1 tail from 200 slabs on, two launches
     below: another accumulation order before the one float16 rounding), so one image's low bits -- and NMS / top-k ties with

@@ -50,17 +50,13 @@ def _in_f32_form(method):
 
 
 def _x3_workspace_of(model):
-    """the split-precision workspace (split-K tickets / parts, the two-limb form's range status word) a detector instance OWNS:
-    every launch of the instance -- eager on any stream, or replayed from a graph captured on a side stream -- uses this one, so
-    a graph never shares tickets with another instance's graph and range_ok() always reads the word its own launches set.
-    One instance's passes must not run concurrently with each other (they share every activation buffer anyway)."""
+    """the ops.X3Workspace (split-K tickets / parts, the two-limb form's range status word) a detector instance OWNS, on its
+    parameters' device (moved to another GPU: a new one there).  Every launch of the instance, eager on any stream or replayed from
+    a graph, uses it (range_ok() reads its own launches' word), so one instance's passes must not run concurrently with each other."""
+    dev = next(model.parameters()).device
     ws = model.__dict__.get('_x3_ws')
-    if ws is None:
-        dev = next(model.parameters()).device
-        if dev.type != 'cuda':
-            return None
-        ws = ops.X3Workspace(dev)
-        model.__dict__['_x3_ws'] = ws
+    if dev.type == 'cuda' and (ws is None or ws.buf.device != dev):      # (off the GPU nothing launches: none is made)
+        ws = model.__dict__['_x3_ws'] = ops.X3Workspace(dev)
     return ws
 
 
@@ -138,7 +134,7 @@ class _NmsCompleteness:
     again from the RPN head's outputs with the exact proposal stage (host-checked chunks, as many as the image needs:
     the reference's NMS is always exact, model/region_proposal.py:73-81) -- their outputs are overwritten in place, the
     other images are not touched; `nms_reruns` counts them.  Throughput loops that do not want a host sync per pass set
-    `model.check_nms = False` and call `recover()` themselves (after a graph replay too); `check_complete()` raises instead."""
+    `model.check_nms = False` and call `recover()` (on 'x2' also `range_ok()`) themselves, after a replay too; `check_complete()` raises."""
 
     check_nms = True
     nms_reruns = 0
@@ -167,20 +163,21 @@ class _NmsCompleteness:
                                'results are reported EMPTY (recover() re-runs them in the exact mode)'
                                % (bad, self._hot[0].blind_chunks))
 
-    def recover(self, batch=None):
-        """re-runs the flagged images of the last pass in the exact mode; -> their indices"""
+    def recover(self, batch=None, last_pass=None):
+        """re-runs the flagged images of the last pass (or of `last_pass`, a captured graph's) in the exact mode; -> their indices"""
         bad = self.incomplete(batch)
-        if bad and self._last_pass is None:
+        last_pass = last_pass or self._last_pass
+        if bad and last_pass is None:
             raise RuntimeError('image(s) %s incomplete and no pass to re-run them from' % bad)
         for b in bad:
-            self._rerun_exact(b)
+            self._rerun_exact(b, last_pass)
         self.nms_reruns += len(bad)
         return bad
 
-    def _rerun_exact(self, b):
-        """image b of the last pass again from the RPN head's outputs: exact proposals -> RoI features -> RoI head ->
+    def _rerun_exact(self, b, last_pass):
+        """image b of `last_pass` again from the RPN head's outputs: exact proposals -> RoI features -> RoI head ->
         post-ops, into the buffers the pass handed out"""
-        rpn_scores, rpn_deltas, maps, heads = self._last_pass
+        rpn_scores, rpn_deltas, maps, heads = last_pass
         if maps is None:
             raise RuntimeError('image %d flagged incomplete after its pass was checked and its maps released' % b)
         hot = self._hot[b]
@@ -197,12 +194,13 @@ class _NmsCompleteness:
         hot.stage_detect(cls, dlt)
 
     def _after_pass(self, batch, check):
-        """-> False if the pass has to be repeated on the three-limb form (range_ok), else True"""
+        """-> False if the pass has to be repeated on the three-limb form (its workspace's passed()), else True"""
         self._last_batch = batch
         if check is None:
             check = self.check_nms and not torch.cuda.is_current_stream_capturing()
+        x2 = getattr(self, 'f32_form', 'exact') == 'x2'
         if check:
-            if getattr(self, 'f32_form', 'exact') == 'x2' and not self.range_ok(batch):
+            if x2 and not _x3_workspace_of(self).passed():
                 return False
             self.recover(batch)
             # every image of the pass is complete: nothing is left to re-run, so the pass's pyramid (P2..P5: ~90 MB per image)
@@ -210,6 +208,8 @@ class _NmsCompleteness:
             lp = self._last_pass
             if lp is not None:
                 self._last_pass = (lp[0], lp[1], None, lp[3])
+        elif x2 and not torch.cuda.is_current_stream_capturing():      # (a pass being captured launches nothing: replays mark)
+            _x3_workspace_of(self).mark_unchecked()       # (host only: whoever checks next cannot call a set word its own)
         return True
 
     # ---- the two-limb float32 form's RANGE (f32_form = 'x2': float16 limbs).  An activation beyond float16's range becomes an
@@ -217,14 +217,16 @@ class _NmsCompleteness:
     # launch's epilogue ORs 1 into the RANGE STATUS word of the instance's workspace (include/odet.h; csrc/conv_f32_common.h) --
     # a flag, not a propagated value: a -inf that a ReLU maps to 0 is still reported.  The word is read where the NMS flags
     # are read; a pass that set it is run again on the three-limb form (bfloat16 limbs: float32's range), counted in
-    # `range_reruns`.
+    # `range_reruns`.  The word's rules are ops.X3Workspace's; this class keeps no range state of its own: a checked pass asks
+    # passed(), an unchecked one (check_nms = False, a graph replay) says mark_unchecked(), the caller asks range_ok().  What a
+    # checked pass reports about itself is not the caller's (that pass was repeated); what unchecked launches reported is, also
+    # when a checked pass or im_detect has read the word in between.
     range_reruns = 0
 
-    def range_ok(self, batch=None):
-        """True iff no two-limb launch of this instance since the last call met an activation outside float16's range (reads
-        and clears the status word: one host sync).  After replays of a capture()d graph the caller calls this itself."""
+    def range_ok(self):
+        """the caller's read: ops.X3Workspace.range_ok() of the instance's workspace (one host sync, on the current stream only)"""
         ws = self.__dict__.get('_x3_ws')
-        return True if ws is None else ws.range_ok()
+        return ws is None or ws.range_ok()                 # (no workspace: no split-precision launch yet)
 
     @contextlib.contextmanager
     def _on_three_limbs(self):
@@ -244,18 +246,18 @@ class _NmsCompleteness:
         list raises): the error is the range's if the status word is set -- then the pass is repeated, else it is the caller's."""
         if getattr(self, 'f32_form', 'exact') != 'x2':
             return fn()
-        self.range_ok()                                    # (a word left set by an earlier, unchecked pass is not this pass's)
+        ws = _x3_workspace_of(self)
         try:
             out = fn()
-            bad = not self.range_ok()
         except Exception:
-            if self.range_ok():
+            if ws is None or ws.passed():                  # (no workspace: not on the GPU, where every layer raises)
                 raise
-            bad = True
-        if bad:
-            with self._on_three_limbs():
-                out = fn()
-        return out
+        else:
+            if ws.passed():
+                return out
+        # out of range -- or the word was left by earlier unchecked launches: one needless repeat, and passed() keeps it reported
+        with self._on_three_limbs():
+            return fn()
 
     def _forward_checked(self, images_nhwc, check, run):
         """run(images) -> outputs, then the after-pass checks; a two-limb pass out of range is repeated on three limbs"""
@@ -413,9 +415,9 @@ class Detector(_NmsCompleteness, _FinalLayer, nn.Module):
         returns `run(images_nhwc) -> outputs`: the images are copied into the graph's static input and the
         graph is replayed -- a few hundred launches cost one host call, which is what a batch-1 latency
         step is bound by.  Needs the sync-free proposal stage (blind_chunks >= 1: no host check inside).
-        A replay makes NO after-pass check (no host sync): `run.recover()` re-runs images whose sync-free NMS did not complete,
-        and with f32_form = 'x2' the caller reads `run.range_ok()` (the instance's status word: False = some replay since the
-        last call met an activation outside float16's range -- run those images through forward() again)."""
+        A replay makes NO after-pass check (no host sync): `run.recover()` re-runs images whose sync-free NMS did not complete
+        (from the CAPTURED pass's tensors), and with f32_form = 'x2' the caller reads `run.range_ok()` (ops.X3Workspace.range_ok
+        of the workspace captured with: False = some replay since the last call left float16's range -- forward() those again)."""
         if not self._hot:
             raise RuntimeError('prepare() first')
         dev = next(self.parameters()).device
@@ -430,13 +432,18 @@ class Detector(_NmsCompleteness, _FinalLayer, nn.Module):
             with torch.cuda.graph(graph, stream=side):
                 static_out = self.forward(static_in)
         torch.cuda.current_stream(dev).wait_stream(side)
+        # what the graph's launches use, whatever the instance does afterwards: the workspace of the passes above (None: they
+        # made no split-precision launch, and none is allocated for them) and the captured pass's own tensors
+        ws, lp = self.__dict__.get('_x3_ws'), self._last_pass
 
         def run(images_nhwc):
             static_in.copy_(images_nhwc)
+            if ws is not None:
+                ws.mark_unchecked()                          # (host only)
             graph.replay()
             return static_out
 
         run.graph = graph
-        run.range_ok = self.range_ok
-        run.recover = lambda: self.recover(batch)
+        run.range_ok = self.range_ok if ws is None else ws.range_ok
+        run.recover = lambda: self.recover(batch, lp)
         return run

@@ -8,13 +8,16 @@ everything padded and sync-free.
 """
 import collections
 import ctypes as C
-import math
 
 import numpy as np
 import torch
 
 from . import _lib as L
-from .derived import derived, invalidate
+from .derived import invalidate
+# the float32 layers' arithmetic forms, the gradient GEMMs' form, the limb splitters and the split-precision workspace
+from .f32_forms import (  # noqa: F401
+    _F32_CTX, current_f32_form, f32_form, _GRAD_CTX, GRAD_FORMS, current_grad_form, check_grad_form, grad_form, carries_grad_form,
+    split_bf16x3, f16x2_exponent, split_f16x2, X3Workspace, _X3_WS, _x3_workspace, _F32_FORMS, _f32_sym, _f32_call)
 
 # constants of include/odet.h
 RPN_LAYOUT_FPN, RPN_LAYOUT_FRCNN = 0, 1
@@ -25,223 +28,8 @@ POSTOPS_MAX_ROIS = 4096
 POSTOPS_MAX_CANDIDATES = 8192
 MAX_LEVELS = 8
 
-# ---- the float32 layers' arithmetic form ------------------------------------------------------------------------------------
-# 'exact': v_mfma_f32_16x16x4_f32 (csrc/conv_f32.hip) -- every product and sum rounded to float32 once, a chain of fmaf.
-# 'x3':    split precision (csrc/conv_x3.hip) -- float32 operands as three bfloat16 limbs, six limb products per k on the
-#          bfloat16 matrix instructions, float32 accumulation: within float32 rounding of the float64 truth like 'exact',
-#          2.6 x its peak rate.  Same tensors in memory; only the weights get a cached companion (their limb planes).
-# 'x2':    the two-limb float16 form of the same kernel -- h + l * 2^-11 (operands to one float32 ulp), three products, half the
-#          matrix work of 'x3'; for data inside float16's RANGE (|activation| <= 65504, else infinities / NaN; include/odet.h).
-# A fixed choice of the caller (the detectors' `f32_form` argument), never a timing decision: the two forms round differently.
-# The form (and, optionally, the split-K / status workspace the launches of the block use) is AMBIENT state of the calling
-# context, held in a contextvars.ContextVar: two Python threads (or asyncio tasks) that enter and leave `f32_form` blocks in any
-# interleaving each see their own value -- a form switch is never implicit and can never leak into another thread's layers.
-import contextvars
-import functools
-
-_F32_CTX = contextvars.ContextVar('odet_f32_form', default=('exact', None))
-
-
-def current_f32_form():
-    return _F32_CTX.get()[0]
-
-
-class f32_form:
-    """with ops.f32_form('x3'): ...  -- the form the float32 conv3x3 / pointwise / dense / lateral_merge / pointwise_dual calls
-    inside the block run on.  `workspace`: an ops.X3Workspace the block's split-precision launches use (the detectors own one
-    per instance); None = the calling stream's default workspace."""
-
-    def __init__(self, form, workspace=None):
-        if form not in ('exact', 'x3', 'x2'):
-            raise ValueError("f32 form must be 'exact', 'x3' or 'x2'")
-        if workspace is not None and not isinstance(workspace, X3Workspace):
-            raise TypeError('workspace must be an ops.X3Workspace')
-        self.form, self.workspace = form, workspace
-
-    def __enter__(self):
-        self._token = _F32_CTX.set((self.form, self.workspace))
-        return self
-
-    def __exit__(self, *exc):
-        _F32_CTX.reset(self._token)
-        return False
-
-
-# ---- the gradient GEMMs' arithmetic form -------------------------------------------------------------------------------------
-# A second ambient form, beside f32_form (which the forward layers read and under which every backward front keeps refusing
-# anything but 'exact'): 'exact' runs the Dense / 3x3 gradients on v_mfma_f32_16x16x4_f32, 'x3' on three bfloat16 limbs and six
-# limb products per k (csrc/grad_gemm.h: dg_tile_x3; the 3x3 input gradient: the forward's x3 kernel on the flipped weight).
-# The bias gradients are the same ordered float32 sums in either.  A two-limb form is not offered.
-# autograd runs `backward` on a thread of its own, where a ContextVar shows its default: a torch.autograd.Function whose backward
-# reaches these ops records the form in `forward` and re-enters it in `backward` (carries_grad_form).
-_GRAD_CTX = contextvars.ContextVar('odet_grad_form', default='exact')
-GRAD_FORMS = ('exact', 'x3')
-
-
-def current_grad_form():
-    return _GRAD_CTX.get()
-
-
-def check_grad_form(form):
-    if form not in GRAD_FORMS:
-        raise ValueError("grad form must be 'exact' or 'x3', got %r" % (form,))
-    return form
-
-
-class grad_form:
-    """with ops.grad_form('x3'): ...  -- the form dense_dgrad / dense_wgrad / conv3x3_wgrad_f32_levels /
-    conv3x3_dgrad_f32_levels calls inside the block, and the backward passes of the *_trainable functions called inside it, run on."""
-
-    def __init__(self, form):
-        self.form = check_grad_form(form)
-
-    def __enter__(self):
-        self._token = _GRAD_CTX.set(self.form)
-        return self
-
-    def __exit__(self, *exc):
-        _GRAD_CTX.reset(self._token)
-        return False
-
-
-def carries_grad_form(cls):
-    """class decorator of a torch.autograd.Function whose backward reaches the gradient ops -- the ONE place that carries the
-    form across threads: forward records the caller's grad form on the node, the whole of backward runs inside it (a node that
-    no forward made has recorded none: the default, 'exact')"""
-    forward, backward = cls.forward, cls.backward
-
-    @functools.wraps(forward)
-    def record(ctx, *args):
-        ctx.grad_form = current_grad_form()
-        return forward(ctx, *args)
-
-    @functools.wraps(backward)
-    def reenter(ctx, *grads):
-        with grad_form(getattr(ctx, 'grad_form', 'exact')):
-            return backward(ctx, *grads)
-    cls.forward, cls.backward = staticmethod(record), staticmethod(reenter)
-    return cls
-
-
-def split_bf16x3(w):
-    """float32 contiguous GPU tensor (even element count) -> its three bfloat16 limb planes, int16 [3, *w.shape]
-    (odet_split_bf16x3): w == plane0 + plane1 + plane2 exactly (round to nearest even at every limb)."""
-    if w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous() or w.numel() % 2:
-        raise ValueError('split_bf16x3: needs a contiguous float32 GPU tensor with an even element count')
-    planes = torch.empty((3,) + tuple(w.shape), dtype=torch.int16, device=w.device)
-    L.call('odet_split_bf16x3', L.dptr(w), C.c_void_p(planes.data_ptr()), w.numel(), L.stream())
-    return planes
-
-
-def f16x2_exponent(w):
-    """the power of two the two-limb planes of `w` are scaled by: the largest |w| * 2^e lies in [512, 1024)"""
-    top = float(w.abs().max())
-    if not math.isfinite(top):
-        raise ValueError('split_f16x2: the weights must be finite')
-    return 0 if top == 0.0 else max(-100, min(100, 9 - math.frexp(top)[1] + 1))
-
-
-def split_f16x2(w, w_exp=None):
-    """float32 contiguous GPU tensor (even element count) -> (its two float16 limb planes of w * 2^w_exp, int16 [2, *w.shape];
-    w_exp) (odet_split_f16x2): w * 2^w_exp = plane0 + plane1 * 2^-11 to within one float32 ulp."""
-    if w.dtype != torch.float32 or not w.is_cuda or not w.is_contiguous() or w.numel() % 2:
-        raise ValueError('split_f16x2: needs a contiguous float32 GPU tensor with an even element count')
-    if w_exp is None:
-        w_exp = f16x2_exponent(w)
-    planes = torch.empty((2,) + tuple(w.shape), dtype=torch.int16, device=w.device)
-    L.call('odet_split_f16x2', L.dptr(w), C.c_void_p(planes.data_ptr()), w.numel(), int(w_exp), L.stream())
-    return planes, int(w_exp)
-
-
-class X3Workspace:
-    """The caller-owned workspace of the split-precision launches (include/odet.h): split-K ticket words (zero-filled once; every
-    launch leaves them zero), the two-limb form's RANGE STATUS word, the split-K parts.  One workspace serves launches that are
-    ordered on the device (one stream, or one captured graph replayed by one stream at a time): two launches that run
-    CONCURRENTLY must not share one -- the detectors own one per instance for that reason (a captured graph keeps using the
-    instance's, whatever stream replays it), bare `ops` calls get one per (device, stream)."""
-
-    def __init__(self, device):
-        self.buf = torch.zeros(int(L.lib().odet_x3_workspace_bytes()), dtype=torch.uint8, device=device)
-        off = int(L.lib().odet_x2_status_offset())
-        self._head = self.buf[:off + 64]
-        self._status = self.buf[off:off + 4].view(torch.int32)
-
-    def args(self):
-        return C.c_void_p(self.buf.data_ptr()), self.buf.numel()
-
-    def range_flag(self):
-        """the status word as a device tensor (int32 [1]; non-zero: a two-limb launch since the last clear saw a non-finite sum)"""
-        return self._status
-
-    def range_ok(self, clear=True):
-        """True iff no two-limb launch on this workspace since the last clear met an activation outside float16's range (one host
-        sync); clears the word when it was set"""
-        bad = int(self._status.item()) != 0
-        if bad and clear:
-            self._status.zero_()
-        return not bad
-
-    def reset(self):
-        """tickets and status back to zero (after a failed or aborted launch the tickets may be left non-zero)"""
-        self._head.zero_()
-
-
-_X3_WS = {}
-
-
-def _x3_workspace(device):
-    """the workspace of the current context: the one the enclosing f32_form block names, else the CURRENT stream's on `device`
-    (allocated at the stream's first split-precision launch -- a warm-up pass before a HIP-graph capture)"""
-    ws = _F32_CTX.get()[1]
-    if ws is not None:
-        return ws
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _X3_WS.get(key)
-    if ws is None:
-        ws = X3Workspace(device)
-        _X3_WS[key] = ws
-    return ws
-
-
 # the name DESIGN.md knows derived.invalidate by: after `.data` / set_() writes (no version bump); drops EVERY derived tensor
 invalidate_planes = invalidate
-
-
-# form -> entry-point suffix, the name a weight's limb planes are derived under, their splitter, and how the derived value reads
-# as (planes, extra arguments ahead of the workspace's)
-_F32_FORMS = {
-    'exact': ('f32', None, None, None),
-    'x3': ('x3', 'x3', split_bf16x3, lambda planes: (planes, ())),
-    'x2': ('x2', 'x2', split_f16x2, lambda planes_exp: (planes_exp[0], (planes_exp[1],))),
-}
-
-
-def _f32_sym(pattern, w, holder=None):
-    """(form, entry point, weight pointer, extra arguments before the stream) of a float32 layer in the current form: `pattern` %
-    the form's suffix.  The limb planes are derived FROM and kept ON the tensor object the caller passed (`holder`: the layer's
-    parameter, or a module's derived concatenation; `w` itself when None) until that tensor is modified (derived.py: they live
-    exactly as long as the weight they belong to -- no global cache that could outlive or be cleared under a captured HIP
-    graph); `w`, the holder's contiguous float32 view, is read only when they are built.  (split_f16x2 reads its exponent from
-    the weights -- one host synchronisation per weight tensor, at its first use: a warm-up pass before a HIP-graph capture, as
-    for the workspace)"""
-    form = _F32_CTX.get()[0]
-    sfx, name, split, read = _F32_FORMS[form]
-    if name is None:
-        return form, pattern % sfx, L.dptr(w), ()
-    holder = w if holder is None else holder
-    planes, extra = read(derived(holder, name, (holder,), lambda _: split(w)))
-    return form, pattern % sfx, C.c_void_p(planes.data_ptr()), extra + _x3_workspace(w.device).args()
-
-
-def _f32_call(form, sym, *args):
-    """L.call for a dense layer (`form`: None for float16); a split-precision launch that FAILS may leave its workspace's tickets
-    non-zero: reset them"""
-    try:
-        L.call(sym, *args)
-    except L.OdetError:
-        if form in ('x3', 'x2'):
-            _x3_workspace(torch.device('cuda', torch.cuda.current_device())).reset()
-        raise
 
 
 def _out(out, shape, dtype, device):
@@ -983,10 +771,10 @@ def _conv3x3(dtype, x, weight, bias, relu, out):
         raise ValueError('bias must be a contiguous %s [cout] tensor' % name)
     shape = (B, H, W, cout)
     out = _out(out, shape, dtype, x.device)
-    form, wp, extra = None, L.dptr(w), ()
+    ws, wp, extra = None, L.dptr(w), ()
     if dtype == torch.float32:
-        form, sym, wp, extra = _f32_sym('odet_conv3x3_%s', w, weight)
-    _f32_call(form, sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None, L.dptr(out), B, H, W,
+        ws, sym, wp, extra = _f32_sym('odet_conv3x3_%s', w, weight)
+    _f32_call(ws, sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None, L.dptr(out), B, H, W,
            cin, cout, 1 if relu else 0, *extra, L.stream())
     return out
 
@@ -1010,10 +798,10 @@ def _conv3x3_levels(dtype, xs, weight, bias, relu, outs):
         if y.dtype != dtype or tuple(y.shape) != tuple(x.shape[:3]) + (cout,) or not y.is_contiguous():
             raise ValueError('outs must be contiguous %s tensors [B,H,W,cout]' % name)
         lv[i].x, lv[i].y, lv[i].H, lv[i].W = x.data_ptr(), y.data_ptr(), int(x.shape[1]), int(x.shape[2])
-    form, sym, wp, extra = None, sym + '_levels', L.dptr(w), ()
+    ws, sym, wp, extra = None, sym + '_levels', L.dptr(w), ()
     if dtype == torch.float32:
-        form, sym, wp, extra = _f32_sym('odet_conv3x3_%s_levels', w, weight)
-    _f32_call(form, sym, lv, len(xs), wp, L.dptr(bias) if bias is not None else None, B, cin, cout,
+        ws, sym, wp, extra = _f32_sym('odet_conv3x3_%s_levels', w, weight)
+    _f32_call(ws, sym, lv, len(xs), wp, L.dptr(bias) if bias is not None else None, B, cin, cout,
            1 if relu else 0, *extra, L.stream())
     return outs
 
@@ -1253,8 +1041,8 @@ def pointwise(x, weight, bias=None, residual=None, relu=False, stride=1, out=Non
     if residual is not None and (residual.dtype != x.dtype or tuple(residual.shape) != shape or not residual.is_contiguous()):
         raise ValueError('residual must be a contiguous tensor of the output\'s dtype and shape %s' % (shape,))
     out = _out(out, shape, x.dtype, x.device)
-    form, sym, wp, extra = _f32_sym('odet_pointwise_%s', w, weight) if sfx == 'f32' else (None, 'odet_pointwise_f16', L.dptr(w), ())
-    _f32_call(form, sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None,
+    ws, sym, wp, extra = _f32_sym('odet_pointwise_%s', w, weight) if sfx == 'f32' else (None, 'odet_pointwise_f16', L.dptr(w), ())
+    _f32_call(ws, sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None,
            L.dptr(residual) if residual is not None else None, L.dptr(out), B, H, W, stride, cin, cout, 1 if relu else 0,
            *extra, L.stream())
     return out
@@ -1579,9 +1367,9 @@ def lateral_merge(x, weight, bias, top, out=None):
         raise ValueError('top must be a contiguous GPU tensor [batch, h, w, cout] of x\'s dtype')
     shape = (B, H, W, cout)
     out = _out(out, shape, x.dtype, x.device)
-    form, sym, wp, extra = _f32_sym('odet_lateral_merge_%s', w, weight) if sfx == 'f32' \
+    ws, sym, wp, extra = _f32_sym('odet_lateral_merge_%s', w, weight) if sfx == 'f32' \
         else (None, 'odet_lateral_merge_f16', L.dptr(w), ())
-    _f32_call(form, sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None, L.dptr(top),
+    _f32_call(ws, sym, L.dptr(x), wp, L.dptr(bias) if bias is not None else None, L.dptr(top),
            int(top.shape[1]), int(top.shape[2]), L.dptr(out), B, H, W, cin, cout, *extra, L.stream())
     return out
 
@@ -1611,9 +1399,9 @@ def pointwise_dual(x1, x2, weight, bias=None, stride=1, relu=True, out=None):
         raise ValueError('pointwise_dual: cin1 / cin2 must be multiples of %d, cout of 64' % gran)
     shape = (B, Ho, Wo, cout)
     out = _out(out, shape, x1.dtype, x1.device)
-    form, sym, wp, extra = _f32_sym('odet_pointwise_dual_%s', weight) if sfx == 'f32' \
+    ws, sym, wp, extra = _f32_sym('odet_pointwise_dual_%s', weight) if sfx == 'f32' \
         else (None, 'odet_pointwise_dual_f16', L.dptr(weight), ())
-    _f32_call(form, sym, L.dptr(x1), c1, L.dptr(x2), c2, H, W, stride, wp,
+    _f32_call(ws, sym, L.dptr(x1), c1, L.dptr(x2), c2, H, W, stride, wp,
            L.dptr(bias) if bias is not None else None, L.dptr(out), B, cout, 1 if relu else 0, *extra, L.stream())
     return out
 
