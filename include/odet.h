@@ -49,7 +49,8 @@ extern "C" {
  * data-parallel gradient exchange (odet_bucket_pack_f32, odet_bucket_unpack_f32, odet_rank_mean_f32) and the FPN stem's
  * max-pooling backward (odet_relu_maxpool3_backward_f32) and the K-image step's accumulate launch
  * (odet_bucket_accumulate_f32) and the RoI pooling over a dense batch of images (odet_roi_pool_images,
- * odet_roi_pool_argmax_images, odet_roi_pool_backward_images, odet_roi_pool_backward_images_plan); no
+ * odet_roi_pool_argmax_images, odet_roi_pool_backward_images, odet_roi_pool_backward_images_plan) and the FPN level
+ * assignment over a dense batch of images (odet_assign_levels_images); no
  * existing struct or signature changed.  One documented order did: from
  * 4096 rows on, odet_dense_wgrad_f32 adds db in 256 running sums per column, not 4 (its own comment; below 4096 rows every bit is
  * as before). */
@@ -225,6 +226,19 @@ int odet_frcnn_proposals(const float* rpn_logits, const float* rpn_deltas, const
 int odet_assign_levels(const float* rois, int n, const int32_t* count_dev, int min_level,
                        int max_level, float* out_rois, int32_t* out_level, int64_t* out_perm,
                        int32_t* out_counts, odet_stream_t stream);
+
+#define ODET_ASSIGN_MAX_BATCH 64     /* what one fused targets call produces */
+/* odet_assign_levels for B images in dense tensors, ONE launch (workgroup b = image b): rois [B,n,4], count_dev int32 [B]
+ * (nullable: n RoIs in every image) -> out_rois [B,n,4], out_level int32 [B,n], out_perm int64 [B,n] (rows counted INSIDE the
+ * image), out_counts int32 [B, max_level-min_level+1].  With cnt_b = min(count_dev[b], n), image b's rows [0, cnt_b) of
+ * out_rois / out_level / out_perm and out_counts[b, :] are what odet_assign_levels writes for image b alone, bit for bit;
+ * rows >= cnt_b are not written; out_counts[b, :] is always written (zeros for an empty image).  No host read, no memset
+ * (n == 0 apart: one hipMemsetAsync of the B*L counts), no atomics: graph-capturable.
+ * Errors, before any HIP call: ODET_E_INVALID (null pointer, B < 1, n < 0, bad levels), ODET_E_LIMIT (B > ODET_ASSIGN_MAX_BATCH,
+ * n > ODET_ASSIGN_MAX_ROIS). */
+int odet_assign_levels_images(const float* rois, int B, int n, const int32_t* count_dev, int min_level,
+                              int max_level, float* out_rois, int32_t* out_level, int64_t* out_perm,
+                              int32_t* out_counts, odet_stream_t stream);
 
 /* ---- RoI feature extraction ---------------------------------------------------------- */
 

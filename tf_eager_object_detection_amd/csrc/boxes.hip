@@ -439,3 +439,41 @@ extern "C" int odet_assign_levels(const float* rois, int n, const int32_t* count
   ODET_LAUNCH_CHECK();
   return ODET_OK;
 }
+
+// The same for B images in dense [B,n,...] tensors: workgroup b runs the routine above on image b's rows (found from the
+// base pointers at b * n rows), so image b's outputs are odet_assign_levels' on image b alone and perm counts rows inside
+// the image.  No atomics, no memset: out_counts[b, :] is written by image b's own workgroup, zeros when it is empty.
+__global__ void __launch_bounds__(AL_THREADS) k_assign_levels_images(const float4* __restrict__ rois, int n,
+                                                                     const int32_t* __restrict__ count_dev, int min_level,
+                                                                     int max_level, float4* __restrict__ out_rois,
+                                                                     int32_t* __restrict__ out_level,
+                                                                     int64_t* __restrict__ out_perm,
+                                                                     int32_t* __restrict__ out_counts) {
+  __shared__ int lds[ODET_MAX_LEVELS * 17];
+  const size_t b = blockIdx.x;
+  const size_t row0 = b * (size_t)n;
+  int cnt = count_dev ? min(count_dev[b], n) : n;
+  d_assign_levels_block<AL_THREADS>(rois + row0, cnt, min_level, max_level, out_rois + row0, out_level + row0,
+                                    out_perm + row0, out_counts + b * (size_t)(max_level - min_level + 1), lds);
+}
+
+extern "C" int odet_assign_levels_images(const float* rois, int B, int n, const int32_t* count_dev, int min_level,
+                                         int max_level, float* out_rois, int32_t* out_level, int64_t* out_perm,
+                                         int32_t* out_counts, odet_stream_t stream) {
+  ODET_REQUIRE(B >= 1 && n >= 0 && max_level >= min_level && max_level - min_level < ODET_MAX_LEVELS,
+               "odet_assign_levels_images: bad sizes");
+  ODET_REQUIRE(out_counts, "odet_assign_levels_images: null out_counts");
+  if (B > ODET_ASSIGN_MAX_BATCH)
+    return odet_set_error(ODET_E_LIMIT, "odet_assign_levels_images: batch %d exceeds %d", B, ODET_ASSIGN_MAX_BATCH);
+  if (n > ODET_ASSIGN_MAX_ROIS)
+    return odet_set_error(ODET_E_LIMIT, "odet_assign_levels_images: n %d exceeds %d", n, ODET_ASSIGN_MAX_ROIS);
+  if (n == 0) {
+    ODET_HIP(hipMemsetAsync(out_counts, 0, sizeof(int32_t) * (size_t)B * (max_level - min_level + 1), (hipStream_t)stream));
+    return ODET_OK;
+  }
+  ODET_REQUIRE(rois && out_rois && out_level && out_perm, "odet_assign_levels_images: null pointer");
+  hipLaunchKernelGGL(k_assign_levels_images, dim3(B), dim3(AL_THREADS), 0, (hipStream_t)stream, (const float4*)rois, n,
+                     count_dev, min_level, max_level, (float4*)out_rois, out_level, out_perm, out_counts);
+  ODET_LAUNCH_CHECK();
+  return ODET_OK;
+}

@@ -24,7 +24,10 @@ extractor runs fpn_detector's extractor_trainable outside no_grad: C2..C5 requir
 losses carry a graph into every convolution of conv2..conv5 (reference resnet_fpn.py:208-225: trainable, batch-norm frozen); the stem
 (conv1 and its pooling) stays under no_grad unless `train_stem=True` as well (which needs `train_extractor`): then it runs
 ops.stem_trainable and conv1's weight and bias receive a gradient too, as in the reference (resnet_fpn.py:233: trainable=True) --
-with all five keywords every parameter of the detector does (134 at depth 50, 236 at depth 101)."""
+with all five keywords every parameter of the detector does (134 at depth 50, 236 at depth 101).
+A training call whose inputs are a FOUR-tuple (images [B,H,W,3], gt_bboxes [sum G,4], gt_labels [sum G], gt_offsets int32 [B+1]) runs
+B images in one forward and one backward pass (`_training_batch`; training_targets = training_losses = 'hip') and returns four
+[B] tensors; with one image it is the three-tuple call, bit for bit."""
 import torch
 
 from .. import ops
@@ -32,7 +35,8 @@ from ..utils.anchor_generator import make_anchors
 from .caller_base import CallerModel, DenseParts, DenseRpnHead, _Part, _image_nhwc, _nhwc, check_train_dependencies, \
     check_training_losses, run_part
 from .detector_base import caller_range_checked, check_caller_f32_form
-from .roi_pooling import RoiPoolingCropAndResize2
+from .losses import fused_roi_losses, fused_rpn_losses
+from .roi_pooling import RoiPoolingCropAndResize2, roi_pooling_images
 from .trainable_common import check_train_flags
 
 __all__ = ['BaseFPN', 'RpnHead', 'ResnetV1Fpn']
@@ -127,16 +131,21 @@ class BaseFPN(CallerModel):
                                             stride=extractor_stride))
         return torch.cat(all_anchors, dim=0)
 
-    def _get_fpn_head_results(self, p_list):
+    def _get_fpn_head_results(self, p_list, per_image=False):
+        """per_image (the batched training call): a level's rows are [B * n_level, ...], image-major, so they are cut per image
+        BEFORE the levels are joined -- [B, n, 2] / [B, n, 4]; joining the flat rows would mix the images"""
         all_fpn_scores, all_fpn_bbox_pred = [], []
         for level_name, p in zip(self._level_name_list, p_list):
             cur_score, cur_bboxes_pred = self._rpn_head(p)
+            if per_image:
+                cur_score, cur_bboxes_pred = cur_score.reshape(p.shape[0], -1, 2), cur_bboxes_pred.reshape(p.shape[0], -1, 4)
             all_fpn_scores.append(cur_score)
             all_fpn_bbox_pred.append(cur_bboxes_pred)
-        return torch.cat(all_fpn_scores, dim=0), torch.cat(all_fpn_bbox_pred, dim=0)
+        dim = 1 if per_image else 0
+        return torch.cat(all_fpn_scores, dim=dim), torch.cat(all_fpn_bbox_pred, dim=dim)
 
     # ---- :208-220: the dense parts of the front (CallerModel._anchors_and_proposals) ------------
-    def _dense_front(self, image, image_shape, training, train):
+    def _dense_front(self, image, image_shape, training, train, per_image=False):
         # extractor: conv2..conv5 OUTSIDE no_grad with train_extractor (the stem stays inside without train_stem): C2..C5 require
         # a gradient, which the trainable neck delivers.  neck: P2..P6 require a gradient with train_neck, which the RpnHead's
         # input gradient and the trainable RoI pooling deliver.  RpnHead: the head of all levels at once with train_rpn_head, so
@@ -147,7 +156,11 @@ class BaseFPN(CallerModel):
                           lambda: self._neck(c_list, training=training))
         all_fpn_scores, all_fpn_bbox_pred = run_part(train and self._train_rpn_head,
                                                      lambda: self._get_trainable_rpn_head_results(list(p_list)),
-                                                     lambda: self._get_fpn_head_results(p_list))
+                                                     lambda: self._get_fpn_head_results(p_list, per_image))
+        if per_image:
+            # (the trainable head's rows are the [B, n, ...] outputs of all levels at once, flattened image-major: a view back)
+            B = int(image.shape[0])
+            all_fpn_scores, all_fpn_bbox_pred = all_fpn_scores.reshape(B, -1, 2), all_fpn_bbox_pred.reshape(B, -1, 4)
         with torch.no_grad():
             all_anchors = self._get_anchors(image_shape)
         return p_list, all_anchors, all_fpn_scores, all_fpn_bbox_pred
@@ -173,6 +186,78 @@ class BaseFPN(CallerModel):
             rois_list.append(srois[off:off + c])
             off += c
         return rois_list, perm[:k]
+
+    # ---- the batched training call (CallerModel._forward_images) ----------------------------------
+    _batched_training = True
+
+    def _pooling_maps(self, p_list):
+        """the maps of min_level..max_level as the batched pooling takes them: one NHWC [B,H,W,C] tensor per level"""
+        return list(p_list[:len(self._level_name_list) - 1])
+
+    def _training_batch(self, images, gt_bboxes, gt_labels, gt_offsets):
+        """B images in one forward pass: the stages of `_fused_losses` in its order, each ONE call over the batch -- except the
+        proposals, which stay `_rpn_proposal`'s exact mode image by image (the fused batched stage decodes from anchors in
+        registers and is pinned to the anchor-tensor path to 1e-4 only; its batch form runs the sync-free mode).  Image b gets
+        the sampler ids a loop over single images would give it.  Head rows stay level-sorted per image, so B = 1 does the
+        three-tuple call's arithmetic.  After the proposal calls nothing is read on the host."""
+        B = int(images.shape[0])
+        image_shape = [int(images.shape[1]), int(images.shape[2])]
+        p_list, anchors, rpn_score, rpn_deltas = self._dense_front(images, image_shape, True, True, per_image=True)
+        n = int(anchors.shape[0])
+        dev = anchors.device
+        at, pt = self._anchor_target, self._proposal_target
+        with torch.no_grad():
+            fg = self._fg_scores(rpn_score.detach()).reshape(B, n)          # (elementwise: one launch over all B n rows)
+            deltas = rpn_deltas.detach()
+            r_max = max(min(int(self._rpn_proposal._num_post_nms_train), n), 1)
+            rois = torch.zeros((B, r_max, 4), dtype=torch.float32, device=dev)
+            kept = torch.zeros((B, r_max), dtype=torch.int32, device=dev)
+            roi_counts = torch.zeros(B, dtype=torch.int32, device=dev)
+            for b in range(B):
+                self._rpn_proposal.padded((deltas[b], anchors, fg[b], image_shape), training=True,
+                                          out=(rois[b], kept[b], roi_counts[b:b + 1]))
+            anchor_targets = at.batch(gt_bboxes, gt_offsets, image_shape, anchors, first_image_id=at._next_image_id, dense=False)
+            at._next_image_id += B
+        rpn_cls_loss, rpn_reg_loss = fused_rpn_losses(rpn_score.float(), rpn_deltas.float(), anchor_targets, self._rpn_sigma,
+                                                      self._rpn_layout, self._num_anchors)
+        with torch.no_grad():
+            # (strict=False: no host read, as in _fused_losses)
+            proposal_targets = pt.batch(rois, gt_bboxes, gt_labels, gt_offsets, first_image_id=pt._next_image_id,
+                                        roi_counts=roi_counts, strict=False)
+            pt._next_image_id += B
+            # all S rows of every image, as the single-image path: levels, stable partition, the rows' target rows -- no host
+            # read of the level counts, no Python list per level
+            sorted_rois, roi_level, row_map, level_counts = ops.assign_levels_images(proposal_targets.final_rois, self._min_level,
+                                                                                    self._max_level)
+        S = int(sorted_rois.shape[1])
+        maps = self._pooling_maps(p_list)
+
+        def pool():
+            return roi_pooling_images(maps, sorted_rois, roi_level, ops.ROI_NORM_IMAGE, self._roi_pooling._pool_size,
+                                      ops.ROI_POOL_MAX2, image_shape=image_shape, trainable=self._roi_pooling._trainable)
+
+        def rows(features):
+            return features.reshape((B * S,) + tuple(features.shape[2:]))
+
+        # (_training_roi_head's decision between the trainable and the plain forms)
+        if self._train_roi_head and any(m.requires_grad for m in maps):
+            roi_features = pool()
+            roi_score, roi_bboxes_txtytwth = self._get_trainable_roi_head()(rows(roi_features))
+        else:
+            with torch.no_grad():
+                roi_features = pool()
+                if not self._train_roi_head:
+                    roi_score, roi_bboxes_txtytwth = self._roi_head(rows(roi_features), training=True)
+            if self._train_roi_head:
+                roi_score, roi_bboxes_txtytwth = self._get_trainable_roi_head()(rows(roi_features))
+        roi_cls_loss, roi_reg_loss = fused_roi_losses(roi_score.float().reshape(B, S, -1), roi_bboxes_txtytwth.float().reshape(B, S, -1),
+                                                      proposal_targets, self._roi_sigma, row_map=row_map)
+        if self.keep_training_pass:
+            self.last_training_pass = dict(
+                rpn_score=rpn_score, rpn_deltas=rpn_deltas, maps=maps, anchors=anchors, rois=rois, roi_counts=roi_counts,
+                anchor_targets=anchor_targets, proposal_targets=proposal_targets, sorted_rois=sorted_rois, roi_level=roi_level,
+                row_map=row_map, level_counts=level_counts, roi_features=roi_features)
+        return rpn_cls_loss, rpn_reg_loss, roi_cls_loss, roi_reg_loss
 
     # ---- :326-362 (im_detect :364-390: CallerModel) ---------------------------------------------
     def predict_rpns(self, image_shape, gt_bboxes):
@@ -273,3 +358,6 @@ class ResnetV1Fpn(DenseParts, BaseFPN):
     def _get_roi_features(self, rois_list, p_list, image_shape):
         # the dense kernels keep maps channels_last [B,C,H,W]; the pooling layer takes the NHWC view of the same memory
         return super()._get_roi_features(rois_list, [_nhwc(p) for p in p_list], image_shape)
+
+    def _pooling_maps(self, p_list):
+        return [_nhwc(p) for p in super()._pooling_maps(p_list)]

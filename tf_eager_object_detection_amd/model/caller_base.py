@@ -65,6 +65,45 @@ def _image_nhwc(image):
     return image.float().contiguous()
 
 
+TRAINING_BATCH_MAX = ops.TARGETS_MAX_BATCH     # what one fused targets call produces
+
+
+def check_training_batch(inputs, training_targets, training_losses):
+    """the input rules of the batched training call -- (images [B,H,W,3], gt_bboxes [sum G,4], gt_labels [sum G], gt_offsets
+    int [B+1]) -- as a pure function (CPU tensors pass it): ValueError naming the reason, else (images, gt_bboxes, gt_labels,
+    the offsets as a list of B+1 Python ints: the call's one read of them)"""
+    if training_targets != 'hip' or training_losses != 'hip':
+        raise ValueError("the batched training call needs training_targets='hip' and training_losses='hip' (the batched stages "
+                         "exist only fused), got training_targets=%r, training_losses=%r" % (training_targets, training_losses))
+    if not isinstance(inputs, (tuple, list)) or len(inputs) != 4:
+        raise ValueError('the batched training call takes (images, gt_bboxes, gt_labels, gt_offsets)')
+    images, gt_bboxes, gt_labels, gt_offsets = inputs
+    if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[3] != 3:
+        raise ValueError('images must be a [B,H,W,3] tensor, got %s'
+                         % (tuple(images.shape) if isinstance(images, torch.Tensor) else type(images).__name__,))
+    B = int(images.shape[0])
+    if not 1 <= B <= TRAINING_BATCH_MAX:
+        raise ValueError('a training call takes 1 .. %d images, got %d' % (TRAINING_BATCH_MAX, B))
+    if not isinstance(gt_bboxes, torch.Tensor) or gt_bboxes.dim() != 2 or gt_bboxes.shape[1] != 4:
+        raise ValueError('gt_bboxes must be a [sum G,4] tensor (the images\' boxes packed in image order)')
+    G = int(gt_bboxes.shape[0])
+    if not isinstance(gt_labels, torch.Tensor) or gt_labels.numel() != G:
+        raise ValueError('gt_labels must hold one label per box of gt_bboxes (%d)' % G)
+    if isinstance(gt_offsets, torch.Tensor):
+        if gt_offsets.dim() != 1 or gt_offsets.is_floating_point() or gt_offsets.is_complex() or gt_offsets.dtype == torch.bool:
+            raise ValueError('gt_offsets must be a vector of B + 1 ints')
+        off = gt_offsets.tolist()
+    else:
+        off = list(gt_offsets)
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in off):
+            raise ValueError('gt_offsets must hold B + 1 ints')
+    if len(off) != B + 1:
+        raise ValueError('gt_offsets has %d entries for %d images (B + 1 wanted)' % (len(off), B))
+    if off[0] != 0 or any(b < a for a, b in zip(off, off[1:])) or off[-1] != G:
+        raise ValueError('gt_offsets must be non-decreasing from 0 to the number of boxes (%d), got %s' % (G, off))
+    return images, gt_bboxes, gt_labels, off
+
+
 class _Part(torch.nn.Module):
     """a dense part of a concrete model as a callable layer: `fn(x)` with keras' call signature"""
 
@@ -116,7 +155,8 @@ class CallerModel(torch.nn.Module):
       _rpn_score_rows             the RPN scores as [N, 2] (bg, fg) rows for the 'torch' RPN loss
       _rois_for_head              RoIs -> (what `_pool_rois` takes, the head rows' target rows or None)
       _pool_rois                  how its pooling layer is called
-      _start_training_call        per-call state of a training call (the single level's dropout image id)"""
+      _start_training_call        per-call state of a training call (the single level's dropout image id)
+      _batched_training, _training_batch   whether it has the batched training call (a four-tuple of inputs), and its pass (FPN)"""
 
     # What the training branches run with a backward pass.  BaseFPN sets these from its keywords; BaseFasterRcnn keeps the
     # reference's arguments, so its concrete models set them on the instance before they call its constructor.
@@ -128,6 +168,12 @@ class CallerModel(torch.nn.Module):
     grad_form = 'exact'        # the arithmetic of the trainable parts' gradient GEMMs: 'exact' | 'x3' (ops.grad_form)
     _rpn_layout = None
     _rpn_head_type = None
+    # The batched training call (a FOUR-tuple of inputs: check_training_batch).  A family that has it sets the flag and supplies
+    # `_training_batch`; keep_training_pass=True leaves the call's tensors in `last_training_pass` (references, no copies).
+    _batched_training = False
+    _training_targets = None
+    keep_training_pass = False
+    last_training_pass = None
 
     def _init_shared_layers(self, a):
         """the layers and attributes both families build from the reference's constructor arguments (`a`: name -> value), at the
@@ -144,6 +190,7 @@ class CallerModel(torch.nn.Module):
                    'nms_iou_threshold'))
         sampling = ('pos_iou_threshold', 'neg_iou_threshold', 'total_num_samples', 'max_pos_samples')
         # training_targets: 'torch' = AnchorTarget / ProposalTarget (generator-driven sampling), 'hip' = the fused stage
+        self._training_targets = a['training_targets']
         self._anchor_target, self._proposal_target = training_target_layers(
             a['training_targets'], dict(pick('rpn_training_', *sampling), **rpn_code),
             dict(pick('roi_training_', *sampling), num_classes=a['num_classes'], target_means=a['roi_proposal_means'],
@@ -199,6 +246,8 @@ class CallerModel(torch.nn.Module):
             return self._forward(inputs, training)
 
     def _forward(self, inputs, training):
+        if training and isinstance(inputs, (tuple, list)) and len(inputs) == 4:
+            return self._forward_images(inputs)
         if training:
             image, gt_bboxes, gt_labels = inputs
         else:
@@ -226,6 +275,24 @@ class CallerModel(torch.nn.Module):
                                        extractor_stride=self._extractor_stride, num_classes=self.num_classes)
 
     call = forward
+
+    def _forward_images(self, inputs):
+        """the batched training call: (images [B,H,W,3], gt_bboxes [sum G,4], gt_labels [sum G], gt_offsets int [B+1]) -> four
+        float32 [B] tensors (rpn_cls, rpn_reg, roi_cls, roi_reg per image).  Every refusal comes before any state changes."""
+        if not self._batched_training:
+            raise ValueError('%s: the batched training call (a four-tuple of inputs) is built for the FPN family only -- a '
+                             'single-level model needs one dropout image id per image of the batch, which is a change of its '
+                             'own; call it with (image, gt_bboxes, gt_labels) per image' % type(self).__name__)
+        images, gt_bboxes, gt_labels, off = check_training_batch(inputs, self._training_targets, self._training_losses)
+        if not images.is_cuda:
+            raise ops.L.OdetError('images must live on the GPU: tf_eager_object_detection_amd has no CPU path')
+        gt_offsets = inputs[3]
+        if not (isinstance(gt_offsets, torch.Tensor) and gt_offsets.is_cuda and gt_offsets.dtype == torch.int32):
+            gt_offsets = torch.tensor(off, dtype=torch.int32, device=images.device)
+        return self._training_batch(images.float().contiguous(), gt_bboxes, gt_labels, gt_offsets.contiguous())
+
+    def _training_batch(self, images, gt_bboxes, gt_labels, gt_offsets):
+        raise NotImplementedError
 
     def _torch_losses(self, rpn_score, rpn_bbox_txtytwth, anchors, rois, gt_bboxes, gt_labels, maps, image_shape, training):
         """training_losses='torch' (base_fpn_model.py:232-264, base_faster_rcnn_model.py:155-185): the target layers' dense outputs

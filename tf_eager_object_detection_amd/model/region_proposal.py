@@ -26,12 +26,13 @@ class RegionProposal(torch.nn.Module):
         self._target_means = [0, 0, 0, 0] if target_means is None else target_means
         self._target_stds = [1, 1, 1, 1] if target_stds is None else target_stds
 
-    def padded(self, inputs, training=None):
-        """Sync-free form: (rois [K,4] padded, kept anchor idx int32 [K], count int32[1] on device)."""
+    def padded(self, inputs, training=None, out=None):
+        """Sync-free form: (rois [K,4] padded, kept anchor idx int32 [K], count int32[1] on device).  ``out`` = preallocated
+        (rois, idx, count) to write into (the batched training call: views of one [B,K,...] tensor each)."""
         bboxes_txtytwth, anchors, scores, image_shape = inputs
         num_post_nms = self._num_post_nms_train if training else self._num_post_nms_test   # :73
         return ops.region_proposal(bboxes_txtytwth, anchors, scores, image_shape, num_post_nms,
-                                   self._nms_iou_threshold, self._target_means, self._target_stds)
+                                   self._nms_iou_threshold, self._target_means, self._target_stds, out=out)
 
     @torch.no_grad()
     def forward(self, inputs, training=None, mask=None):

@@ -339,6 +339,39 @@ def assign_levels(rois, min_level, max_level, count_dev=None, out=None):
     return out, lvl[:n], perm[:n], counts
 
 
+ASSIGN_IMAGES_MAX_BATCH = 64   # ODET_ASSIGN_MAX_BATCH (= TARGETS_MAX_BATCH: what one targets call produces)
+
+
+def assign_levels_images(rois, min_level, max_level, count_dev=None, out=None):
+    """assign_levels for B images in ONE launch: rois [B,n,4], count_dev int32 [B] (None: n RoIs in every image)
+    -> (sorted rois [B,n,4], level int32 [B,n] (0-based), perm int64 [B,n] (rows inside the image), counts int32 [B,L]).
+    Image b's rows below its count and counts[b] are assign_levels' on image b alone, bit for bit; the rows from its count on
+    are not written.  ``out`` = preallocated (sorted rois, level, perm, counts) to reuse."""
+    rois = L.f32c(rois, 'all_rois')
+    if rois.dim() != 3 or rois.shape[2] != 4:
+        raise ValueError('all_rois must have shape [B,n,4], got %s' % (tuple(rois.shape),))
+    B, n = int(rois.shape[0]), int(rois.shape[1])
+    nl = int(max_level) - int(min_level) + 1
+    if count_dev is not None and (count_dev.dtype != torch.int32 or count_dev.numel() != B):
+        raise ValueError('count_dev must be int32 [%d], got %s %s' % (B, count_dev.dtype, tuple(count_dev.shape)))
+    if out is not None:
+        out, lvl, perm, counts = out
+        if tuple(out.shape) != (B, n, 4) or tuple(lvl.shape) != (B, n) or tuple(perm.shape) != (B, n) or \
+                counts.numel() != B * max(nl, 0):
+            raise ValueError('out must be (sorted rois [%d,%d,4], level [%d,%d], perm [%d,%d], counts [%d,%d])'
+                             % (B, n, B, n, B, n, B, nl))
+    else:
+        out = torch.empty_like(rois)
+        lvl = torch.empty((B, n), dtype=torch.int32, device=rois.device)
+        perm = torch.empty((B, n), dtype=torch.int64, device=rois.device)
+        counts = torch.empty((B, max(nl, 0)), dtype=torch.int32, device=rois.device)
+    L.check(L.lib().odet_assign_levels_images(L.dptr(rois), B, n, L.dptr(count_dev, torch.int32, 'count_dev'), int(min_level),
+                                              int(max_level), L.dptr(out, torch.float32, 'out'), L.dptr(lvl, torch.int32, 'level'),
+                                              L.dptr(perm, torch.int64, 'perm'), L.dptr(counts, torch.int32, 'counts'),
+                                              L.stream()))
+    return out, lvl, perm, counts
+
+
 def fpn_topdown_merge(top, lateral, out=None):
     """P_k = 0.5 * tf.image.resize_bilinear(P_{k+1}, size(lateral)) + 0.5 * lateral (reference
     model/fpn/resnet_fpn.py:385-398, TF 1.x legacy resize) in one launch.  ``top`` [B,h,w,C] and

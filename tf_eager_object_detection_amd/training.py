@@ -358,13 +358,20 @@ class GradientAccumulator:
     and strides (None where the gradient is absent): the same tensors in every window, so the optimizer's pointer column is
     uploaded once (and the next window overwrites them).  The set of present gradients is fixed by a window's first image; a
     later image with another set raises ValueError and leaves the window as it was.  images == 1 returns the gradients as given,
-    with no launch.  CPU tensors run the same steps in torch ops."""
+    with no launch.  CPU tensors run the same steps in torch ops.
 
-    def __init__(self, variables, images, average=True):
+    `divisor` (default: `images`) is what the window's sum is divided by.  A caller whose add() brings the SUM of several images'
+    gradients (Trainer with images_per_call = B: a window of W = K / B calls) passes divisor = K.  With images == 1 and a
+    divisor above 1 the one call is a window's first and last at once: ONE launch with first = 1 and that divisor."""
+
+    def __init__(self, variables, images, average=True, divisor=None):
         self.variables = list(variables)
         self.images = int(images)
         if self.images < 1:
             raise ValueError('images must be at least 1, got %d' % self.images)
+        self.divisor = self.images if divisor is None else int(divisor)
+        if self.divisor < 1 or self.divisor >= 1 << 24:
+            raise ValueError('divisor must lie in 1 .. 2^24 - 1, got %d' % self.divisor)
         for i, v in enumerate(self.variables):
             if v.dtype != torch.float32:
                 raise TypeError('variable %d must be float32, got %s' % (i, v.dtype))
@@ -395,14 +402,14 @@ class GradientAccumulator:
         from . import parallel
         gradients = list(gradients)
         parallel.check_gradients(self.variables, gradients)
-        if self.images == 1:
+        if self.images == 1 and (self.divisor == 1 or not self.average):
             return gradients
         numels = tuple(None if g is None else g.numel() for g in gradients)
         if self._count and numels != self._key:
             raise ValueError('image %d of the window has another set of present gradients than its first image' % (self._count + 1))
         lay = self._layout(numels)
         first, last = self._count == 0, self._count + 1 == self.images
-        divisor = float(self.images) if (last and self.average) else 1.0        # (float32(K) exactly: K < 2^24)
+        divisor = float(self.divisor) if (last and self.average) else 1.0       # (float32(K) exactly: K < 2^24)
         if lay.tables.bucket_numel:
             if lay.bucket.is_cuda:
                 ops.bucket_accumulate(lay.tables, gradients, lay.bucket, first, divisor)
@@ -419,7 +426,7 @@ class GradientAccumulator:
     def state_dict(self):
         """the open window: its count, its set of present gradients and a host copy of its bucket"""
         open_ = self._count > 0
-        return {'images': self.images, 'average': self.average, 'count': self._count,
+        return {'images': self.images, 'average': self.average, 'divisor': self.divisor, 'count': self._count,
                 'numels': list(self._key) if open_ else None,
                 'bucket': self._layouts[self._key].bucket.detach().cpu().clone() if open_ else None}
 
@@ -427,6 +434,9 @@ class GradientAccumulator:
         if int(state['images']) != self.images or bool(state['average']) != self.average:
             raise ValueError('state of an accumulator over %d images (average=%s), this one has %d (average=%s)'
                              % (state['images'], state['average'], self.images, self.average))
+        if int(state.get('divisor', state['images'])) != self.divisor:       # (a state from before the key: divisor = images)
+            raise ValueError('state of an accumulator that divides by %d, this one divides by %d'
+                             % (int(state.get('divisor', state['images'])), self.divisor))
         count = int(state['count'])
         if not 0 <= count < self.images:
             raise ValueError('an open window holds 0 .. %d images, got %d' % (self.images - 1, count))
@@ -472,34 +482,52 @@ class Trainer:
     holds the parameters), with an optimizer step every `images_per_step` images on the images' mean gradient
     (GradientAccumulator) and a state that resumes a run exactly: the parameters, the optimizer's slots and step, the number of
     images seen -- which is the Philox image id of the target samplers and the dropout -- and the open window.
-    weight_decay: None, or the L2 coefficient of l2_variables.  The image summaries and TensorBoard are not built."""
+    weight_decay: None, or the L2 coefficient of l2_variables.  The image summaries and TensorBoard are not built.
+    images_per_call=B (the FPN family's batched training call; images_per_step must be a multiple): a step is K / B calls of B
+    images each, one backward() per call."""
 
     LOG_FORMAT = 'steps %d, lr is %.5f, loss: %.4f, %.4f, %.4f, %.4f, %.4f, %.4f'           # train.py:150
 
-    def __init__(self, model, optimizer, images_per_step=1, learning_rate_bias_double=False, weight_decay=None):
+    def __init__(self, model, optimizer, images_per_step=1, learning_rate_bias_double=False, weight_decay=None, images_per_call=1):
         self.model, self.optimizer = model, optimizer
         self.learning_rate_bias_double = bool(learning_rate_bias_double)
+        self.images_per_step, self.images_per_call = int(images_per_step), int(images_per_call)
+        if self.images_per_call < 1 or self.images_per_step < 1 or self.images_per_step % self.images_per_call:
+            raise ValueError('images_per_step (%d) must be a positive multiple of images_per_call (%d)'
+                             % (self.images_per_step, self.images_per_call))
         self.named = model_variables(model.dense)
         self.weight_decays = None if weight_decay is None else l2_variables(model.dense, weight_decay)
-        self.accumulator = GradientAccumulator([p for _, p in self.named], images_per_step)
+        # a window of W = K / B calls: a call brings the SUM over its B images, the window's sum is divided by float32(K) once
+        self.accumulator = GradientAccumulator([p for _, p in self.named], self.images_per_step // self.images_per_call,
+                                               divisor=self.images_per_step)
         self.images_seen = 0
         self.l2_loss = None           # of the last optimizer step's pre-update values (a device tensor), with weight_decay
 
     def step(self, inputs):
-        """inputs: (image, gt_bboxes, gt_labels) of ONE image.  Returns (the image's four losses as detached device tensors,
-        whether the optimizer stepped)."""
+        """inputs: (image, gt_bboxes, gt_labels) of ONE image, or the batched call's (images, gt_bboxes, gt_labels, gt_offsets)
+        of exactly `images_per_call` images (the only form when that is above 1).  The call's gradient is ONE backward() of the
+        sum of its losses; the step's gradient is the calls' gradients added in ascending call order, divided by
+        float32(images_per_step) once.  The images get the ids images_seen .. images_seen + B - 1.  Returns (the call's four
+        losses as detached device tensors -- scalars for the three-tuple, [B] for the four-tuple --, whether the optimizer
+        stepped)."""
         m = self.model
+        batched = isinstance(inputs, (tuple, list)) and len(inputs) == 4
+        if not batched and self.images_per_call != 1:
+            raise ValueError('images_per_call=%d: step takes (images, gt_bboxes, gt_labels, gt_offsets)' % self.images_per_call)
+        if batched and (not isinstance(inputs[0], torch.Tensor) or inputs[0].dim() != 4
+                        or int(inputs[0].shape[0]) != self.images_per_call):
+            raise ValueError('step takes exactly images_per_call=%d images per call' % self.images_per_call)
         image_id = self.images_seen
         m._anchor_target._next_image_id = image_id
         m._proposal_target._next_image_id = image_id
         if hasattr(m, '_next_dropout_image_id'):
             m._next_dropout_image_id = image_id
         losses = m(inputs, True)
-        sum(losses).backward()
+        (sum(x.sum() for x in losses) if batched else sum(losses)).backward()
         gradients = self.accumulator.add([p.grad for _, p in self.named])
         for _, p in self.named:
             p.grad = None
-        self.images_seen += 1
+        self.images_seen += self.images_per_call
         if gradients is not None:
             out = train_step(self.named, gradients, self.optimizer, learning_rate_bias_double=self.learning_rate_bias_double,
                              weight_decays=self.weight_decays, l2=self.weight_decays is not None)
@@ -535,12 +563,13 @@ class Trainer:
 
     # ---- the loop ---------------------------------------------------------------------------------------------------------------
     def train_one_epoch(self, dataset, logging_every_n_steps=20, save_every_n_steps=5000, save_path=None):
-        """train.py:77-159 over an iterable of (image, gt_bboxes, gt_labels); idx counts images, as the reference's does"""
+        """train.py:77-159 over an iterable of step()'s inputs; idx counts calls (images, as the reference's does, with one image
+        per call); a batched call logs the mean of its images' losses"""
         idx = 0
         for inputs in dataset:
             losses, _ = self.step(inputs)
             if idx % logging_every_n_steps == 0:
-                four = [float(x) for x in losses]
+                four = [float(x.mean()) for x in losses]
                 l2 = 0.0 if self.l2_loss is None else float(self.l2_loss)
                 lr = learning_rate_at(self.optimizer._schedule, self.global_step())
                 print(self.LOG_FORMAT % ((idx + 1, lr) + tuple(four) + (l2, sum(four) + l2)), flush=True)
